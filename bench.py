@@ -12,11 +12,15 @@ traffic is the timing barrier, a MAX-reduce of the elapsed time and the gather o
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 ... bench.py --gpus 4     # the driver's form
 
 `n_gpus` in the result is the number of ranks that actually ran (WORLD_SIZE), each on its own device (listed under
-`ranks`); `--gpus` that disagrees with WORLD_SIZE is an error.  Before timing, EVERY document of the shard is compared
-with the CPU checker (oracle/_ref = the compiled reference when present, else the oracle port): id offsets and every id,
-exactly -- a mismatch refuses to time.
+`ranks`); `--gpus` that disagrees with WORLD_SIZE is an error.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline`, `cpu_baseline` and `timings`.
+A plain run sets up, warms up, times --steps steps and prints the line.  `--full` adds everything else the line used to
+carry: before timing, EVERY document of the shard is compared with the CPU checker (oracle/_ref = the compiled reference
+when present, else the oracle port): id offsets and every id, exactly -- a mismatch refuses to time; after timing, the
+PCIe-inclusive and host-API timings, the lexer's gather roofline and the CPU baseline.  `--verify` overrides the first
+in either form.  `--dump-outputs DIR` writes a fixed, seeded sample of the last timed step's outputs as DIR/<name>.npy.
+
+Prints ONE JSON line (rank 0) with the driver's contract keys plus `roofline` (and with --full `cpu_baseline` and `timings`).
 """
 import argparse
 import ctypes
@@ -59,13 +63,79 @@ def parse_args():
     ap.add_argument("--sub-batch-docs", type=int, default=0, help="documents per TextToIdsBatchDevice call (0 = auto: whole shard if the workspace fits)")
     ap.add_argument("--model", default="")
     ap.add_argument("--variant", type=int, default=-1, help="kernel variant (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also verify against the CPU checker, take the extra timings and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-docs", type=int, default=0)
-    ap.add_argument("--verify", default="full", help="'full' (default): every document of the shard against the CPU checker; N: the first N; 0: none")
-    ap.add_argument("--no-extra-timings", action="store_true", help="skip the PCIe-inclusive / host-API timings and the lexer transition count")
+    ap.add_argument("--verify", default=None, help="'full' (default with --full): every document of the shard against the CPU checker; N: the first N; 0: none (default without --full)")
+    ap.add_argument("--no-extra-timings", action="store_true", help="with --full: skip the PCIe-inclusive / host-API timings and the lexer transition count")
     ap.add_argument("--offsets", action="store_true", help="time TextToIdsWithOffsetsBatchDevice (ids + byte offsets of every id) instead of TextToIdsBatchDevice; single-process form only")
     ap.add_argument("--inproc", action="store_true", help="N GPUs from ONE process through the library (BfSetDevices + the per-range handles, a thread per device) instead of N ranks")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write a fixed, seeded sample of the last timed step's outputs as DIR/<name>.npy (<= 64 MB)")
+    args = ap.parse_args()
+    if args.verify is None:
+        args.verify = "full" if args.full else "0"
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra_timings = True
+    return args
+
+
+# --dump-outputs: what the timed path hands its caller, as a sample that is the same for every run of the same arguments
+DUMP_SEED = 20240601
+DUMP_COUNT_DOCS = 1 << 21        # documents whose output length is written: 2 M x (4 + 8) bytes = 24 MB
+DUMP_ROW_DOCS = 16384            # documents whose every output element is written ...
+DUMP_ROW_BYTES = 32 << 20        # ... as long as their elements fit this many bytes
+
+
+def dump_outputs(path, ndocs, parts, prefix="", share=1):
+    """Writes the outputs of the last timed step as path/<prefix><name>.npy.  parts: [(d0, d1, row_off, {name: per-element tensor})] in
+    document order, covering documents [0, ndocs): row_off int64[d1 - d0 + 1] are the offsets of every document's elements (id offsets,
+    or byte offsets of TextToWords' output).  Written: the output length of a seeded sample of documents (`counts`, `counts_docs`),
+    every element of a second seeded sample (`<name>`, `rows_docs`, `rows_offsets`), and `total` = the elements of all documents.
+    Element arrays are float32 (ids and bytes: exact below 2^24), offsets and indices float64.  `share` divides the budget among ranks."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def lengths(docs):
+        out = np.zeros(len(docs), dtype=np.int64)
+        for d0, d1, row_off, _ in parts:
+            sel = np.nonzero((docs >= d0) & (docs < d1))[0]
+            if len(sel):
+                t = torch.from_numpy(docs[sel] - d0).to(row_off.device)
+                out[sel] = (row_off[t + 1] - row_off[t]).cpu().numpy()
+        return out
+
+    cnt_docs = np.sort(rng.choice(ndocs, min(ndocs, DUMP_COUNT_DOCS // share), replace=False))
+    row_docs = rng.choice(ndocs, min(ndocs, DUMP_ROW_DOCS // share), replace=False)
+    names = list(parts[0][3])
+    elem_bytes = sum(4 if k in ("ids", "bytes") else 8 for k in names)
+    n = lengths(row_docs)
+    keep = np.cumsum(n * elem_bytes) <= DUMP_ROW_BYTES // share                 # a prefix of the random order, then document order
+    row_docs = np.sort(row_docs[:int(keep.sum())])
+    rows = {k: [] for k in names}
+    for d0, d1, row_off, arrays in parts:
+        loc = row_docs[(row_docs >= d0) & (row_docs < d1)] - d0
+        if not len(loc):
+            continue
+        t = torch.from_numpy(loc).to(row_off.device)
+        a, z = row_off[t].cpu().numpy(), row_off[t + 1].cpu().numpy()
+        idx = torch.from_numpy(np.concatenate([np.arange(x, y, dtype=np.int64) for x, y in zip(a, z)])).to(row_off.device)
+        for k in names:
+            rows[k].append(arrays[k][idx].cpu().numpy())
+    row_len = lengths(row_docs)
+    out = {"counts": lengths(cnt_docs).astype(np.float32), "counts_docs": cnt_docs.astype(np.float64),
+           "rows_docs": row_docs.astype(np.float64), "rows_offsets": np.concatenate([[0], np.cumsum(row_len)]).astype(np.float64),
+           "total": np.array([sum(int(p[2][-1].item()) for p in parts)], dtype=np.float64)}
+    for k in names:
+        v = np.concatenate(rows[k]) if rows[k] else np.zeros(0, dtype=np.int64)
+        if k in ("ids", "bytes"):
+            assert not len(v) or int(np.abs(v).max()) < (1 << 24), "bench: %s beyond float32's exact integers" % k
+            out[k] = v.astype(np.float32)
+        else:
+            out[k] = v.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v)
 
 
 def free_port():
@@ -172,6 +242,8 @@ def run_config1(args):
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     gpu_ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, nl, [(0, nl, t_off, {"bytes": out})])
     out_bytes = int(t_off[-1].item())
     alg = len(text) + out_bytes + 16 * nl
     res = {"metric": "lines/sec", "value": nl * args.steps / elapsed, "unit": "lines/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -288,6 +360,8 @@ def run_inproc(args):
     for pt in parts:
         pt["kms"][:] = 0
     elapsed = run_all(args.steps, collect=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, total_docs, [(b["d0"], b["d1"], b["id_off"], {"ids": b["ids"]}) for pt in parts for b in pt["batches"]])
     ranks = []
     for pt in parts:
         props = torch.cuda.get_device_properties(pt["dev"])
@@ -498,6 +572,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kms /= max(args.steps, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ndocs, [(b["d0"], b["d1"], b["id_off"], dict(ids=b["ids"], **({"starts": b["starts"], "ends": b["ends"]} if args.offsets else {})))
+                                                for b in batches], prefix="rank%d_" % rank if world > 1 else "", share=world)
     n_ids = sum(int(b["id_off"][-1].item()) for b in batches)
     status = bf.lib().BfLastStatus(h)
 

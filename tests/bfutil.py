@@ -107,6 +107,39 @@ def reference():
     return _T2I(REF_LIB, "LoadModel", "TextToIds", "FreeModel")
 
 
+REF_ANSWERS = os.path.join(ROOT, "tests", "golden", "ref_answers")
+
+
+def reference_answers(name, compute):
+    """The compiled reference's answers to a test's fixed inputs, as JSON values.  Where oracle/_ref is built, `compute()` asks the live
+    reference and the answers must equal the stored copy tests/golden/ref_answers/<name>.json.gz (BF_WRITE_REF_ANSWERS=1 rewrites it);
+    elsewhere the stored copy stands in for the reference."""
+    import gzip
+    import json
+    path = os.path.join(REF_ANSWERS, name + ".json.gz")
+    if have_ref():
+        got = json.loads(json.dumps(compute()))
+        if os.environ.get("BF_WRITE_REF_ANSWERS") == "1":
+            os.makedirs(REF_ANSWERS, exist_ok=True)
+            with gzip.GzipFile(path, "wb", mtime=0) as f:
+                f.write(json.dumps(got, separators=(",", ":")).encode())
+        else:
+            with gzip.open(path, "rb") as f:
+                assert json.loads(f.read()) == got, "the live reference differs from %s" % path
+        return got
+    with gzip.open(path, "rb") as f:
+        return json.loads(f.read())
+
+
+def trim_ids(r, sentinel=-7):
+    """(count, buffer) of _T2I.text_to_ids without the buffer's untouched tail: what a stored answer keeps"""
+    c, buf = r
+    n = len(buf)
+    while n and buf[n - 1] == sentinel:
+        n -= 1
+    return [c, list(buf[:n]), len(buf)]
+
+
 def checker_lib_path():
     """the CPU TextToIds used as golden/CPU baseline: the compiled reference when present, else the oracle port"""
     return (REF_LIB, "reference") if have_ref() else (ORACLE_LIB, "port")

@@ -48,18 +48,30 @@ def test_known_answer_gpt2():
     ora.free(h)
 
 
-@pytest.mark.skipif(not bfutil.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("model", I2W_MODELS)
 def test_oracle_vs_live_reference(model):
+    """the live reference where oracle/_ref is built, its stored answers to the same calls elsewhere (bfutil.reference_answers)"""
     ora, f = _oracle_fn()
-    ref = bfutil.reference()
-    g = ref.lib.IdsToText
-    g.restype = ctypes.c_int
-    g.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_bool]
-    ho, hr = ora.load(bfutil.model_path(model)), ref.load(bfutil.model_path(model))
-    cnt = ora.lib.bfo_i2w_count(ho)
-    for ids, mx, skip in _cases(cnt, 1500, 5):
-        assert _run(f, ctypes.c_void_p(ho), ids, mx, skip) == _run(g, ctypes.c_void_p(hr), ids, mx, skip, True), (model, ids[:8], mx, skip)
+    ho = ora.load(bfutil.model_path(model))
+    calls = list(_cases(ora.lib.bfo_i2w_count(ho), 1500, 5))
+
+    def ask_reference():
+        ref = bfutil.reference()
+        g = ref.lib.IdsToText
+        g.restype = ctypes.c_int
+        g.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_bool]
+        hr = ref.load(bfutil.model_path(model))
+        out = []
+        for ids, mx, skip in calls:
+            r, text = _run(g, ctypes.c_void_p(hr), ids, mx, skip, True)
+            out.append([r, text.hex()])
+        ref.free(hr)
+        return out
+
+    want = bfutil.reference_answers("ids_to_text_" + model, ask_reference)
+    assert len(want) == len(calls)
+    for (ids, mx, skip), (r, text) in zip(calls, want):
+        assert _run(f, ctypes.c_void_p(ho), ids, mx, skip) == (r, bytes.fromhex(text)), (model, ids[:8], mx, skip)
     ora.free(ho)
 
 

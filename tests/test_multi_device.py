@@ -120,7 +120,7 @@ def test_set_devices_rejects_devices_the_box_does_not_have():
 def _bench(extra, env_extra):
     env = dict(os.environ)
     env.update(env_extra)
-    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--docs", "40000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings"] + extra
+    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--full", "--docs", "40000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
@@ -181,7 +181,7 @@ def test_eight_ranks_of_the_bench_on_one_device(extra):
     disjoint ranges that cover the corpus, every document verified, status 0 (BF_BENCH_SHARE_GPU=1: all on device 0, over gloo)"""
     env = dict(os.environ)
     env["BF_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--docs", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings", "--gpus", "8"] + extra
+    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--full", "--docs", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings", "--gpus", "8"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads(out.stdout.strip().splitlines()[-1])

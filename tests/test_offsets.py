@@ -31,19 +31,27 @@ def test_readme_known_answer_offsets():
     assert toks[-8:] == [" дев", "у", "шку", " с", " теле", "скоп", "ом", "."]
 
 
-@pytest.mark.skipif(not bfutil.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("model", MODELS)
 def test_oracle_offsets_vs_live_reference(model):
+    """the live reference where oracle/_ref is built, its stored answers to the same calls elsewhere (bfutil.reference_answers)"""
     if not bfutil.have_model(model):
         pytest.skip("%s not present" % model)
-    ora, ref = bfutil.oracle(), bfutil.reference()
-    ho, hr = ora.load(bfutil.model_path(model)), ref.load(bfutil.model_path(model))
-    for k, b in enumerate(_docs(800, 91)):
-        mx = (64, 3, 512)[k % 3]
-        unk = (0, 100)[k % 2]
-        assert ora.with_offsets(ho, b, mx, unk, "bfo_text_to_ids_with_offsets") == ref.with_offsets(hr, b, mx, unk, "TextToIdsWithOffsets"), (model, b[:60])
+    calls = [(b, (64, 3, 512)[k % 3], (0, 100)[k % 2]) for k, b in enumerate(_docs(800, 91))]
+
+    def ask_reference():
+        ref = bfutil.reference()
+        hr = ref.load(bfutil.model_path(model))
+        out = [ref.with_offsets(hr, b, mx, unk, "TextToIdsWithOffsets") for b, mx, unk in calls]
+        ref.free(hr)
+        return out
+
+    want = bfutil.reference_answers("text_to_ids_with_offsets_" + model, ask_reference)
+    assert len(want) == len(calls)
+    ora = bfutil.oracle()
+    ho = ora.load(bfutil.model_path(model))
+    for (b, mx, unk), w in zip(calls, want):
+        assert list(ora.with_offsets(ho, b, mx, unk, "bfo_text_to_ids_with_offsets")) == w, (model, b[:60])
     ora.free(ho)
-    ref.free(hr)
 
 
 @pytest.mark.parametrize("model", MODELS)

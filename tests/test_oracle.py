@@ -89,18 +89,25 @@ def test_oracle_matches_committed_reference_fixtures(ora, fname):
     ora.free(h)
 
 
-@pytest.mark.skipif(not bfutil.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("model", ["bert_base_tok.bin", "bert_base_cased_tok.bin", "wbd.bin", "gpt2.bin", "roberta.bin", "xlnet.bin",
                                    "bpe_example.bin", "xlm_roberta_base.bin", "laser500k.bin", "bert_chinese.bin"])
 def test_oracle_vs_live_reference(ora, model):
+    """the live reference where oracle/_ref is built, its stored answers to the same calls elsewhere (bfutil.reference_answers)"""
     if not bfutil.have_model(model):
         pytest.skip("%s not present" % model)
-    ref = bfutil.reference()
-    ho, hr = ora.load(bfutil.model_path(model)), ref.load(bfutil.model_path(model))
     docs = list(bfutil.ADVERSARIAL) + bfutil.fuzz_docs(1500, seed=77)
-    for k, b in enumerate(docs):
-        mx = (0, 1, 3, 16, 64, 512)[k % 6]
-        unk = (0, 100, 3, 257)[k % 4]
-        assert ora.text_to_ids(ho, b, mx, unk) == ref.text_to_ids(hr, b, mx, unk), (model, b[:60], mx, unk)
+    calls = [(b, (0, 1, 3, 16, 64, 512)[k % 6], (0, 100, 3, 257)[k % 4]) for k, b in enumerate(docs)]
+
+    def ask_reference():
+        ref = bfutil.reference()
+        hr = ref.load(bfutil.model_path(model))
+        out = [bfutil.trim_ids(ref.text_to_ids(hr, b, mx, unk)) for b, mx, unk in calls]
+        ref.free(hr)
+        return out
+
+    want = bfutil.reference_answers("text_to_ids_" + model, ask_reference)
+    assert len(want) == len(calls)
+    ho = ora.load(bfutil.model_path(model))
+    for (b, mx, unk), w in zip(calls, want):
+        assert bfutil.trim_ids(ora.text_to_ids(ho, b, mx, unk)) == w, (model, b[:60], mx, unk)
     ora.free(ho)
-    ref.free(hr)

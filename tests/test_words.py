@@ -22,6 +22,15 @@ def _call(fn, args_before, b, mx, args_after=()):
     return r, o.raw, list(s), list(e)
 
 
+def _stored(r):
+    """a _call result as a stored answer (bfutil.reference_answers): the buffers without their untouched tails"""
+    n, raw, st, en = r
+    k = len(st)
+    while k and st[k - 1] == -7 and en[k - 1] == -7:
+        k -= 1
+    return [n, raw.rstrip(b"\x7f").hex(), len(raw), st[:k], en[:k], len(st)]
+
+
 def _oracle_fn():
     ora = bfutil.oracle()
     f = ora.lib.bfo_text_to_words_with_offsets
@@ -41,19 +50,32 @@ def test_readme_known_answer():
     ora.free(h)
 
 
-@pytest.mark.skipif(not bfutil.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
+def _reference_answers(name, fn_name, model, calls):
+    """the reference's TextToWords / TextToSentences answers to `calls` (live where oracle/_ref is built, else stored: bfutil.reference_answers)"""
+    def ask_reference():
+        ref = bfutil.reference()
+        g = getattr(ref.lib, fn_name)
+        g.restype = ctypes.c_int
+        g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        hr = ref.load(bfutil.model_path(model)) if model else None      # None = the reference's built-in model
+        out = [_stored(_call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,))) for b, mx in calls]
+        if hr:
+            ref.free(hr)
+        return out
+
+    want = bfutil.reference_answers("%s_%s" % (name, model or "built_in"), ask_reference)
+    assert len(want) == len(calls)
+    return want
+
+
 @pytest.mark.parametrize("model", WORD_MODELS + [None])
 def test_oracle_words_vs_live_reference(model):
     ora, f = _oracle_fn()
-    ref = bfutil.reference()
-    g = ref.lib.TextToWordsWithOffsetsWithModel
-    g.restype = ctypes.c_int
-    g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    calls = [(b, (4 * len(b) + 8, 5, 0)[k % 3]) for k, b in enumerate(_docs(1500, 61))]
+    want = _reference_answers("text_to_words", "TextToWordsWithOffsetsWithModel", model, calls)
     ho = ora.load(bfutil.model_path(model or "wbd.bin"))
-    hr = ref.load(bfutil.model_path(model)) if model else None      # None = the reference's built-in model
-    for k, b in enumerate(_docs(1500, 61)):
-        mx = (4 * len(b) + 8, 5, 0)[k % 3]
-        assert _call(f, (ctypes.c_void_p(ho),), b, mx) == _call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,)), (model, b[:60], mx)
+    for (b, mx), w in zip(calls, want):
+        assert _stored(_call(f, (ctypes.c_void_p(ho),), b, mx)) == w, (model, b[:60], mx)
     ora.free(ho)
 
 
@@ -168,19 +190,14 @@ def test_sentences_readme_known_answer():
     ora.free(h)
 
 
-@pytest.mark.skipif(not bfutil.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("model", SENT_MODELS + [None])
 def test_oracle_sentences_vs_live_reference(model):
     ora, f = _oracle_sent_fn()
-    ref = bfutil.reference()
-    g = ref.lib.TextToSentencesWithOffsetsWithModel
-    g.restype = ctypes.c_int
-    g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+    calls = [(b, (4 * len(b) + 8, 5, 0)[k % 3]) for k, b in enumerate(_docs(1500, 83) + SENT_DOCS)]
+    want = _reference_answers("text_to_sentences", "TextToSentencesWithOffsetsWithModel", model, calls)
     ho = ora.load(bfutil.model_path(model or "sbd.bin"))
-    hr = ref.load(bfutil.model_path(model)) if model else None      # None = the reference's built-in model
-    for k, b in enumerate(_docs(1500, 83) + SENT_DOCS):
-        mx = (4 * len(b) + 8, 5, 0)[k % 3]
-        assert _call(f, (ctypes.c_void_p(ho),), b, mx) == _call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,)), (model, b[:60], mx)
+    for (b, mx), w in zip(calls, want):
+        assert _stored(_call(f, (ctypes.c_void_p(ho),), b, mx)) == w, (model, b[:60], mx)
     ora.free(ho)
 
 

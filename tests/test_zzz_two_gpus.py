@@ -41,7 +41,7 @@ def test_two_physical_devices():
         bf.free_model(h)
     env = dict(os.environ)
     env.pop("BF_BENCH_SHARE_GPU", None)
-    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--gpus", "2", "--docs", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings"]
+    cmd = [sys.executable, os.path.join(bfutil.ROOT, "bench.py"), "--full", "--gpus", "2", "--docs", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-timings"]
     for extra in ([], ["--inproc"]):
         out = subprocess.run(cmd + extra, capture_output=True, text=True, env=env, timeout=900)
         assert out.returncode == 0, out.stderr[-2000:]

@@ -12,7 +12,7 @@ root=${GRAFT_REPO_ROOT:-$PWD}
 git -C $root rev-parse HEAD > $O/head.txt 2>/dev/null
 line() { # name, bench args...: the bench line of a configuration
   local name=$1; shift
-  timeout 900 python $root/bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err
+  timeout 900 python $root/bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err
   python - $O/bench_$name.json $name <<'PY'
 import json, sys
 try:

@@ -13,8 +13,8 @@ try:
 except Exception as e: print(sys.argv[2], "failed", e)
 PY
 }
-timeout 300 python bench.py --workload config3 --no-cpu-baseline --no-extra-timings > $O/bench_config3.json 2> $O/bench_config3.err; show $O/bench_config3.json "config3"
+timeout 300 python bench.py --full --workload config3 --no-cpu-baseline --no-extra-timings > $O/bench_config3.json 2> $O/bench_config3.err; show $O/bench_config3.json "config3"
 for v in 1048579 "$@"; do
   timeout 300 python bench.py --workload config3 --no-cpu-baseline --no-extra-timings --verify 0 --variant $v > $O/bench_config3_var$v.json 2> $O/bench_config3_var$v.err; show $O/bench_config3_var$v.json "config3 variant $v"
 done
-timeout 300 python bench.py --workload config3 --model roberta.bin --no-cpu-baseline --no-extra-timings > $O/bench_config3_roberta.json 2> $O/bench_config3_roberta.err; show $O/bench_config3_roberta.json "config3 corpus, roberta.bin"
+timeout 300 python bench.py --full --workload config3 --model roberta.bin --no-cpu-baseline --no-extra-timings > $O/bench_config3_roberta.json 2> $O/bench_config3_roberta.err; show $O/bench_config3_roberta.json "config3 corpus, roberta.bin"

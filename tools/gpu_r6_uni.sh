@@ -15,7 +15,7 @@ except Exception as e: print(sys.argv[2], "failed", e)
 PY
 }
 for w in config4 config5; do
-  timeout 240 python bench.py --workload $w --no-cpu-baseline --no-extra-timings > $O/bench_$w.json 2> $O/bench_$w.err; show $O/bench_$w.json "$w cut"
+  timeout 240 python bench.py --full --workload $w --no-cpu-baseline --no-extra-timings > $O/bench_$w.json 2> $O/bench_$w.err; show $O/bench_$w.json "$w cut"
 done
 for v in "$@"; do
   timeout 240 python bench.py --workload config4 --no-cpu-baseline --no-extra-timings --verify 0 --variant $v > $O/bench_config4_var$v.json 2> $O/bench_config4_var$v.err; show $O/bench_config4_var$v.json "config4 variant $v"

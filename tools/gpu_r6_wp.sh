@@ -12,7 +12,7 @@ try:
 except Exception as e: print(sys.argv[2], "failed", e)
 PY
 }
-timeout 400 python bench.py --no-cpu-baseline --no-extra-timings > $O/bench_default.json 2> $O/bench_default.err; show $O/bench_default.json "default"
+timeout 400 python bench.py --full --no-cpu-baseline --no-extra-timings > $O/bench_default.json 2> $O/bench_default.err; show $O/bench_default.json "default"
 timeout 400 python bench.py --no-cpu-baseline --no-extra-timings --steps 20 --warmup 5 --verify 0 > $O/bench_default2.json 2> $O/bench_default2.err; show $O/bench_default2.json "default (20 steps)"
 timeout 400 python bench.py --no-cpu-baseline --no-extra-timings --offsets --verify 2000000 > $O/bench_offsets.json 2> $O/bench_offsets.err; show $O/bench_offsets.json "offsets"
-timeout 300 python bench.py --no-cpu-baseline --no-extra-timings --workload config2 > $O/bench_config2.json 2> $O/bench_config2.err; show $O/bench_config2.json "config2"
+timeout 300 python bench.py --full --no-cpu-baseline --no-extra-timings --workload config2 > $O/bench_config2.json 2> $O/bench_config2.err; show $O/bench_config2.json "config2"
