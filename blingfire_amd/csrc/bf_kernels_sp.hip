@@ -2482,6 +2482,8 @@ __global__ __launch_bounds__(256) void k_compact(CompactParams p)
         const int64_t id_slot = (p.slot_mul > 0 ? stream_slot : ids_slot(b, d)) + (p.first ? p.first[d] : 0);
         const int32_t *src = p.ids_tmp + id_slot;
         const int64_t o = p.id_off[d];
+        // (by the whole count: a document whose ids run past ids_cap after its first 64 reports it too)
+        if (lane == 0 && o + c > p.ids_cap) atomicOr(p.status, 1);
         for (int i = lane; i < c; i += 64) {
             if (o + i < p.ids_cap) {
                 p.ids_out[o + i] = src[i];
@@ -2495,7 +2497,7 @@ __global__ __launch_bounds__(256) void k_compact(CompactParams p)
                     if (eo >= 0) { const uint32_t ch = p.b.text[b + eo]; sz = (ch & 0x80) == 0 ? 1 : (ch & 0xE0) == 0xC0 ? 2 : (ch & 0xF0) == 0xE0 ? 3 : (ch & 0xF8) == 0xF0 ? 4 : 0; }
                     p.starts_out[o + i] = so; p.ends_out[o + i] = eo + (sz > 0 ? sz - 1 : 0);
                 }
-            } else if (i == lane) atomicOr(p.status, 1);
+            }
         }
     }
 }

@@ -77,7 +77,7 @@ class _T2I:
         buf = ctypes.create_string_buffer(b"A" + b, len(b) + 1)
         c = f(ctypes.c_void_p(h), ctypes.addressof(buf) + 1, len(b), i, s, e, max_ids, unk)
         c = max(c, 0)
-        return c, list(i)[:c], list(s)[:c], list(e)[:c]
+        return c, i[:c], s[:c], e[:c]
 
     def batch(self, h, text, off, max_ids, unk):
         """per-document loop -> (ids int32[total], id_offsets int64[ndocs+1]) -- the golden form of TextToIdsBatch"""

@@ -106,3 +106,80 @@ def test_device_batch_reports_a_full_pool_per_document():
     finally:
         bf.free_model(h)
         ck.free(hck)
+
+
+def _compare_offsets(h, ck, hck, docs, max_ids, unk):
+    name = "TextToIdsWithOffsets" if bfutil.have_ref() else "bfo_text_to_ids_with_offsets"
+    ids, st, en, off = bf.text_to_ids_with_offsets_batch(h, docs, max_ids, unk)
+    for d, b in enumerate(docs):
+        c, gi, gs, ge = ck.with_offsets(hck, b, max_ids, unk, name)
+        a, z = int(off[d]), int(off[d + 1])
+        if (z - a, ids[a:z].tolist(), st[a:z].tolist(), en[a:z].tolist()) != (c, gi, gs, ge):
+            raise AssertionError("doc %d %r (%d bytes, max %d unk %d): gpu %d tokens %s != ref %d tokens %s" % (
+                d, b[:60], len(b), max_ids, unk, z - a, list(zip(ids[a:z], st[a:z], en[a:z]))[:10], c, list(zip(gi, gs, ge))[:10]))
+
+
+@pytest.mark.parametrize("model", [m for m in ("gpt2.bin", "roberta.bin") if bfutil.have_model(m)])
+@pytest.mark.parametrize("n", [10000, 50000])
+def test_long_runs_with_offsets_grow_the_pool(model, n, checker):
+    """the batches of test_long_runs_of_one_character_inside_a_batch through TextToIdsWithOffsetsBatch (k_bpe_fused, the offsets path) on a
+    handle whose pool starts at 1 MiB, too small for the runs: the call grows the pool, runs the batch again, and every document's ids, first
+    bytes and last bytes equal the reference's"""
+    h = bf.load_model(bfutil.model_path(model))
+    hck = checker.load(bfutil.model_path(model))
+    try:
+        bf.lib().BfSetBpePoolBytes(ctypes.c_void_p(h), 1 << 20)
+        docs = bfutil.fuzz_docs(60, seed=11)
+        mixed = docs[:30] + [b"-" * n, b"=" * n, b"see " + b"." * n + b" end", b"ab" * (n // 2)] + docs[30:]
+        _compare_offsets(h, checker, hck, mixed, 1 << 20, 0)
+        assert bf.lib().BfLastStatus(ctypes.c_void_p(h)) & (2 | 16 | 32 | 64) == 0
+        assert bf.lib().BfSetBpePoolBytes(ctypes.c_void_p(h), 1 << 20) > 1 << 20         # the call grew the pool
+        _compare_offsets(h, checker, hck, mixed, 7, 0)
+        assert bf.lib().BfLastStatus(ctypes.c_void_p(h)) & (2 | 16 | 32 | 64) == 0
+    finally:
+        bf.free_model(h)
+        checker.free(hck)
+
+
+def test_device_offsets_report_a_full_pool_per_document():
+    """test_device_batch_reports_a_full_pool_per_document through TextToIdsWithOffsetsBatchDevice: the document whose arcs do not fit gets 0
+    ids and BfLastStatus bit 64, every other document its ids, first and last bytes; after BfSetBpePoolBytes the same batch is complete"""
+    import torch
+    model = "gpt2.bin"
+    ck = bfutil.reference() if bfutil.have_ref() else bfutil.oracle()
+    name = "TextToIdsWithOffsets" if bfutil.have_ref() else "bfo_text_to_ids_with_offsets"
+    h = bf.load_model(bfutil.model_path(model))
+    hck = ck.load(bfutil.model_path(model))
+    try:
+        docs = [b"hello world", b"=" * 200000, b"the quick brown fox", "#" * 50 + " café \U0001F600"]
+        docs = [d.encode("utf-8") if isinstance(d, str) else d for d in docs]
+        want = [ck.with_offsets(hck, b, 1 << 20, 0, name) for b in docs]
+        text, off = bf.pack_docs(docs)
+        assert bf.lib().BfSetBpePoolBytes(ctypes.c_void_p(h), 1 << 20) == 64 << 20
+        dev = torch.device("cuda", 0)
+        d_text = torch.from_numpy(text).to(dev); d_off = torch.from_numpy(off).to(dev)
+        cap = 2 * (len(text) + len(docs))
+        for full in (False, True):
+            outs = [torch.full((cap,), -7, dtype=torch.int32, device=dev) for _ in range(3)]
+            ido = torch.empty(len(off), dtype=torch.int64, device=dev)
+            r = bf.lib().TextToIdsWithOffsetsBatchDevice(ctypes.c_void_p(h), d_text.data_ptr(), d_off.data_ptr(), len(docs), len(text), outs[0].data_ptr(),
+                                                         outs[1].data_ptr(), outs[2].data_ptr(), cap, ido.data_ptr(), 1 << 20, 0,
+                                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            assert r == 0
+            torch.cuda.synchronize(dev)
+            status = bf.lib().BfLastStatus(ctypes.c_void_p(h))
+            id_off = ido.cpu().numpy()
+            g_ids, g_st, g_en = [t.cpu().numpy() for t in outs]
+            if full:
+                assert status & (2 | 16 | 32 | 64) == 0
+            else:
+                assert status & 64 and id_off[2] - id_off[1] == 0
+            for d, (c, wi, ws, we) in enumerate(want):
+                if d == 1 and not full:
+                    continue
+                a, z = int(id_off[d]), int(id_off[d + 1])
+                assert (z - a, g_ids[a:z].tolist(), g_st[a:z].tolist(), g_en[a:z].tolist()) == (c, wi, ws, we), (d, full)
+            bf.lib().BfSetBpePoolBytes(ctypes.c_void_p(h), 256 << 20)
+    finally:
+        bf.free_model(h)
+        ck.free(hck)
