@@ -2256,8 +2256,9 @@ __global__ __launch_bounds__(256) void k_normsp(NormSpParams p)
         }
         if (nwritten > 1 && last_usp) { total -= last_len; if (last_norm) --nspaces; }  // tokdll:667-669
         const bool any_bad = __any(bad) || nchars <= 0;                                  // tokdll:646-648
+        const bool no_usp = p.usp_len == 0 && nspaces > 0;                              // a uSpace that cannot be encoded is needed: the single call fails (FAUtf8Utils.cpp:549-552)
         if (!WRITE && lane == 0) {
-            p.lens[d] = (any_bad || total > 0x7ffffff0ll) ? 0 : (int32_t)total;
+            p.lens[d] = (any_bad || no_usp || total > 0x7ffffff0ll) ? 0 : (int32_t)total;
             p.aux[d] = (any_bad ? 1 : 0) | ((nspaces > 0x3fffffff ? 0x3fffffff : (nspaces < 0 ? 0 : nspaces)) << 1);
         }
     }

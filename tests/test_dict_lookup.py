@@ -4,7 +4,7 @@ blingfireclient.library/inc/FADictInterpreter_t.h:334-390).
 CPU: the oracle restatement (bfo_dict_get_info*) is pinned against the reference's own interpreter (oracle/_ref/libdictref.so =
 oracle/ref_dict_glue.cpp + the reference sources, built by oracle/Makefile) and against a known answer of the reference's docs
 (ldbsrc/gpt2/README.TXT:40-47: `pedia` -> id 50236); the device program (bf_seg.h dict_info_id) runs on the host against the oracle.
-GPU: DictGetInfoBatch through the C-ABI against the oracle."""
+GPU: DictGetInfoBatch through the C-ABI against the reference's interpreter (the oracle where oracle/_ref is absent)."""
 import ctypes
 import gzip
 import os
@@ -130,13 +130,16 @@ def test_gpu_batch_lookup_matches_oracle(ora_lib, model):
     import blingfire_amd as bf
     if not bfutil.have_model(model):
         pytest.skip("%s not present" % model)
+    import secondary_cases as sc
     keys = keys_for(model, n_random=20000, seed=3)
     h = bf.load_model(bfutil.model_path(model))
     ho = ora_lib.bfo_load_model(bfutil.model_path(model).encode())
+    dck = sc.DictChecker(model)          # the reference's own interpreter where oracle/_ref/libdictref.so is built, else the oracle
     try:
         ret, ids, vals, v_off = bf.dict_get_info_batch(h, keys)
         for k, key in enumerate(keys):
-            gr, gi, gout = oracle_lookup(ora_lib, ho, key)
+            # (a negative symbol: the reference itself reads out of bounds, see keys_for -- those two keys stay with the oracle)
+            gr, gi, gout = oracle_lookup(ora_lib, ho, key) if min(key, default=0) < 0 else dck.lookup(key)
             assert (int(ret[k]), int(ids[k])) == (gr, gi), (model, key[:12])
             n = max(gr, 0)
             assert v_off[k + 1] - v_off[k] == n and list(vals[v_off[k]:v_off[k + 1]]) == gout[:n]
@@ -144,6 +147,7 @@ def test_gpu_batch_lookup_matches_oracle(ora_lib, model):
     finally:
         bf.free_model(h)
         ora_lib.bfo_free_model(ctypes.c_void_p(ho))
+        dck.close()
 
 
 @pytest.mark.gpu

@@ -1,5 +1,6 @@
 """IdsToText (reference tokdll:1689-1745): the oracle's restatement is pinned to the compiled
-reference on the reference's own .i2w files; the GPU tests call the product's IdsToText / IdsToTextBatch."""
+reference on the reference's own .i2w files; the GPU tests call the product's IdsToText / IdsToTextBatch and compare with the compiled
+reference where oracle/_ref is built, else with the oracle."""
 import ctypes
 import random
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 
 import bfutil
+import secondary_cases as sc
 
 I2W_MODELS = ["gpt2.i2w", "bert_base_cased_tok.i2w", "xlnet.i2w", "laser100k.i2w", "roberta.i2w"]
 
@@ -18,6 +20,17 @@ def _oracle_fn():
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     ora.lib.bfo_i2w_count.argtypes = [ctypes.c_void_p]
     return ora, f
+
+
+def _checker_fn():
+    """the GPU tests' checker: the compiled reference's IdsToText where oracle/_ref is built, else the oracle restatement -> (library wrapper, function, bool-typed skip)"""
+    if not bfutil.have_ref():
+        return _oracle_fn() + (False,)
+    ref = bfutil.reference()
+    g = ref.lib.IdsToText
+    g.restype = ctypes.c_int
+    g.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_bool]
+    return ref, g, True
 
 
 def _cases(cnt, n_cases, seed):
@@ -79,15 +92,15 @@ def test_oracle_vs_live_reference(model):
 @pytest.mark.parametrize("model", I2W_MODELS)
 def test_gpu_ids_to_text(model):
     import blingfire_amd as bf
-    ora, f = _oracle_fn()
+    cnt = sc.i2w_count(model)
+    ora, f, as_bool = _checker_fn()
     ho = ora.load(bfutil.model_path(model))
-    cnt = ora.lib.bfo_i2w_count(ho)
     h = bf.load_model(bfutil.model_path(model))
     L = bf.lib()
     try:
         cases = list(_cases(cnt, 300, 9))
         for ids, mx, skip in cases:
-            assert _run(L.IdsToText, ctypes.c_void_p(h), ids, mx, skip, True) == _run(f, ctypes.c_void_p(ho), ids, mx, skip), (model, ids[:8], mx, skip)
+            assert _run(L.IdsToText, ctypes.c_void_p(h), ids, mx, skip, True) == _run(f, ctypes.c_void_p(ho), ids, mx, skip, as_bool), (model, ids[:8], mx, skip)
         # the batch form = the single calls, concatenated without terminators; a sequence with an unknown id yields nothing
         for skip in (0, 1):
             flat = np.array([i for ids, _, _ in cases for i in ids], dtype=np.int32)
@@ -95,7 +108,7 @@ def test_gpu_ids_to_text(model):
             np.cumsum([len(ids) for ids, _, _ in cases], out=off[1:])
             text, t_off = bf.ids_to_text_batch(h, flat, off, bool(skip))
             for d, (ids, _, _) in enumerate(cases):
-                r, out = _run(f, ctypes.c_void_p(ho), ids, 8192, skip)
+                r, out = _run(f, ctypes.c_void_p(ho), ids, 8192, skip, as_bool)
                 want = out[:-1] if r > 0 else b""
                 assert text[t_off[d]:t_off[d + 1]].tobytes() == want, (model, d, ids[:8], skip)
         assert bf.text_to_ids(h, "hello", 8).sum() == 0        # an [i2w]-only model has no tokenizer: TextToIds returns 0 ids

@@ -65,7 +65,7 @@ def test_oracle_vs_live_reference():
 @pytest.mark.gpu
 def test_gpu_normalize_spaces_and_hashes():
     import blingfire_amd as bf
-    f, g = _oracle_fns()
+    f, g = _set(bfutil.reference().lib) if bfutil.have_ref() else _oracle_fns()      # the compiled reference where oracle/_ref is built
     pf, pg = _set(bf.lib())
     docs = DOCS + bfutil.fuzz_docs(400, seed=37)
     for b in docs:

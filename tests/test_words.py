@@ -225,13 +225,28 @@ def test_gpu_text_to_sentences(model):
         ora.free(ho)
 
 
+def _gpu_checker(model, mode):
+    """the checker of the GPU batch tests: ask(b, mx) -> the _call tuple of the compiled reference's TextToWords / TextToSentences
+    ...WithOffsetsWithModel where oracle/_ref is built (model None = its built-in model), else of the oracle; close() frees the model"""
+    if bfutil.have_ref():
+        ref = bfutil.reference()
+        g = getattr(ref.lib, "TextToWordsWithOffsetsWithModel" if mode == 1 else "TextToSentencesWithOffsetsWithModel")
+        g.restype = ctypes.c_int
+        g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        hr = ref.load(bfutil.model_path(model)) if model else None
+        return (lambda b, mx: _call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,))), (lambda: ref.free(hr) if hr else None)
+    ora, f = _oracle_fn() if mode == 1 else _oracle_sent_fn()
+    ho = ora.load(bfutil.model_path(model or ("wbd.bin" if mode == 1 else "sbd.bin")))
+    return (lambda b, mx: _call(f, (ctypes.c_void_p(ho),), b, mx)), (lambda: ora.free(ho))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("model", ["wbd.bin", "bert_base_cased_tok.bin", None])
 def test_gpu_text_to_words_batch(model):
-    """additive batch form: per document exactly the string TextToWordsWithModel produces (checked against the oracle)"""
+    """additive batch form: per document exactly the string TextToWordsWithModel produces (checked against the compiled reference, the oracle
+    where oracle/_ref is absent)"""
     import blingfire_amd as bf
-    ora, f = _oracle_fn()
-    ho = ora.load(bfutil.model_path(model or "wbd.bin"))
+    ask, close = _gpu_checker(model, 1)
     h = bf.load_model(bfutil.model_path(model)) if model else None
     try:
         docs = _docs(1500, 97) + [b"", b"Hello world . This is a test ."] * 3
@@ -240,22 +255,22 @@ def test_gpu_text_to_words_batch(model):
         docs += [raw[off[d]:off[d + 1]] for d in range(3000)]
         out, t_off = bf.text_to_words_batch(docs, h)
         for d, b in enumerate(docs):
-            r, o, _, _ = _call(f, (ctypes.c_void_p(ho),), b, 4 * len(b) + 8)
+            r, o, _, _ = ask(b, 4 * len(b) + 8)
             want = o[:r - 1] if r > 0 else b""
             assert out[t_off[d]:t_off[d + 1]].tobytes() == want, (model, d, b[:60])
     finally:
         if h:
             bf.free_model(h)
-        ora.free(ho)
+        close()
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("model", ["sbd.bin", None])
 def test_gpu_text_to_sentences_batch(model):
-    """additive batch form: per document exactly the string TextToSentencesWithModel produces (checked against the oracle)"""
+    """additive batch form: per document exactly the string TextToSentencesWithModel produces (checked against the compiled reference, the
+    oracle where oracle/_ref is absent)"""
     import blingfire_amd as bf
-    ora, f = _oracle_sent_fn()
-    ho = ora.load(bfutil.model_path(model or "sbd.bin"))
+    ask, close = _gpu_checker(model, 2)
     h = bf.load_model(bfutil.model_path(model)) if model else None
     try:
         docs = _docs(1500, 101) + SENT_DOCS * 3 + [b""]
@@ -264,13 +279,13 @@ def test_gpu_text_to_sentences_batch(model):
         docs += [raw[off[d]:off[d + 1]].replace(b" the ", b". The ") for d in range(2000)]
         out, t_off = bf.text_to_sentences_batch(docs, h)
         for d, b in enumerate(docs):
-            r, o, _, _ = _call(f, (ctypes.c_void_p(ho),), b, 4 * len(b) + 8)
+            r, o, _, _ = ask(b, 4 * len(b) + 8)
             want = o[:r - 1] if r > 0 else b""
             assert out[t_off[d]:t_off[d + 1]].tobytes() == want, (model, d, b[:60])
     finally:
         if h:
             bf.free_model(h)
-        ora.free(ho)
+        close()
 
 
 # ---- long documents of the words modes (bf_lex.h lex_one_start / lex_chain_visit, bf_kernels.hip k_lex_long*): every start position of
@@ -328,9 +343,7 @@ def test_gpu_long_documents(model, mode):
     with the long-document path at its default threshold, at 16 characters, and switched off"""
     import random
     import blingfire_amd as bf
-    ora, f = _oracle_fn() if mode == 1 else _oracle_sent_fn()
-    default = "wbd.bin" if mode == 1 else "sbd.bin"
-    ho = ora.load(bfutil.model_path(model or default))
+    ask, close = _gpu_checker(model, mode)          # the compiled reference where oracle/_ref is built, else the oracle
     h = bf.load_model(bfutil.model_path(model)) if model else None
     fn = bf.text_to_words_batch if mode == 1 else bf.text_to_sentences_batch
     try:
@@ -343,7 +356,7 @@ def test_gpu_long_documents(model, mode):
         docs += [big, b"", lines[0], big[:200000]]
         want = []
         for b in docs:
-            r, o, _, _ = _call(f, (ctypes.c_void_p(ho),), b, 4 * len(b) + 8)
+            r, o, _, _ = ask(b, 4 * len(b) + 8)
             want.append(o[:r - 1] if r > 0 else b"")
         # (0x10000000: a workspace of 40 chunks -- most of the long documents do not fit and stay with the lane kernel)
         # the single-document calls (reference signatures, byte offsets of every token) on long documents: the same kernels behind run_host
@@ -353,7 +366,7 @@ def test_gpu_long_documents(model, mode):
         g1.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         for b in [docs[0], docs[24], big[:50000], docs[-12]]:
             mx = 4 * len(b) + 8
-            assert _call(g1, (), b, mx, (ctypes.c_void_p(h) if h else None,)) == _call(f, (ctypes.c_void_p(ho),), b, mx), (model, mode, len(b), b[:60])
+            assert _call(g1, (), b, mx, (ctypes.c_void_p(h) if h else None,)) == ask(b, mx), (model, mode, len(b), b[:60])
         # (0x08000000: the two-level chain of very long documents from 256 cells on instead of 512 K)
         variants = [0] if h is None else [0, 1 << 12, 0x40000000, 0x10000000 | (1 << 12), 0x10000000 | (3 << 12), 0x08000000, 0x08000000 | (1 << 12)]
         for v in variants:
@@ -380,4 +393,4 @@ def test_gpu_long_documents(model, mode):
     finally:
         if h:
             bf.free_model(h)
-        ora.free(ho)
+        close()
