@@ -117,6 +117,10 @@ def lib():
         L.TextToHashes.argtypes = [c_char_p, c_int, c_void_p, c_int, c_int, c_int]
         L.WordHyphenationWithModel.restype = c_int
         L.WordHyphenationWithModel.argtypes = [c_char_p, c_int, c_void_p, c_int, c_void_p, c_int]
+        L.WordHyphenationBatch.restype = c_int64
+        L.WordHyphenationBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int]
+        L.WordHyphenationBatchDevice.restype = c_int
+        L.WordHyphenationBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]
         _lib = L
     return _lib
 
@@ -177,12 +181,30 @@ def text_to_hashes(s, word_n_grams, bucketSize):
 
 
 def word_hyphenation_with_model(h, s, uHy=0x2D):
-    """reference __init__.py:125-142.  The hyphenation engine is not part of this library (not on the TextToIds path): the C entry
-    point exists and returns the reference's error value, so this returns '' for every non-empty word."""
+    """reference __init__.py:125-142: the word with uHy behind every hyphenation point of the model's [w2h] patterns (h: a handle of
+    syllab.bin or of another model with that section); '' on error or for a handle without one."""
     s_bytes = s.encode("utf-8")
     o = ctypes.create_string_buffer(len(s_bytes) * 4 + 1)
     n = lib().WordHyphenationWithModel(s_bytes, len(s_bytes), o, len(o), c_void_p(h) if h else None, uHy)
     return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+
+
+def word_hyphenation_batch(h, words, uHy=0x2D):
+    """additive: word_hyphenation_with_model over many words (str or bytes) in one call -> list of str; '' where the single call fails."""
+    text, off = pack_docs([w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words])
+    nw = len(off) - 1
+    t_off = np.zeros(nw + 1, dtype=np.int64)
+    args = (c_void_p(h), c_void_p(text.ctypes.data), c_void_p(off.ctypes.data), nw)
+    fn = lib().WordHyphenationBatch
+    n = fn(*args, None, 0, c_void_p(t_off.ctypes.data), uHy)
+    out = np.empty(0, dtype=np.uint8)
+    if n == -3:                                           # BF_E_CAPACITY: the offsets tell the size
+        out = np.empty(int(t_off[-1]), dtype=np.uint8)
+        n = fn(*args, c_void_p(out.ctypes.data), len(out), c_void_p(t_off.ctypes.data), uHy)
+    if n < 0:
+        raise RuntimeError("WordHyphenationBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    raw = out.tobytes()
+    return [raw[t_off[i]:t_off[i + 1]].decode("utf-8") for i in range(nw)]
 
 
 def text_to_words(s):

@@ -5,6 +5,7 @@
   oracle/libcpubaseline.so              TEST INFRA: multi-threaded driver that times a TextToIds .so on host cores
   tools/libcorpusgen.so                 TEST INFRA: deterministic synthetic corpus generator
   tools/single_calls                    TEST INFRA: native-thread harness for single-document calls through the C-ABI
+  tools/libw2hcpu.so                    MEASUREMENT: times a library's WordHyphenationWithModel on host threads (tools/bench_w2h.py)
   tools/microbench/{stream,gather,valu_issue}  MEASUREMENT: counter calibration, gather ceiling, VALU / SALU issue rate
   tests/hosttest/libbf_hosttest.so      TEST INFRA: table-equivalence + host emulation of the lane programs
   oracle/_ref/libblingfiretokdll_ref.so TEST INFRA: the unmodified reference, only when /root/reference exists
@@ -40,8 +41,8 @@ def hipcc():
 
 
 def build_product(force=False):
-    """the product: four translation units compiled side by side (the two kernel files are most of the time), then linked"""
-    names = ("bf_kernels.hip", "bf_kernels_sp.hip", "bf_capi.cpp", "bf_model.cpp")
+    """the product: five translation units compiled side by side (the two large kernel files are most of the time), then linked"""
+    names = ("bf_kernels.hip", "bf_kernels_sp.hip", "bf_kernels_w2h.hip", "bf_capi.cpp", "bf_model.cpp")
     srcs = [os.path.join(CSRC, f) for f in names]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
         os.path.join(ROOT, "include", "blingfiretokdll_amd.h"), os.path.join(CSRC, "exports.map"), os.path.join(ROOT, "models", "wbd.bin"), os.path.join(ROOT, "models", "sbd.bin")]
@@ -91,6 +92,9 @@ def build_test_infra(force=False):
     sc = os.path.join(ROOT, "tools", "single_calls")
     if force or _newer(sc, [os.path.join(ROOT, "tools", "single_calls.c")]):
         _run(["gcc", "-O2", "-Wall", "-o", "single_calls", "single_calls.c", "-ldl", "-lpthread"], cwd=os.path.join(ROOT, "tools"))
+    wd = os.path.join(ROOT, "tools", "libw2hcpu.so")
+    if force or _newer(wd, [os.path.join(ROOT, "tools", "w2h_cpu_baseline.c")]):
+        _run(["gcc", "-O2", "-Wall", "-std=gnu99", "-fPIC", "-shared", "w2h_cpu_baseline.c", "-o", "libw2hcpu.so", "-ldl", "-lpthread"], cwd=os.path.join(ROOT, "tools"))
     # microbenchmarks the evidence scripts run on the GPU box (counter calibration, gather ceiling, issue rate): binaries, not tracked
     mb = os.path.join(ROOT, "tools", "microbench")
     for name in ("stream", "gather", "valu_issue", "gather_sweep"):
@@ -98,7 +102,8 @@ def build_test_infra(force=False):
         if os.path.exists(src) and (force or _newer(out, [src])):
             _run([hipcc(), "--offload-arch=gfx950", "-O2", "-w", "-o", out, src])
     ht = os.path.join(ROOT, "tests", "hosttest", "libbf_hosttest.so")
-    ht_src = [os.path.join(ROOT, "tests", "hosttest", "bf_hosttest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_wavetest.cpp"), os.path.join(CSRC, "bf_model.cpp")]
+    ht_src = [os.path.join(ROOT, "tests", "hosttest", "bf_hosttest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_wavetest.cpp"),
+              os.path.join(ROOT, "tests", "hosttest", "bf_w2htest.cpp"), os.path.join(CSRC, "bf_model.cpp")]
     ht_dep = ht_src + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(odir, "bf_oracle.c"),
                                                                                               os.path.join(ROOT, "tests", "hosttest", "wave_emu.h"), os.path.join(ROOT, "tests", "hosttest", "hosttest.h")]
     if force or _newer(ht, ht_dep):

@@ -157,6 +157,8 @@ struct Handle {
     std::mutex defer_mu;
     // device tables
     DevBuf t_wbd, t_info, t_acts, t_cp_l1, t_cp_pages, t_multi, t_i2w_off, t_i2w_data;
+    DevBuf t_w2h, t_w2h_pats, t_w2h_l1, t_w2h_pages;             // [w2h]: pattern automaton, pattern pool, code point -> class (bf_w2h.h)
+    DevBuf w_hcls, w_hnch, w_hsrc;                               // WordHyphenationBatch: position stream, characters and source bytes per word
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -202,7 +204,7 @@ struct Handle {
         for (Handle *c : shards) if (c && c != this) { DeviceGuard dg(c->device); (void)hipDeviceSynchronize(); delete c; }
         shards.clear();
         pipe.release(); m_small.release();
-        for (DevBuf *b : {&t_segscore, &t_segid, &t_bpetab, &t_bpe_prio, &t_bpe_place, &t_dk_l1, &t_dk_pages, &t_dn_l1, &t_dn_pages, &t_dn_pool, &t_k2i, &t_rows, &w_keys, &w_keyoff, &w_dids, &w_dret, &w_vals, &t_i2w_off, &t_i2w_data, &t_kind, &t_wbd, &t_info, &t_acts, &t_cp_l1, &t_cp_pages, &t_multi, &t_wcp_l1, &t_wcp_pages, &t_dict, &t_seginfo, &w_s1, &w_s2, &w_s3, &w_s4, &w_big, &w_perm, &w_hist, &w_narcs, &w_bwflags, &w_cls, &w_nchars, &w_tmp, &w_counts, &w_flags, &w_out, &w_outoff,
+        for (DevBuf *b : {&t_w2h, &t_w2h_pats, &t_w2h_l1, &t_w2h_pages, &w_hcls, &w_hnch, &w_hsrc, &t_segscore, &t_segid, &t_bpetab, &t_bpe_prio, &t_bpe_place, &t_dk_l1, &t_dk_pages, &t_dn_l1, &t_dn_pages, &t_dn_pool, &t_k2i, &t_rows, &w_keys, &w_keyoff, &w_dids, &w_dret, &w_vals, &t_i2w_off, &t_i2w_data, &t_kind, &t_wbd, &t_info, &t_acts, &t_cp_l1, &t_cp_pages, &t_multi, &t_wcp_l1, &t_wcp_pages, &t_dict, &t_seginfo, &w_s1, &w_s2, &w_s3, &w_s4, &w_big, &w_perm, &w_hist, &w_narcs, &w_bwflags, &w_cls, &w_nchars, &w_tmp, &w_counts, &w_flags, &w_out, &w_outoff,
                           &w_bsums, &w_misc, &w_text, &w_docoff, &w_ids, &w_idoff, &w_starts, &w_ends, &w_srcoff, &w_span, &w_long, &w_preplong, &w_w2tlong, &w_ent, &w_home, &w_entoff, &w_entcnt, &w_dstat, &w_ranges, &w_list, &w_wrec, &t_flat, &w_espan, &w_hspan, &w_chard}) b->release();
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
@@ -295,7 +297,7 @@ Handle *make_handle(const uint8_t *img, size_t size)
              upload(h->t_cp_l1, m.wbd_cpmap.l1) && upload(h->t_cp_pages, m.wbd_cpmap.pages) && upload(h->t_multi, m.wbd_multi_pool, 16) &&
              upload(h->t_wcp_l1, m.words_cpmap.l1) && upload(h->t_wcp_pages, m.words_cpmap.pages) && upload(h->t_kind, m.wave_kind, 16);
         if (m.flat_ok) ok = ok && upload(h->t_flat, m.flat_tab, 16);
-    } else if (m.kind != KIND_I2W) {
+    } else if (m.kind != KIND_I2W && m.kind != KIND_W2H) {
         ok = ok && upload(h->t_dict, m.dict.t64, 16) && upload(h->t_seginfo, m.seg_info, 16) &&
              upload(h->t_cp_l1, m.sp_cpmap.l1) && upload(h->t_cp_pages, m.sp_cpmap.pages) && upload(h->t_multi, m.sp_multi_pool, 16);
         if (m.kind == KIND_BPE_MERGES) ok = ok && upload(h->t_bpe_prio, m.bpe_prio, 16) && upload(h->t_bpe_place, m.bpe_place_id, 16);
@@ -308,6 +310,7 @@ Handle *make_handle(const uint8_t *img, size_t size)
         fprintf(stderr, "[blingfire_amd] %s\n", g_last_error.c_str()); delete h; return nullptr;
     }
     if (m.has_i2w) ok = ok && upload(h->t_i2w_off, m.i2w_off, 4) && upload(h->t_i2w_data, m.i2w_data, 16);
+    if (m.w2h_ready) ok = ok && upload(h->t_w2h, m.w2h.t64, 16) && upload(h->t_w2h_pats, m.w2h_pats, 16) && upload(h->t_w2h_l1, m.w2h_cpmap.l1) && upload(h->t_w2h_pages, m.w2h_cpmap.pages);
     ok = ok && hip_ok(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "hipStreamCreate");
     for (auto &e : h->ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate");
     ok = ok && h->w_misc.reserve(256) && hip_ok(hipMemset(h->w_misc.p, 0, 256), "hipMemset");
@@ -431,7 +434,7 @@ int run_device(Handle *h, const char *d_text, const int64_t *d_doc_off, int64_t 
                int32_t *d_starts = nullptr, int32_t *d_ends = nullptr, int words = 0)
 {
     const bool want_off = d_starts && d_ends;                                  // fNeedOffsets (tokdll:1137,1381)
-    if (h->m.kind == KIND_I2W) return BF_E_UNSUPPORTED;                        // an [i2w]-only model has no tokenizer
+    if (h->m.kind == KIND_I2W || h->m.kind == KIND_W2H) return BF_E_UNSUPPORTED;   // an [i2w]-only or [w2h]-only model has no tokenizer
     if (words && (h->m.kind != KIND_WP || !want_off)) return BF_E_ARG;
     if (ndocs < 0 || total_bytes < 0 || !d_doc_off || !d_id_off || (ids_cap > 0 && !d_ids_out) || (total_bytes > 0 && !d_text)) return BF_E_ARG;
     if (max_ids < 0) max_ids = 0;
@@ -918,7 +921,7 @@ int64_t run_host_locked(Handle *h, const char *text, const int64_t *doc_off, int
     hipStream_t s = h->stream;
     if (!defer_ids && ndocs >= 1 && ndocs <= SMALL_MAX_DOCS && total <= SMALL_MAX_BYTES && !want_off && use_wave(h, want_off, words) && small_ready(h))
         return run_host_mapped(h, text, doc_off, ndocs, ids_out, ids_cap, id_off_out, max_ids, unk);
-    if (!defer_ids && !want_off && !words && h->m.kind != KIND_I2W && h->host_chunk_bytes > 0 && total >= h->host_chunk_bytes && ndocs >= 2) {
+    if (!defer_ids && !want_off && !words && h->m.kind != KIND_I2W && h->m.kind != KIND_W2H && h->host_chunk_bytes > 0 && total >= h->host_chunk_bytes && ndocs >= 2) {
         const int64_t r = run_host_chunked(h, text, doc_off, ndocs, ids_out, ids_cap, id_off_out, max_ids, unk);
         if (r != HOST_PIPE_UNAVAILABLE) return r;
     }
@@ -1126,6 +1129,48 @@ int run_hashes_device(Handle *h, const char *d_text, const int64_t *d_doc_off, i
     return hip_ok(hipGetLastError(), "TextToHashes kernels") ? 0 : BF_E_DEVICE;
 }
 
+// WordHyphenationBatch on device buffers (bf_kernels_w2h.hip): prep, walk, scan when `size` is set; copy when d_out is given
+bool reserve_w2h_workspaces(Handle *h, int64_t nwords, int64_t total_bytes)
+{
+    return h->w_hcls.reserve((size_t)(total_bytes + 2 * nwords + 64) * 2) && h->w_hnch.reserve((size_t)(nwords + 1) * 4) && h->w_hsrc.reserve((size_t)(nwords + 1) * 4) &&
+           h->w_counts.reserve((size_t)(nwords + 1) * 4) && h->w_bsums.reserve((size_t)(scan_nblocks(nwords) + 1) * 8);
+}
+
+int run_w2h_device(Handle *h, const char *d_text, const int64_t *d_word_off, int64_t nwords, int64_t total_bytes, char *d_out, int64_t out_cap,
+                   int64_t *d_out_off, int u_hy, hipStream_t s, bool size)
+{
+    const Model &m = h->m;
+    if (!m.w2h_ready) { g_last_error = "WordHyphenation: the model has no usable [w2h] section"; return BF_E_UNSUPPORTED; }
+    W2hParams p;
+    p.hy_bytes = 0; p.hy_len = w2h_encode(u_hy, &p.hy_bytes);
+    if (p.hy_len == 0) return BF_E_ARG;                                        // FAIntToUtf8 refuses it: the single call answers -1 (tokdll:867-870)
+    if (nwords < 0 || total_bytes < 0 || !d_word_off || !d_out_off || (total_bytes > 0 && !d_text)) return BF_E_ARG;
+    if (!reserve_w2h_workspaces(h, nwords, total_bytes)) return BF_E_DEVICE;
+    p.t.T = h->t_w2h.as<uint64_t>(); p.t.pats = h->t_w2h_pats.as<uint8_t>(); p.t.cp_l1 = h->t_w2h_l1.as<uint16_t>(); p.t.cp_pages = h->t_w2h_pages.as<uint32_t>();
+    p.t.initial = m.w2h.initial_base; p.t.cls_l = m.w2h_cls_l; p.t.cls_r = m.w2h_cls_r; p.t.min_pat_len = m.w2h_min_pat_len; p.t.no_hyph_len = m.w2h_no_hyph_len;
+    p.text = (const uint8_t *)d_text; p.word_off = d_word_off; p.nwords = nwords; p.total_bytes = total_bytes; p.status = (int *)(h->w_misc.as<char>() + 16);
+    p.cls = h->w_hcls.as<uint16_t>(); p.nch = h->w_hnch.as<int32_t>(); p.srcb = h->w_hsrc.as<int32_t>(); p.lens = h->w_counts.as<int32_t>();
+    p.out_off = d_out_off; p.out = (uint8_t *)d_out; p.out_cap = out_cap;
+    if (size) {
+        if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
+        h->small_status = -1;
+        (void)hipEventRecord(h->ev[EV_BEGIN], s);
+        if (nwords > 0) launch_w2h_prep(p, s);
+        (void)hipEventRecord(h->ev[EV_PREP], s);
+        (void)hipEventRecord(h->ev[EV_DOM0], s);
+        if (nwords > 0) launch_w2h_walk(p, s);
+        (void)hipEventRecord(h->ev[EV_DOM1], s);
+        (void)hipEventRecord(h->ev[EV_TOK], s);
+        ScanParams sp{h->w_counts.as<int32_t>(), nwords, d_out_off, h->w_bsums.as<int64_t>(), scan_nblocks(nwords)};
+        launch_scan(sp, s);
+        (void)hipEventRecord(h->ev[EV_SCAN], s);
+    }
+    if (d_out && nwords > 0) launch_w2h_copy(p, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "WordHyphenation kernels") ? 0 : BF_E_DEVICE;
+}
+
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
 bool ensure_dict_tables(Handle *h)
 {
@@ -1240,6 +1285,7 @@ int text_to_ids_one(void *hp, const char *s, int n, int32_t *ids, int max_ids, i
     Handle *h = as_handle(hp);
     if (!h) return 0;                                         // tokdll:1629-1631
     if (n <= 0 || n > 1000000000 || !s) return 0;             // tokdll:1121-1123
+    if (h->m.kind == KIND_W2H) return 0;                      // a [w2h]-only model: the reference's TextToIds answers 0
     if (want_kind == 0 && h->m.kind != KIND_WP) return 0;
     if (want_kind == 1 && h->m.kind == KIND_WP) return 0;
     if (max_ids <= 0 || !ids) return 0;
@@ -1821,14 +1867,70 @@ int64_t DictGetInfoBatch(void *p, const int32_t *keys, const int64_t *key_offset
     return nvals;
 }
 
-/* reference tokdll:818-915.  Not on the TextToIds path, no hyphenation engine here: resolves, fails loudly. */
-int WordHyphenationWithModel(const char *, int n, char *, const int, void *, const int)
+/* reference tokdll:818-911 over FAHyphInterpreter_core_t.h:136-267, as a batch of one on the GPU (bf_w2h.h, bf_kernels_w2h.hip) */
+int WordHyphenationWithModel(const char *s, int n, char *out, const int max_out, void *hModel, const int u_hy)
 {
     if (n == 0) return 0;                                                      // tokdll:832-834
-    static bool warned = false;
-    if (!warned) { warned = true; fprintf(stderr, "[blingfire_amd] WordHyphenationWithModel: the hyphenation engine is not part of this library (TextToIds path only); returning -1\n"); }
-    g_last_error = "WordHyphenationWithModel is not implemented by this library";
-    return -1;
+    if (n < 0 || n > 1000000000 || !s) return -1;                              // tokdll:835-840
+    Handle *h = as_handle(hModel);                                             // (NULL: the reference has no built-in model and dereferences it)
+    if (!h || !h->m.w2h_ready) { g_last_error = "WordHyphenationWithModel: the handle has no usable [w2h] section"; return -1; }      // the engine is not ready: -1 (FAHyphInterpreter_core_t.h:148-150)
+    uint32_t hyb = 0;
+    if (w2h_encode(u_hy, &hyb) == 0) return -1;                                // tokdll:867-870
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return -1;
+    hipStream_t st = h->stream;
+    // 300 characters of at most 4 bytes behind a BOM: what lies behind them is never looked at (tokdll:843-849)
+    const int64_t up = n < 3 + 4 * W2H_MAX_CHARS ? n : 3 + 4 * W2H_MAX_CHARS, off[2] = {0, up};
+    constexpr int64_t full_cap = 8 * W2H_MAX_CHARS + 16;
+    uint8_t full[full_cap];
+    int64_t out_off[2] = {0, 0};
+    if (upload_docs(h, s, off, 1, st) < 0 || !h->w_out.reserve((size_t)full_cap)) return -1;
+    if (run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, up, h->w_out.as<char>(), full_cap, h->w_outoff.as<int64_t>(), u_hy, st, true) != 0) return -1;
+    int32_t nch = 0;
+    if (!hip_ok(hipMemcpyAsync(out_off, h->w_outoff.p, 16, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(hipMemcpyAsync(&nch, h->w_hnch.p, 4, hipMemcpyDeviceToHost, st), "D2H") ||
+        !hip_ok(hipMemcpyAsync(full, h->w_out.p, (size_t)full_cap, hipMemcpyDeviceToHost, st), "D2H text") || !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return -1;
+    if (nch <= 0 || out_off[1] <= 0 || out_off[1] > full_cap) return -1;       // invalid UTF-8 / nothing decoded (tokdll:846-849)
+    return w2h_finish(full, (int)out_off[1], out, max_out);
+}
+
+int64_t WordHyphenationBatch(void *p, const char *text, const int64_t *word_off, int64_t nwords, char *text_out, int64_t text_cap, int64_t *text_off_out, int u_hy)
+{
+    Handle *h = as_handle(p);
+    if (!h) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    if (!h->m.w2h_ready) { g_last_error = "WordHyphenation: the model has no usable [w2h] section"; return BF_E_UNSUPPORTED; }
+    uint32_t hyb = 0;
+    if (w2h_encode(u_hy, &hyb) == 0) return BF_E_ARG;
+    const int64_t total = upload_docs(h, text, word_off, nwords, s);
+    if (total < 0) return total;
+    int rc = run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), nwords, total, nullptr, 0, h->w_outoff.as<int64_t>(), u_hy, s, true);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
+    std::vector<int64_t> tmp_off; int64_t *dst_off = text_off_out;
+    if (!dst_off) { tmp_off.resize((size_t)nwords + 1); dst_off = tmp_off.data(); }
+    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(nwords + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    const int64_t nout = dst_off[nwords];
+    if (nout > text_cap) return BF_E_CAPACITY;
+    if (nout > 0) {
+        if (!text_out || !h->w_out.reserve((size_t)nout + 16)) return text_out ? BF_E_DEVICE : BF_E_ARG;
+        rc = run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), nwords, total, h->w_out.as<char>(), nout, h->w_outoff.as<int64_t>(), u_hy, s, false);
+        if (rc != 0) return rc;
+        if (!hip_ok(hipMemcpyAsync(text_out, h->w_out.p, (size_t)nout, hipMemcpyDeviceToHost, s), "D2H text") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    }
+    return nout;
+}
+
+int WordHyphenationBatchDevice(void *p, const char *d_text, const int64_t *d_word_off, int64_t nwords, int64_t total_bytes, char *d_text_out, int64_t text_cap,
+                               int64_t *d_text_off_out, int u_hy, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_w2h_device(h, d_text, d_word_off, nwords, total_bytes, d_text_out, text_cap, d_text_off_out, u_hy, (hipStream_t)stream, true);
 }
 
 int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
@@ -1838,6 +1940,8 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     if (h->m.kind == KIND_I2W) return BF_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words
+    if (h->m.kind == KIND_W2H) return 0;
     // both forms of the WordPiece path: the wave program's workspaces and (words = 1 skips use_wave()'s early return) the class stream and flags of
     // the lane-per-document kernels, which TextToWords / TextToSentences, lexers outside the unit form and BfSetVariant(2) run -- no hipMalloc
     // (= device synchronisation) inside a later call of either kind
@@ -1878,7 +1982,7 @@ int BfSetDevices(void *p, const int *device_ids, int n)
 {
     Handle *h = as_handle(p);
     if (!h || !device_ids || n < 1 || n > 64) return BF_E_ARG;
-    if (h->m.kind == KIND_I2W) return BF_E_UNSUPPORTED;
+    if (h->m.kind == KIND_I2W || h->m.kind == KIND_W2H) return BF_E_UNSUPPORTED;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) return BF_E_DEVICE;
     for (int i = 0; i < n; ++i) if (device_ids[i] < 0 || device_ids[i] >= ndev) return BF_E_ARG;
@@ -2066,7 +2170,7 @@ const char *BfTokeniseKernel(void *p)
     switch (h->m.kind) {
     case KIND_WP: return h->last_flat ? "k_wp_flat" : use_wave(h, false, 0) ? "k_wp_wave" : (h->m.two_level ? "k_lex_wp_plain" : "k_lex_wp_flat");
     case KIND_UNIGRAM: return h->last_uni_cut ? "k_uni_cut" : "k_seg_unigram_lane";
-    case KIND_I2W: return "";
+    case KIND_I2W: case KIND_W2H: return "";
     default: return use_bpe_wave(h, false) ? "k_bpe_wave" : "k_bpe_fused";
     }
 }
@@ -2085,7 +2189,7 @@ const char *BfStepKernels(void *p)
     case KIND_UNIGRAM:
         if (h->last_uni_cut) return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_uni_cut | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_uni_ids";
         return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_seg_unigram_lane, k_uni_back | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
-    case KIND_I2W: return "";
+    case KIND_I2W: case KIND_W2H: return "";
     default:
         if (use_bpe_wave(h, false)) return bpe_wave_home((h->variant >> 8) & 0xf) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather"
                                                                               : "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";

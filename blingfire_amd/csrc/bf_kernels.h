@@ -8,6 +8,7 @@
 #include "bf_wave.h"
 #include "bf_bpe_wave.h"
 #include "bf_flat.h"
+#include "bf_w2h.h"
 
 namespace bfa {
 
@@ -235,6 +236,20 @@ struct HashParams {
 void launch_hash_count(const HashParams &p, hipStream_t s);
 void launch_hash_fill(const HashParams &p, hipStream_t s);
 void launch_i2t_copy(const I2tParams &p, hipStream_t s);
+
+// WordHyphenation (reference tokdll:818-911, FAHyphInterpreter_core_t.h:136-267) as a batch: word w = text[word_off[w] .. word_off[w+1]); bf_w2h.h, bf_kernels_w2h.hip
+struct W2hParams {
+    W2hTables t;
+    const uint8_t *text; const int64_t *word_off; int64_t nwords, total_bytes; int *status;
+    uint16_t *cls;               // position stream, [total_bytes + 2 * nwords]: classes, then the "a hyphen follows" flags (bf_w2h.h w2h_slot)
+    int32_t *nch, *srcb;         // [nwords] characters (0: the word yields nothing) and the bytes they take in the source
+    int32_t *lens;               // [nwords] output bytes (no terminator)
+    int hy_len; uint32_t hy_bytes;      // the hyphen's UTF-8 length (1 .. 4) and bytes, little end first
+    const int64_t *out_off; uint8_t *out; int64_t out_cap;      // copy pass
+};
+void launch_w2h_prep(const W2hParams &p, hipStream_t s);
+void launch_w2h_walk(const W2hParams &p, hipStream_t s);
+void launch_w2h_copy(const W2hParams &p, hipStream_t s);
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <string>
 #include <unordered_map>
 
 namespace bfa {
@@ -1240,6 +1241,91 @@ bool build_model(Model &m, const uint8_t *img, size_t size)
         fused(0x2581, m.sp_prefix);
         build_bpe_word_table(m);
     }
+    // ---- [w2h] (reference FAHyphConfKeeper.cpp:49-151; the engine that reads it: FAHyphInterpreter_core_t.h:110-267, restated in bf_w2h.h)
+    if (conf.get(FUNC_W2H, vals)) {
+        m.has_w2h = true;
+        int fsm_dump = -1, pats_dump = -1, charmap_dump = -1;
+        for (size_t i = 0; i < vals.size(); ++i) {
+            const int p = vals[i];
+            if (p == PARAM_IGNORE_CASE) { m.w2h_ignore_case = true; continue; }
+            if (p == PARAM_NORMALIZE) continue;                                    // stored by the reference, unused by the core engine
+            if (p != PARAM_MIN_LEN && p != PARAM_MIN_LEN2 && p != PARAM_LEFT_ANCHOR && p != PARAM_RIGHT_ANCHOR && p != PARAM_HYPH_TYPE &&
+                p != PARAM_FSM && p != PARAM_CHARMAP && p != PARAM_MULTI_MAP) return fail(m, "[w2h] unknown parameter " + std::to_string(p));
+            if (i + 1 >= vals.size()) return fail(m, "truncated [w2h] parameters");
+            const int v = vals[++i];
+            switch (p) {
+            case PARAM_MIN_LEN: if (v <= 0 || v > 300) return fail(m, "[w2h] min-len must be in 1 .. 300"); m.w2h_min_pat_len = v; break;
+            case PARAM_MIN_LEN2: if (v < 0 || v > 5) return fail(m, "[w2h] min-len2 must be in 0 .. 5"); m.w2h_no_hyph_len = v; break;
+            case PARAM_LEFT_ANCHOR: if (v <= 0) return fail(m, "[w2h] left-anchor must be positive"); m.w2h_left_anchor = v; break;
+            case PARAM_RIGHT_ANCHOR: if (v <= 0) return fail(m, "[w2h] right-anchor must be positive"); m.w2h_right_anchor = v; break;
+            case PARAM_HYPH_TYPE: if (v < 0 || v >= HYPH_TYPE_COUNT) return fail(m, "[w2h] unknown hyph-type"); break;
+            case PARAM_FSM: if (v < 0 || v >= count) return fail(m, "[w2h] fsm dump is missing"); fsm_dump = v; break;
+            case PARAM_CHARMAP: if (v < 0 || v >= count) return fail(m, "[w2h] charmap dump is missing"); charmap_dump = v; break;
+            default: if (v < 0 || v >= count) return fail(m, "[w2h] multi-map dump is missing"); pats_dump = v; break;
+            }
+        }
+        m.w2h_ready = fsm_dump >= 0 && pats_dump >= 0;
+        if (m.w2h_ready) {
+            if (!decode_dfa(dump(fsm_dump), false, m.w2h_raw, m.error)) return false;
+            if (!pack_dfa(m.w2h_raw, true, {m.w2h_left_anchor, m.w2h_right_anchor}, m.w2h, m.error)) return false;
+            if (m.w2h.nclasses >= 0xFFFF) return fail(m, "[w2h] too many symbol classes for the class stream");
+            m.w2h_cls_none = (uint32_t)m.w2h.nclasses;                   // pack_dfa leaves nclasses + 1 entries behind the last base: the probe stays in range, no entry carries this class
+            auto cls_sym = [&](int iw) -> uint32_t {
+                int c = m.w2h_raw.class_of(iw);
+                if (c < 0) return m.w2h_cls_none;
+                if (!m.w2h_raw.remap) {
+                    auto &S = m.w2h.sym_of_class;
+                    auto it = std::lower_bound(S.begin(), S.end(), c);
+                    if (it == S.end() || *it != c) return m.w2h_cls_none;
+                    c = (int)(it - S.begin());
+                }
+                return (uint32_t)c;
+            };
+            m.w2h_cls_l = cls_sym(m.w2h_left_anchor); m.w2h_cls_r = cls_sym(m.w2h_right_anchor);
+            // the patterns.  A slot of the output ends as the one value it saw, or as HYPH_CONFLICT if it saw two different ones, whatever the order
+            // the patterns are laid over it -- as long as no pattern holds HYPH_UNKNOWN or HYPH_CONFLICT as a value (with one, the result of
+            // FAHyphInterpreter_core_t.h:226-242 depends on its From-then-length order).  The kernels overlay in parallel (one bit per value in a byte
+            // per slot), so a model with a value outside 0 .. HYPH_DONT_CARE is refused here.
+            TrivMap pats;
+            if (!pats.set(dump(pats_dump))) return fail(m, "[w2h] bad pattern map");
+            m.w2h_pats.assign(2, 0);                                      // record 0: no pattern (a final state without one: FAMultiMap_pack::Get answers -1)
+            std::vector<uint32_t> pat_off((size_t)pats.max_key + 1, 0u);
+            std::vector<int> pv;
+            for (uint32_t id = 0; id <= pats.max_key; ++id) {
+                if (!pats.get((int)id, pv) || pv.empty()) continue;
+                if (pv.size() > 302) return fail(m, "[w2h] pattern longer than a word with its anchors");
+                pat_off[id] = (uint32_t)m.w2h_pats.size();
+                m.w2h_pats.push_back((uint8_t)(pv.size() & 255)); m.w2h_pats.push_back((uint8_t)(pv.size() >> 8));
+                for (int x : pv) {
+                    if (x < HYPH_NO_HYPH || x > HYPH_DONT_CARE)
+                        return fail(m, "[w2h] pattern " + std::to_string(id) + " holds the value " + std::to_string(x) + ": outside 0 .. 7 the reference's overlay depends on its order, which the parallel overlay does not keep");
+                    m.w2h_pats.push_back((uint8_t)x);
+                }
+            }
+            if (m.w2h_pats.size() >= (1ull << (64 - T64_OW_SHIFT))) return fail(m, "[w2h] pattern pool too large for the table entry format");
+            std::vector<uint32_t> pat_of_base(m.w2h.table_len(), 0u);
+            for (size_t st = 0; st < m.w2h_raw.state_off.size(); ++st) {
+                const int ow = m.w2h_raw.ow[st];
+                if (m.w2h_raw.is_final[st] && ow >= 0 && (uint32_t)ow <= pats.max_key) pat_of_base[m.w2h.state_base[st]] = pat_off[(size_t)ow];
+            }
+            for (uint64_t &e : m.w2h.t64) {
+                if ((e & T64_CLS_MASK) == T64_CLS_MASK || !(e & T64_FINAL_BIT)) continue;
+                e = (e & ((1ull << T64_OW_SHIFT) - 1)) | ((uint64_t)pat_of_base[(size_t)((e >> T64_NEXT_SHIFT) & T64_NEXT_MASK)] << T64_OW_SHIFT);
+            }
+            // fused code-point map: what FAHyphInterpreter_core_t.h:165-183 does to a character on its way into GetDest, behind tokdll:851
+            FixedMap cm;
+            if (charmap_dump >= 0 && !cm.set(dump(charmap_dump))) return fail(m, "[w2h] bad charmap");
+            m.w2h_cpmap.init(m.w2h_cls_none);
+            for (int cp = 0; cp <= 0x10FFFF; ++cp) {
+                int c = cp == 0 ? 0x20 : cp;
+                if (m.w2h_ignore_case) c = bf_tolower(c);
+                int co = 0;
+                if (cm.set_ && cm.get(c, &co, 1) == 1) c = co;
+                const uint32_t k = cls_sym(c);
+                if (k != m.w2h_cls_none) m.w2h_cpmap.set(cp, k);
+            }
+        }
+    }
     // ---- [i2w] (reference tokdll:998-1045): string array dump + the range of regular token ids
     if (conf.get(35 /* FUNC_I2W */, vals)) {
         for (size_t i = 0; i < vals.size(); ++i) {
@@ -1261,8 +1347,8 @@ bool build_model(Model &m, const uint8_t *img, size_t size)
     if (!m.has_seg) {
         m.kind = KIND_WP;
         if (!m.has_wbd || m.wbd.table_len() == 0) {
-            if (!m.has_i2w) return fail(m, "model has neither a [wbd] lexer, a [pos-dict] dictionary nor an [i2w] string array");
-            m.kind = KIND_I2W;
+            if (!m.has_i2w && !m.has_w2h) return fail(m, "model has neither a [wbd] lexer, a [pos-dict] dictionary, an [i2w] string array nor a [w2h] hyphenator");
+            m.kind = m.has_i2w ? KIND_I2W : KIND_W2H;
         }
     }
     return true;

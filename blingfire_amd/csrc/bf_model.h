@@ -20,7 +20,9 @@ enum : int {
     IW_ANY = 0, IW_L_ANCHOR = 1, IW_R_ANCHOR = 2, IW_EPSILON = 3,
     DFA_DEAD_STATE = -2,
     TRS_NONE = 0, TRS_RANGE = 1, TRS_IMPL = 2, TRS_PARA = 4, TRS_IWIA = 6,
-    FUNC_POS_DICT = 12, FUNC_WBD = 19, FUNC_GLOBAL = 20,
+    FUNC_W2H = 11, FUNC_POS_DICT = 12, FUNC_WBD = 19, FUNC_GLOBAL = 20,
+    PARAM_MIN_LEN = 17, PARAM_LEFT_ANCHOR = 27, PARAM_RIGHT_ANCHOR = 28, PARAM_MIN_LEN2 = 32, PARAM_HYPH_TYPE = 34, PARAM_NORMALIZE = 35,
+    HYPH_CONFLICT = -2, HYPH_UNKNOWN = -1, HYPH_NO_HYPH = 0, HYPH_DONT_CARE = 7, HYPH_TYPE_COUNT = 3,
     PARAM_DIRECTION = 11, PARAM_FSM = 2, PARAM_MAP_MODE = 16, PARAM_NO_TR = 18, PARAM_IGNORE_CASE = 22,
     PARAM_ARRAY = 24, PARAM_MULTI_MAP = 25, PARAM_FSM_TYPE = 26, PARAM_DEPTH = 38, PARAM_CHARMAP = 47,
     PARAM_MAX_LENGTH = 69, PARAM_VERIFY_LDB_BIN = 70, PARAM_TOKENIZATION_TYPE = 71, PARAM_ID_OFFSET = 72,
@@ -30,7 +32,8 @@ enum : int {
 };
 
 // kinds of TextToIds algorithm a model selects (reference tokdll:959-974, 1619-1646)
-enum ModelKind : int { KIND_WP = 0, KIND_UNIGRAM = 1, KIND_BPE = 2, KIND_BPE_OPT = 3, KIND_BPE_MERGES = 4, KIND_I2W = 5 /* [i2w] only: IdsToText */ };
+enum ModelKind : int { KIND_WP = 0, KIND_UNIGRAM = 1, KIND_BPE = 2, KIND_BPE_OPT = 3, KIND_BPE_MERGES = 4, KIND_I2W = 5 /* [i2w] only: IdsToText */,
+                       KIND_W2H = 6 /* [w2h] only: WordHyphenation */ };
 
 // Abstract automaton decoded from a packed dump (test hooks compare it with the oracle's readers).
 struct RawDfa {
@@ -101,6 +104,18 @@ struct Model {
     std::vector<uint32_t> i2w_off;     // [count + 1] byte offsets into i2w_data
     std::vector<uint8_t> i2w_data;
     int min_token_id = 0, max_token_id = 1000000000;   // regular (non special) ids (FALimits::MaxArrSize default)
+
+    // ---- [w2h] hyphenation patterns (reference FAHyphConfKeeper.cpp:49-151, FAHyphInterpreter_core_t.h:136-267; bf_w2h.h)
+    bool has_w2h = false;              // the section exists
+    bool w2h_ready = false;            // ... and carries the automaton and the pattern map: without them every call answers -1 (the engine's m_Ready)
+    bool w2h_ignore_case = false;
+    int w2h_min_pat_len = 3, w2h_no_hyph_len = 0, w2h_left_anchor = IW_L_ANCHOR, w2h_right_anchor = IW_R_ANCHOR;
+    RawDfa w2h_raw;
+    // T64 entries; the output-weight field of a transition INTO a final state is the offset of that state's pattern in w2h_pats
+    PackedDfa w2h;
+    std::vector<uint8_t> w2h_pats;     // records [length low byte, length high byte, one byte per value (0 .. HYPH_DONT_CARE)]; record 0 is the empty pattern
+    uint32_t w2h_cls_l = 0, w2h_cls_r = 0, w2h_cls_none = 0;      // classes of the anchors' symbols; the class no transition carries
+    TwoLevelMap w2h_cpmap;             // fused "code point -> (U+0000 -> U+0020) -> fold if ignore-case -> 1:1 charmap -> class"
 
     // ---- [wbd] lexer (reference FAWbdConfKeeper.cpp:56-232, FALexTools_t.h:129-202)
     bool has_wbd = false;

@@ -151,12 +151,27 @@ BF_API int IdsToTextBatchDevice(void *ModelPtr, const int32_t *d_ids, const int6
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
 
-/* reference tokdll:818-915 (blingfiretokdll.def: WordHyphenationWithModel).  The hyphenation engine is NOT on the TextToIds path
- * and is not part of this library: the symbol exists so that consumers that bind every export by name
- * resolve, and fails loudly -- 0 for an empty input like the reference, -1 (the reference's error value) otherwise, with one
- * diagnostic on stderr. */
+/* reference tokdll:818-911 (blingfiretokdll.def: WordHyphenationWithModel) over FAHyphInterpreter_core_t.h:136-267: the word with uHy
+ * written behind every character that a pattern of the model's [w2h] section (syllab.bin) marks as a hyphenation point.  hModel: a LoadModel
+ * handle of a model with a [w2h] section; any other handle, and NULL, answer -1 (the reference has no built-in model here).  Returns 0
+ * for a 0-byte input; -1 for a negative size, a NULL string, invalid UTF-8 within the first 300 characters or a uHy that UTF-8 cannot
+ * encode (negative, a surrogate, above U+10FFFF); otherwise the bytes the whole output needs, plus 1 for a terminating 0 that is written
+ * and counted only when it fits.  At most 300 characters are looked at (FALimits::MaxWordSize), a leading BOM is not part of the word,
+ * U+0000 is written as U+0020.  Whole symbols are copied while they fit MaxOutUtf8StrByteCount; pOutUtf8Str may be NULL to size only.
+ * Runs as a batch of one on the GPU (the kernels of WordHyphenationBatch). */
 BF_API int WordHyphenationWithModel(const char *pInUtf8Str, int InUtf8StrByteCount, char *pOutUtf8Str, const int MaxOutUtf8StrByteCount,
                              void *hModel, const int uHy);
+/* additive: WordHyphenationWithModel (tokdll:818-911, FAHyphInterpreter_core_t.h:136-267) for many words at once; word w =
+ * text[word_offsets[w] .. word_offsets[w+1]).  The output of word w -- the bytes the single call produces, without the terminating 0;
+ * nothing for a word the single call answers with 0 or -1 -- = text_out[text_offsets_out[w] .. text_offsets_out[w+1]).  Contracts of
+ * TextToWordsBatch / TextToWordsBatchDevice: the host form returns the byte total, or BF_E_CAPACITY with complete offsets and text_out
+ * untouched; the Device form writes only the offsets when d_text_out is NULL, never writes at or past text_cap, does not synchronise and,
+ * after BfReserve(h, max_words, max_bytes, 0), does not allocate.  BF_E_ARG for a uHy the single call refuses, BF_E_UNSUPPORTED for a
+ * handle without a usable [w2h] section, for the whole call.  Words whose offsets leave the text are empty (BfLastStatus bit 3). */
+BF_API int64_t WordHyphenationBatch(void *ModelPtr, const char *text, const int64_t *word_offsets, int64_t nwords, char *text_out, int64_t text_cap,
+                             int64_t *text_offsets_out, int uHy);
+BF_API int WordHyphenationBatchDevice(void *ModelPtr, const char *d_text, const int64_t *d_word_offsets, int64_t nwords, int64_t total_bytes,
+                               char *d_text_out, int64_t text_cap, int64_t *d_text_offsets_out, int uHy, void *stream);
 
 /* ---- additive batch entry points (a GPU wants batches; semantics = "for every document,
  *      exactly what TextToIds(h, doc, len, buf, max_ids_per_doc, unk) would have written",
@@ -237,7 +252,8 @@ BF_API int BfLastStatus(void *ModelPtr);
 /* Last load error message of the calling thread ("" if none). */
 BF_API const char *BfLastError(void);
 
-/* Model facts: 0 = WordPiece lexer, 1 = Unigram-LM, 2 = BPE, 3 = BPE-opt, 4 = BPE with merge ranks */
+/* Model facts: 0 = WordPiece lexer, 1 = Unigram-LM, 2 = BPE, 3 = BPE-opt, 4 = BPE with merge ranks, 5 = [i2w] only (IdsToText),
+ * 6 = [w2h] only (WordHyphenation; a model that has [w2h] beside other sections keeps its kind and hyphenates too) */
 BF_API long long BfBpeFallbackDocs(void *ModelPtr);   /* diagnostics: documents of the last BPE batch that took the full (sort + apply) path */
 BF_API int BfModelKind(void *ModelPtr);
 
