@@ -12,6 +12,7 @@ import pytest
 
 import bfutil
 import blingfire_amd as bf
+import flat_cases
 
 WP_MODELS = ["bert_base_tok.bin", "bert_base_cased_tok.bin", "bert_chinese.bin"]
 # (max_ids, unk, waves, ranges): ranges 0 = four per wave (as many as documents allow)
@@ -195,6 +196,75 @@ def test_batch_not_fit(ht):
         assert st[9] == 1 and st[8] == 3, st.tolist()
 
     check(ht, model, (text, off), [(64, 100, 2, 0)], want)
+
+
+# ---- the builders of tests/flat_cases.py at small size (tests/test_gpu_flat_other_text.py runs them at device size): text the flat program was
+# not tuned on.  st[8]: distinct documents handed to the wave program, st[9]: the batch was not fit.  The bounds are conditions on the inputs
+# (what share of such text leaves the flat program), not measurements
+@pytest.mark.parametrize("model", WP_MODELS)
+def test_other_text_real_lines(ht, model):
+    if not bfutil.have_model(model):
+        pytest.skip("model not present")
+    docs = flat_cases.real_lines(3000)
+    nd = len(docs[1]) - 1
+
+    def want(st):
+        assert st[9] == 0 and 0 < st[8] < nd / 2, st.tolist()          # (seen: 27, 25 and 414 of 3,000)
+
+    check(ht, model, docs, [(512, 100, 2, 0), (8, 7, 1, 1)], want)
+
+
+@pytest.mark.parametrize("model", WP_MODELS)
+def test_other_text_multilingual(ht, model):
+    if not bfutil.have_model(model):
+        pytest.skip("model not present")
+    docs = flat_cases.multilingual(300)
+    nd = len(docs[1]) - 1
+
+    def want(st):
+        assert st[9] == 0 and nd / 4 <= st[8] <= 3 * nd / 4, st.tolist()          # (seen: 144, 164 and 153 of 300)
+
+    check(ht, model, docs, [(512, 100, 2, 0), (8, 7, 3, 1)], want)
+
+
+@pytest.mark.parametrize("model", WP_MODELS)
+def test_other_text_mixture(ht, model):
+    if not bfutil.have_model(model):
+        pytest.skip("model not present")
+    docs = flat_cases.mixture(375)
+    nd = len(docs[1]) - 1
+    assert nd == 375 + 125 + 7 and nd % 64
+
+    def want(st):
+        assert st[9] == 0 and 0 < st[8] < nd, st.tolist()
+
+    check(ht, model, docs, [(512, 100, 2, 0), (8, 7, 1, 3)], want)
+
+
+def test_other_text_shapes(ht):
+    model = bfutil.bert_model_name()
+
+    def want(st):
+        assert st[9] == 0 and st[8] >= 1, st.tolist()
+
+    # the record-list overflow bodies alone among plain documents: they are what is handed back
+    check(ht, model, flat_cases.overflow_batch(100), [(4096, 100, 2, 0)], want)
+    for rotation in range(flat_cases.SHAPES_ROTATIONS):
+        docs = flat_cases.shapes(rotation, 200)
+        raw = docs[0].tobytes()
+        assert raw.endswith(flat_cases.TAILS[rotation]) and raw.startswith(flat_cases.run_docs()[0])
+        check(ht, model, docs, [(512, 100, 2, 0), (8, 7, 1, 1)] if rotation == 0 else [(512, 100, 3, 0)], want)
+
+
+def test_other_text_size_limits(ht):
+    model = bfutil.bert_model_name()
+    docs = flat_cases.size_limits(400)
+    assert int(np.diff(docs[1]).max()) == flat_cases.WF_DOC_MAX
+
+    def want(st):
+        assert st[9] == 0 and st[8] == 0, st.tolist()          # the document of 4 MiB stays in the flat program
+
+    check(ht, model, docs, [(1 << 20, 100, 2, 0)], want)
 
 
 def test_invalid_utf8_everywhere(ht):
