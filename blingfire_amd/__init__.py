@@ -86,6 +86,12 @@ def lib():
         L.IdsToTextBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int]
         L.IdsToTextBatchDevice.restype = c_int
         L.IdsToTextBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]
+        L.IdsToRowsBatch.restype = c_int64
+        L.IdsToRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+        L.IdsToRowsBatchDevice.restype = c_int
+        L.IdsToRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
         L.BfLastKernelMs.restype = c_int
         L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
         L.BfLastStatus.restype = c_int
@@ -446,6 +452,94 @@ def ids_to_text_batch_device(h, d_ids, d_id_off, out_text=None, out_off=None, sk
     if r != 0:
         raise RuntimeError("IdsToTextBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
     return out_text, out_off
+
+
+def _special(i):
+    return -1 if i is None else int(i)
+
+
+def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False):
+    """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> fixed-shape model inputs (IdsToRowsBatch).  A sequence longer than
+    the row is cut into windows that share `stride` ids (max_rows_per_seq: 1 = truncate, 0 = every window); cls_id / sep_id None = no
+    such special.  Returns (rows int32[R, L], mask uint8[R, L], row_seq int32[R], row_first int32[R], row_offsets int64[nseq+1]):
+    the rows of sequence q are [row_offsets[q], row_offsets[q+1]), row_first is the index within its sequence of a row's first id."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
+    nseq = len(id_off) - 1
+    r_off = np.zeros(nseq + 1, dtype=np.int64)
+    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride),
+           int(max_rows_per_seq), int(bool(pad_left)))
+    fn = lib().IdsToRowsBatch
+    n = fn(*pre, None, None, None, None, 0, r_off.ctypes.data)          # the size query
+    if n < 0:
+        raise RuntimeError("IdsToRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    rows = np.empty((n, L), dtype=np.int32)
+    mask = np.empty((n, L), dtype=np.uint8)
+    seq = np.empty(n, dtype=np.int32)
+    first = np.empty(n, dtype=np.int32)
+    if n > 0:
+        r = fn(*pre, rows.ctypes.data, mask.ctypes.data, seq.ctypes.data, first.ctypes.data, n, r_off.ctypes.data)
+        if r != n:
+            raise RuntimeError("IdsToRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return rows, mask, seq, first, r_off
+
+
+def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False,
+                             rows_cap=None, stream=None):
+    """Device-resident ids_to_rows_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are) ->
+    the same five results as tensors on that device, enqueued on torch's current stream (or `stream`).  rows_cap None: nseq rows when
+    max_rows_per_seq is 1 (nothing is read back); otherwise a size query whose total is read back (one synchronisation).  With a
+    rows_cap of the caller's the tensors have rows_cap rows, row_offsets[-1] of them valid; rows beyond it are dropped (BfLastStatus bit 0)."""
+    import torch
+    nseq = d_id_off.numel() - 1
+    dev = d_ids.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
+    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id),
+           int(stride), int(max_rows_per_seq), int(bool(pad_left)))
+    fn = lib().IdsToRowsBatchDevice
+    if rows_cap is None:
+        if max_rows_per_seq == 1:
+            rows_cap = nseq
+        else:
+            r = fn(*pre, None, None, None, None, 0, r_off.data_ptr(), c_void_p(s))
+            if r != 0:
+                raise RuntimeError("IdsToRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+            if stream is not None:
+                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
+            rows_cap = int(r_off[-1].item())
+    rows = torch.empty((rows_cap, L), dtype=torch.int32, device=dev)
+    mask = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
+    seq = torch.empty(rows_cap, dtype=torch.int32, device=dev)
+    first = torch.empty(rows_cap, dtype=torch.int32, device=dev)
+    r = fn(*pre, rows.data_ptr(), mask.data_ptr(), seq.data_ptr(), first.data_ptr(), rows_cap, r_off.data_ptr(), c_void_p(s))
+    if r != 0:
+        raise RuntimeError("IdsToRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return rows, mask, seq, first, r_off
+
+
+def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False):
+    """Text in HBM -> tensors a model takes, nothing on the host: text_to_ids_batch_device and ids_to_rows_batch_device on one stream.
+    Every document is tokenised up to the ids its rows can hold (all of them when max_rows_per_doc is 0).
+    Returns (rows int32[R, L], mask uint8[R, L], row_doc int32[R], row_offsets int64[ndocs+1])."""
+    body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
+    step = body - int(stride)
+    if body < 1 or stride < 0 or step < 1 or max_rows_per_doc < 0:
+        raise ValueError("encode_batch_device: L leaves no room for ids, or stride / max_rows_per_doc are out of range")
+    max_len = min(body + (max_rows_per_doc - 1) * step, 2 ** 31 - 1) if max_rows_per_doc > 0 else 2 ** 31 - 1
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, max_len, unk)
+    rows, mask, seq, _, r_off = ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, stride, max_rows_per_doc, pad_left)
+    return rows, mask, seq, r_off
+
+
+def encode_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False):
+    """encode_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed, uploaded with torch to the current
+    device, encoded there."""
+    import torch
+    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
+    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
+    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
+    return encode_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, stride, max_rows_per_doc, pad_left)
 
 
 def dict_get_info_batch(h, keys):

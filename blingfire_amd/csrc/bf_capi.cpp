@@ -159,6 +159,7 @@ struct Handle {
     DevBuf t_wbd, t_info, t_acts, t_cp_l1, t_cp_pages, t_multi, t_i2w_off, t_i2w_data;
     DevBuf t_w2h, t_w2h_pats, t_w2h_l1, t_w2h_pages;             // [w2h]: pattern automaton, pattern pool, code point -> class (bf_w2h.h)
     DevBuf w_hcls, w_hnch, w_hsrc;                               // WordHyphenationBatch: position stream, characters and source bytes per word
+    DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch: sequence and first id of every row, where the caller takes neither
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -204,7 +205,7 @@ struct Handle {
         for (Handle *c : shards) if (c && c != this) { DeviceGuard dg(c->device); (void)hipDeviceSynchronize(); delete c; }
         shards.clear();
         pipe.release(); m_small.release();
-        for (DevBuf *b : {&t_w2h, &t_w2h_pats, &t_w2h_l1, &t_w2h_pages, &w_hcls, &w_hnch, &w_hsrc, &t_segscore, &t_segid, &t_bpetab, &t_bpe_prio, &t_bpe_place, &t_dk_l1, &t_dk_pages, &t_dn_l1, &t_dn_pages, &t_dn_pool, &t_k2i, &t_rows, &w_keys, &w_keyoff, &w_dids, &w_dret, &w_vals, &t_i2w_off, &t_i2w_data, &t_kind, &t_wbd, &t_info, &t_acts, &t_cp_l1, &t_cp_pages, &t_multi, &t_wcp_l1, &t_wcp_pages, &t_dict, &t_seginfo, &w_s1, &w_s2, &w_s3, &w_s4, &w_big, &w_perm, &w_hist, &w_narcs, &w_bwflags, &w_cls, &w_nchars, &w_tmp, &w_counts, &w_flags, &w_out, &w_outoff,
+        for (DevBuf *b : {&w_rowseq, &w_rowfirst, &t_w2h, &t_w2h_pats, &t_w2h_l1, &t_w2h_pages, &w_hcls, &w_hnch, &w_hsrc, &t_segscore, &t_segid, &t_bpetab, &t_bpe_prio, &t_bpe_place, &t_dk_l1, &t_dk_pages, &t_dn_l1, &t_dn_pages, &t_dn_pool, &t_k2i, &t_rows, &w_keys, &w_keyoff, &w_dids, &w_dret, &w_vals, &t_i2w_off, &t_i2w_data, &t_kind, &t_wbd, &t_info, &t_acts, &t_cp_l1, &t_cp_pages, &t_multi, &t_wcp_l1, &t_wcp_pages, &t_dict, &t_seginfo, &w_s1, &w_s2, &w_s3, &w_s4, &w_big, &w_perm, &w_hist, &w_narcs, &w_bwflags, &w_cls, &w_nchars, &w_tmp, &w_counts, &w_flags, &w_out, &w_outoff,
                           &w_bsums, &w_misc, &w_text, &w_docoff, &w_ids, &w_idoff, &w_starts, &w_ends, &w_srcoff, &w_span, &w_long, &w_preplong, &w_w2tlong, &w_ent, &w_home, &w_entoff, &w_entcnt, &w_dstat, &w_ranges, &w_list, &w_wrec, &t_flat, &w_espan, &w_hspan, &w_chard}) b->release();
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
@@ -1171,6 +1172,79 @@ int run_w2h_device(Handle *h, const char *d_text, const int64_t *d_word_off, int
     return hip_ok(hipGetLastError(), "WordHyphenation kernels") ? 0 : BF_E_DEVICE;
 }
 
+// IdsToRowsBatch on device buffers (bf_rows.h, bf_kernels_rows.hip): count, scan, then -- when the caller takes any of the four outputs -- map and fill
+bool reserve_rows_workspaces(Handle *h, int64_t nseq)
+{
+    return h->w_counts.reserve((size_t)(nseq + 1) * 4) && h->w_bsums.reserve((size_t)(scan_nblocks(nseq) + 1) * 8) &&
+           h->w_rowseq.reserve((size_t)(nseq + 1) * 4) && h->w_rowfirst.reserve((size_t)(nseq + 1) * 4);
+}
+
+int run_rows_device(Handle *h, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, const RowsSpec &spec, int32_t *d_rows,
+                    uint8_t *d_mask, int32_t *d_row_seq, int32_t *d_row_first, int64_t rows_cap, int64_t *d_row_off, hipStream_t s)
+{
+    if (nseq < 0 || ids_len < 0 || rows_cap < 0 || !d_id_off || !d_row_off || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
+    h->small_status = -1;
+    RowsParams p;
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = (int *)(h->w_misc.as<char>() + 16);
+    p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap; p.rows = d_rows; p.mask = d_mask;
+    // a row's sequence and first id go to the caller's arrays or, for the fill, to as much workspace as the handle has (the rows of a batch
+    // that is truncated to one row per sequence always fit; growing it here would be a hipMalloc the reserved call must not make)
+    p.row_seq = d_row_seq ? d_row_seq : h->w_rowseq.as<int32_t>(); p.seq_rows = d_row_seq ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
+    p.row_first = d_row_first ? d_row_first : h->w_rowfirst.as<int32_t>(); p.first_rows = d_row_first ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
+    if (nseq > 0) launch_rows_count(p, s);
+    ScanParams sp{h->w_counts.as<int32_t>(), nseq, d_row_off, h->w_bsums.as<int64_t>(), scan_nblocks(nseq)};
+    launch_scan(sp, s);
+    if (nseq > 0 && (d_rows || d_mask || d_row_seq || d_row_first)) {
+        launch_rows_map(p, s);
+        if (rows_cap > 0 && (d_rows || d_mask)) launch_rows_fill(p, s);
+    }
+    return hip_ok(hipGetLastError(), "IdsToRows kernels") ? 0 : BF_E_DEVICE;
+}
+
+// host buffers: upload, run, download; returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written
+int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const RowsSpec &spec, int32_t *rows_out, uint8_t *mask_out,
+                      int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
+{
+    if (nseq < 0 || rows_cap < 0 || !id_off || !row_off_out) return BF_E_ARG;
+    // the ids the sequences can name: from the first offset to the largest (an offset below the first one makes its sequences empty, as on the device)
+    const int64_t base = id_off[0];
+    if (base < 0) return BF_E_ARG;
+    int64_t ids_len = 0;
+    for (int64_t i = 0; i <= nseq; ++i) ids_len = std::max(ids_len, id_off[i] - base);
+    if (ids_len > 0 && !ids) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (the id buffers this call uses may hold a sharded range's ids that wait for their copy out)
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    if (!h->w_ids.reserve((size_t)(ids_len + 1) * 4) || !h->w_docoff.reserve((size_t)(nseq + 1) * 8) || !h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
+    std::vector<int64_t> rel((size_t)nseq + 1);
+    for (int64_t i = 0; i <= nseq; ++i) rel[(size_t)i] = id_off[i] - base;
+    if (ids_len > 0 && !hip_ok(hipMemcpyAsync(h->w_ids.p, ids + base, (size_t)ids_len * 4, hipMemcpyHostToDevice, s), "H2D ids")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
+    if (!hip_ok(hipMemcpyAsync(h->w_docoff.p, rel.data(), (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
+    int rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, nullptr, nullptr, nullptr, nullptr, 0, h->w_idoff.as<int64_t>(), s);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
+    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
+        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    const int64_t total = row_off_out[nseq];
+    if (total == 0 || (!rows_out && !mask_out && !row_seq_out && !row_first_out)) return total;      // (a size query needs no capacity)
+    if (total > rows_cap) return BF_E_CAPACITY;
+    const size_t cells = (size_t)total * (size_t)spec.row_len;
+    if ((rows_out && !h->w_out.reserve(cells * 4 + 16)) || (mask_out && !h->w_text.reserve(cells + 16)) ||
+        (row_seq_out && !h->w_starts.reserve((size_t)total * 4)) || (row_first_out && !h->w_ends.reserve((size_t)total * 4))) return BF_E_DEVICE;
+    rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, rows_out ? h->w_out.as<int32_t>() : nullptr,
+                         mask_out ? h->w_text.as<uint8_t>() : nullptr, row_seq_out ? h->w_starts.as<int32_t>() : nullptr,
+                         row_first_out ? h->w_ends.as<int32_t>() : nullptr, total, h->w_idoff.as<int64_t>(), s);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
+    bool ok = true;
+    if (rows_out) ok = ok && hip_ok(hipMemcpyAsync(rows_out, h->w_out.p, cells * 4, hipMemcpyDeviceToHost, s), "D2H rows");
+    if (mask_out) ok = ok && hip_ok(hipMemcpyAsync(mask_out, h->w_text.p, cells, hipMemcpyDeviceToHost, s), "D2H mask");
+    if (row_seq_out) ok = ok && hip_ok(hipMemcpyAsync(row_seq_out, h->w_starts.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row sequences");
+    if (row_first_out) ok = ok && hip_ok(hipMemcpyAsync(row_first_out, h->w_ends.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row firsts");
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && ok ? total : BF_E_DEVICE;
+}
+
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
 bool ensure_dict_tables(Handle *h)
 {
@@ -1821,6 +1895,30 @@ int IdsToTextBatchDevice(void *p, const int32_t *d_ids, const int64_t *d_id_offs
     return run_i2t_device(h, d_ids, d_id_offsets, nseq, d_text_out, text_cap, d_text_offsets_out, skip_special, s);
 }
 
+/* ---- additive: fixed-shape model inputs from ragged ids (bf_rows.h): rows of row_len cells with the specials in place, padding and a mask */
+int IdsToRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
+                         int pad_id, int stride, int max_rows_per_seq, int flags, int32_t *d_rows_out, uint8_t *d_mask_out, int32_t *d_row_seq_out,
+                         int32_t *d_row_first_out, int64_t rows_cap, int64_t *d_row_offsets_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    RowsSpec spec;
+    if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_rows_device(h, d_ids, ids_len, d_id_offsets, nseq, spec, d_rows_out, d_mask_out, d_row_seq_out, d_row_first_out, rows_cap, d_row_offsets_out,
+                           (hipStream_t)stream);
+}
+
+int64_t IdsToRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int stride,
+                       int max_rows_per_seq, int flags, int32_t *rows_out, uint8_t *mask_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap,
+                       int64_t *row_offsets_out)
+{
+    Handle *h = as_handle(p);
+    RowsSpec spec;
+    if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec)) return BF_E_ARG;
+    return run_rows_host(h, ids, id_offsets, nseq, spec, rows_out, mask_out, row_seq_out, row_first_out, rows_cap, row_offsets_out);
+}
+
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */
 int DictGetInfoBatchDevice(void *p, const int32_t *d_keys, const int64_t *d_key_offsets, int64_t nkeys, int32_t *d_ret_out, int32_t *d_info_ids_out,
                            int32_t *d_values_out, int64_t values_cap, int64_t *d_value_offsets_out, void *stream)
@@ -1937,9 +2035,10 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
 {
     Handle *h = as_handle(p);
     if (!h || max_docs < 0 || max_bytes < 0) return BF_E_ARG;
-    if (h->m.kind == KIND_I2W) return BF_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    if (!reserve_rows_workspaces(h, max_docs)) return BF_E_DEVICE;                                   // IdsToRowsBatchDevice, any handle: documents = sequences
+    if (h->m.kind == KIND_I2W) return 0;                                                             // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words
     if (h->m.kind == KIND_W2H) return 0;
     // both forms of the WordPiece path: the wave program's workspaces and (words = 1 skips use_wave()'s early return) the class stream and flags of

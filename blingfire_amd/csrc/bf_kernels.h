@@ -9,6 +9,7 @@
 #include "bf_bpe_wave.h"
 #include "bf_flat.h"
 #include "bf_w2h.h"
+#include "bf_rows.h"
 
 namespace bfa {
 
@@ -250,6 +251,22 @@ struct W2hParams {
 void launch_w2h_prep(const W2hParams &p, hipStream_t s);
 void launch_w2h_walk(const W2hParams &p, hipStream_t s);
 void launch_w2h_copy(const W2hParams &p, hipStream_t s);
+
+// IdsToRowsBatch (additive; bf_rows.h, bf_kernels_rows.hip): ragged ids -> rows of row_len cells + mask.  Sequence q = ids[id_off[q] .. id_off[q+1])
+struct RowsParams {
+    RowsSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    int32_t *counts;             // [nseq] rows per sequence
+    const int64_t *row_off;      // [nseq + 1] exclusive scan of counts; row_off[nseq] = the row total, read on the device
+    int64_t rows_cap;            // no row r >= rows_cap of any output is written
+    int32_t *rows; uint8_t *mask;                                    // [rows_cap * row_len] each, either may be NULL
+    // sequence and first id of every row: the caller's arrays (seq_rows / first_rows = rows_cap) or, for one the caller left out, the
+    // handle's workspace and the rows it holds; the fill finds a row at or past them by its own search
+    int32_t *row_seq, *row_first; int64_t seq_rows, first_rows;
+};
+void launch_rows_count(const RowsParams &p, hipStream_t s);
+void launch_rows_map(const RowsParams &p, hipStream_t s);
+void launch_rows_fill(const RowsParams &p, hipStream_t s);
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -1,0 +1,107 @@
+// bf_rows.h -- fixed-shape model inputs from ragged ids: the window count of a sequence and the cell of a row.
+//
+// Additive (the reference has no counterpart; include/blingfiretokdll_amd.h IdsToRowsBatchDevice is the specification).  A sequence of n
+// ids is cut into windows of `body` ids whose starts lie `step` = body - stride apart; window w becomes the row
+//     [cls] ids[w * step .. min(n, w * step + body)) [sep] pad...          (flag bit 0: the padding comes first)
+// of row_len cells, with a mask that is 1 over the real cells.  A sequence that fits (n <= body; an empty one too) has one row.
+//
+// Everything a cell depends on is written once here as BF_HD code: bf_kernels_rows.hip runs it per lane, tests/hosttest compiles the same
+// header for the host (test-only: the product library never fills rows on the CPU).  Plain C++, no HIP types.
+#pragma once
+#include <stdint.h>
+
+#if !defined(BF_HD)
+#if defined(__HIPCC__)
+#define BF_HD __host__ __device__ __forceinline__
+#else
+#define BF_HD inline
+#endif
+#endif
+
+namespace bfa {
+
+constexpr int ROWS_MAX_LEN = 1 << 20;     // row_len above this is refused
+constexpr int ROWS_PAD_LEFT = 1;          // flags bit 0
+
+// what a cell holds: an index into its sequence (>= 0) or one of these
+constexpr int64_t ROWS_CELL_PAD = -1, ROWS_CELL_CLS = -2, ROWS_CELL_SEP = -3;
+
+struct RowsSpec {
+    int row_len, cls_id, sep_id, pad_id;
+    int body, step;                       // ids per window; distance of two window starts
+    int lead, trail;                      // 1 when cls_id / sep_id are written
+    int max_rows;                         // windows kept per sequence; 0 = all
+    int pad_left;
+};
+
+// fills `s`; false = the parameters are refused (BF_E_ARG)
+BF_HD bool rows_spec(int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags, RowsSpec *s)
+{
+    if (row_len < 1 || row_len > ROWS_MAX_LEN || max_rows_per_seq < 0 || (flags & ~ROWS_PAD_LEFT) != 0) return false;
+    s->row_len = row_len; s->cls_id = cls_id; s->sep_id = sep_id; s->pad_id = pad_id;
+    s->lead = cls_id >= 0 ? 1 : 0; s->trail = sep_id >= 0 ? 1 : 0;
+    s->body = row_len - s->lead - s->trail;
+    if (s->body < 1 || stride < 0 || stride >= s->body) return false;
+    s->step = s->body - stride;
+    s->max_rows = max_rows_per_seq; s->pad_left = (flags & ROWS_PAD_LEFT) ? 1 : 0;
+    return true;
+}
+
+// ids of sequence q as the kernels see it: 0 when its range is not inside [0, ids_len] or its offsets decrease (*bad is set then)
+BF_HD int64_t rows_seq_len(int64_t b, int64_t e, int64_t ids_len, bool *bad)
+{
+    *bad = b < 0 || e < b || e > ids_len;
+    return *bad ? 0 : e - b;
+}
+
+// rows of a sequence of n ids; a count beyond INT32_MAX saturates (*saturated is set then)
+BF_HD int32_t rows_count(const RowsSpec &s, int64_t n, bool *saturated)
+{
+    *saturated = false;
+    if (n <= s.body) return 1;
+    int64_t rows = 1 + (n - s.body + s.step - 1) / s.step;
+    if (s.max_rows > 0 && rows > s.max_rows) rows = s.max_rows;
+    if (rows > 0x7fffffff) { rows = 0x7fffffff; *saturated = true; }
+    return (int32_t)rows;
+}
+
+// cell j (0 .. row_len - 1) of the row whose first id is number row_first of a sequence of n ids: the index of the id it holds, or ROWS_CELL_*
+BF_HD int64_t rows_cell(const RowsSpec &s, int64_t row_first, int64_t n, int j)
+{
+    int64_t k = n - row_first;            // ids in this window
+    if (k > s.body) k = s.body;
+    if (k < 0) k = 0;
+    const int real = (int)k + s.lead + s.trail;
+    const int x = s.pad_left ? j - (s.row_len - real) : j;
+    if (x < 0 || x >= real) return ROWS_CELL_PAD;
+    if (s.lead && x == 0) return ROWS_CELL_CLS;
+    const int i = x - s.lead;
+    return i < k ? row_first + i : ROWS_CELL_SEP;
+}
+
+// the id and the mask byte of a cell; `seq` = the ids of its sequence
+BF_HD int32_t rows_cell_value(const RowsSpec &s, int64_t cell, const int32_t *seq, uint8_t *mask)
+{
+    *mask = cell == ROWS_CELL_PAD ? 0 : 1;
+    return cell >= 0 ? seq[cell] : cell == ROWS_CELL_CLS ? s.cls_id : cell == ROWS_CELL_SEP ? s.sep_id : s.pad_id;
+}
+
+// row_first as the int32 the outputs hold: an index beyond INT32_MAX (one sequence of more than 2^31 ids) saturates (*saturated is set then)
+BF_HD int32_t rows_first_i32(int64_t first, bool *saturated)
+{
+    *saturated = first > 0x7fffffff;
+    return *saturated ? 0x7fffffff : (int32_t)first;
+}
+
+// the sequence of row r: the last q of [0, nseq) with row_off[q] <= r (every sequence has at least one row: the offsets rise strictly)
+BF_HD int64_t rows_find_seq(const int64_t *row_off, int64_t nseq, int64_t r)
+{
+    int64_t lo = 0, hi = nseq - 1;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (row_off[mid] <= r) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+} // namespace bfa

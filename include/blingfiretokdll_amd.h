@@ -148,6 +148,34 @@ BF_API int64_t IdsToTextBatch(void *ModelPtr, const int32_t *ids, const int64_t 
 BF_API int IdsToTextBatchDevice(void *ModelPtr, const int32_t *d_ids, const int64_t *d_id_offsets, int64_t nseq, char *d_text_out,
                          int64_t text_cap, int64_t *d_text_offsets_out, int skip_special, void *stream);
 
+/* additive (no counterpart in the reference; this comment is the specification): fixed-shape model inputs from ragged ids, e.g. the
+ * d_ids_out / d_id_offsets_out of TextToIdsBatchDevice as they are.  Sequence q = ids[id_offsets[q] .. id_offsets[q+1]), n ids.  With
+ * body = row_len - (cls_id >= 0) - (sep_id >= 0) and step = body - stride, it yields 1 row when n <= body (an empty sequence too), else
+ * 1 + ceil((n - body) / step) rows, at most max_rows_per_seq of them when that is > 0 (1 = truncate, 0 = all windows).  Row w of a sequence
+ * holds its ids [w * step, min(n, w * step + body)):  [cls_id] ids... [sep_id] pad_id...  (flags bit 0: the padding comes first); the mask
+ * is 1 over the ids and the specials, 0 over the padding.  cls_id / sep_id < 0 = no such special.  Rows come in sequence order, windows
+ * in order.  BF_E_ARG unless 1 <= row_len <= 1 << 20, body >= 1, 0 <= stride < body, max_rows_per_seq >= 0 and no other flag bit is set.
+ * ModelPtr: any live handle (it lends its device, workspaces and status word; the model is not consulted); NULL = BF_E_ARG.
+ * Device form: enqueues on `stream` (a hipStream_t), does not synchronise, returns 0 or BF_E_*.  ids_len = the elements of d_ids that may
+ * be read (the capacity of the tokenizer's id array will do: the exact total is on the device only); a sequence whose range is not inside
+ * [0, ids_len] or whose offsets decrease counts as empty and sets BfLastStatus bit 3 -- chaining behind a tokenizer call that overflowed
+ * its ids_cap is safe.  d_row_offsets_out[nseq+1] is always complete: the rows of sequence q are [off[q], off[q+1]).  d_rows_out and
+ * d_mask_out ([rows_cap * row_len] each), d_row_seq_out (the sequence of every row) and d_row_first_out (the index within its sequence of
+ * the row's first id; [rows_cap] each) may each be NULL; all four NULL = a size query.  No row r >= rows_cap of any output is written;
+ * rows dropped that way, and a row count or a d_row_first_out value of one sequence beyond INT32_MAX (they saturate), set BfLastStatus bit 0 (the call clears the
+ * status word first, like every batch call: what an earlier call on the handle reported is gone).  After
+ * BfReserve(h, max_docs >= nseq, ...) the call allocates nothing.  16-byte aligned d_rows_out, 4-byte aligned d_mask_out and
+ * row_len % 4 == 0 take the wide stores.  Host form: returns the row total, or BF_E_CAPACITY with complete offsets and nothing else written; with all four
+ * outputs NULL it is a size query that returns the total whatever rows_cap is.  id_offsets[0] < 0 = BF_E_ARG. */
+BF_API int IdsToRowsBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                         int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags,
+                         int32_t *d_rows_out, uint8_t *d_mask_out, int32_t *d_row_seq_out, int32_t *d_row_first_out,
+                         int64_t rows_cap, int64_t *d_row_offsets_out, void *stream);
+BF_API int64_t IdsToRowsBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                       int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags,
+                       int32_t *rows_out, uint8_t *mask_out, int32_t *row_seq_out, int32_t *row_first_out,
+                       int64_t rows_cap, int64_t *row_offsets_out);
+
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
 
@@ -260,6 +288,7 @@ BF_API int BfModelKind(void *ModelPtr);
 /* Optional: size every workspace of the handle for batches of up to max_docs documents / max_bytes bytes of text now, so that
  * later ...BatchDevice calls of that size allocate nothing (workspaces only ever grow; growing means hipMalloc, which
  * synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
+ * Every kind of handle has the workspaces of IdsToRowsBatchDevice sized for max_docs sequences (an [i2w]-only handle has no others).
  * Returns 0 or BF_E_*. */
 BF_API int BfReserve(void *ModelPtr, int64_t max_docs, int64_t max_bytes, int want_offsets);
 /* BPE models: the size of the pool from which documents with very many candidate arcs claim their working memory (about 16 bytes per
