@@ -228,6 +228,9 @@ BF_API int64_t TextToIdsBatch(void *ModelPtr, const char *text, const int64_t *d
  * PRECONDITION of every ...BatchDevice call: d_doc_offsets[0] == 0 and d_doc_offsets[ndocs] == total_bytes (offsets are relative to
  * d_text; pass d_text + first_byte and rebased offsets for a sub-range).  The kernels index their workspaces by these offsets; a
  * document whose range falls outside [0, total_bytes] is treated as empty and reported through BfLastStatus (bit 3).
+ * Every device pointer of every ...BatchDevice call needs only the natural alignment of its element type (1 byte for text, 4 for int32_t,
+ * 8 for int64_t): nothing in front of d_text or at / behind d_text + total_bytes is looked at, nothing in front of an output or at / behind
+ * its capacity is written -- the contract tests/test_gpu_caller_pointers.py pins, with every pointer inside a larger buffer.
  * A handle owns ONE set of device workspaces: the ...Device calls on one handle must be ordered on the device (the same
  * stream, or streams the caller synchronises); for concurrent batches use one handle per stream (LoadModel is cheap:
  * a few MB of tables).  The host-buffer calls serialise on the handle's mutex and synchronise before they return. */

@@ -13,14 +13,14 @@ import pytest
 import bfutil
 import blingfire_amd as bf
 import flat_cases
+import pointer_cases
 
 WP_MODELS = ["bert_base_tok.bin", "bert_base_cased_tok.bin", "bert_chinese.bin"]
 # (max_ids, unk, waves, ranges): ranges 0 = four per wave (as many as documents allow)
 CONFS = [(512, 100, 1, 0), (512, 100, 2, 3), (16, 7, 1, 1), (64, 5, 3, 7), (0, 100, 2, 1), (512, 100, 2, 1)]
 
 
-@pytest.fixture(scope="module")
-def ht():
+def load_hosttest():
     L = ctypes.CDLL(bfutil.HOSTTEST_LIB)
     L.bft_load.restype = ctypes.c_void_p
     L.bft_load.argtypes = [ctypes.c_char_p]
@@ -34,6 +34,11 @@ def ht():
     L.bft_emu_flat_batch_offsets.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]
     return L
+
+
+@pytest.fixture(scope="module")
+def ht():
+    return load_hosttest()
 
 
 def flat_batch_offsets(ht, h, text, off, max_ids, unk, nwaves, nranges):
@@ -282,6 +287,151 @@ def test_invalid_utf8_everywhere(ht):
             body = bytearray(b"\xef\xbb\xbf") + body   # a BOM at the start is skipped, elsewhere it is a character
         docs.append(bytes(body))
     check(ht, model, docs, [(512, 100, 2, 0), (512, 100, 1, 1), (512, 100, 3, 9)])
+
+
+@pytest.mark.parametrize("name", ["mixture", "shapes"])
+def test_outputs_at_odd_alignments(ht, name):
+    """k_wp_merge derives its 16-byte row stores from the caller's pointer values (head / oq from ids_out, rows_ok from starts_out / ends_out) and
+    bft_emu_flat_batch_offsets hands the caller's three arrays straight to it: every combination of pointer_cases.OUT_SHIFTS_3 -- in 12 of the 16
+    starts_out / ends_out are not aligned like ids_out, the element-wise path -- gives the ids and spans of the aligned run (which the tests above
+    pin to the oracle), and the canaries in front of and behind each array stay"""
+    model = bfutil.bert_model_name()
+    text, off = flat_cases.mixture(600) if name == "mixture" else flat_cases.shapes()
+    text = np.ascontiguousarray(text)
+    nd = len(off) - 1
+    h = ht.bft_load(bfutil.model_path(model).encode())
+    try:
+        r0, ids0, sts0, ens0, ido0, _ = flat_batch_offsets(ht, h, text, off, 512, 100, 2, 0)
+        assert r0 > 0 and r0 == ido0[-1]
+        ids0, sts0, ens0 = ids0.copy(), sts0.copy(), ens0.copy()
+        ora = bfutil.oracle()
+        ho = ora.load(bfutil.model_path(model))
+        gids, goff = ora.batch(ho, text, off, 512, 100)
+        ora.free(ho)
+        assert np.array_equal(ido0, goff) and np.array_equal(ids0, gids)
+        for shifts in pointer_cases.OUT_SHIFTS_3:
+            rooms = [pointer_cases.host_room(r0, s) for s in shifts]
+            ido = np.zeros(nd + 1, dtype=np.int64)
+            st = np.zeros(16, dtype=np.uint64)
+            r = ht.bft_emu_flat_batch_offsets(h, text.ctypes.data, len(text), off.ctypes.data, nd, 512, 100, 2, 0, rooms[0][1].ctypes.data, rooms[1][1].ctypes.data,
+                                              rooms[2][1].ctypes.data, r0, ido.ctypes.data, st.ctypes.data)
+            assert r == r0 and np.array_equal(ido, ido0), (shifts, r, r0)
+            for what, (whole, view, first), want in zip(("ids", "first bytes", "last bytes"), rooms, (ids0, sts0, ens0)):
+                if not np.array_equal(view, want):
+                    bad = int(np.nonzero(view != want)[0][0])
+                    raise AssertionError("shifts %s: %s differ at id %d (document %d): %d, aligned run %d" % (
+                        shifts, what, bad, int(np.searchsorted(ido0, bad, side="right")) - 1, view[bad], want[bad]))
+                canary = pointer_cases.CANARY[whole.dtype]
+                assert (whole[:first] == canary).all() and (whole[first + r0:] == canary).all(), "shifts %s: %s written outside [0, %d)" % (shifts, what, r0)
+    finally:
+        ht.bft_free(h)
+
+
+def test_text_inside_hostile_buffers(ht):
+    """the END_CASES / START_CASES of tests/pointer_cases.py as the last / first document of a text that lies inside a larger buffer, between bytes
+    that would complete its truncated characters and continue its words, 0xFF bytes, zeros, at byte shifts 0, 1, 8, 15 behind a 16-byte boundary (in turn): the
+    oracle's answer for the text alone (wf_units reads a word of up to 16 bytes with two 8-byte loads only where they end inside the text)"""
+    model = bfutil.bert_model_name()
+    h = ht.bft_load(bfutil.model_path(model).encode())
+    ora = bfutil.oracle()
+    ho = ora.load(bfutil.model_path(model))
+    spans = {}
+    try:
+        for k, (name, docs) in enumerate(pointer_cases.edge_batches()):
+            text, off = flat_cases.pack(docs)
+            gids, goff = ora.batch(ho, text, off, 512, 100)
+            for b in docs:
+                if b not in spans:
+                    c, _, s_, e_ = ora.with_offsets(ho, b, 512, 100, "bfo_text_to_ids_with_offsets")
+                    spans[b] = (s_[:c], e_[:c])
+            ws = np.array([x for b in docs for x in spans[b][0]], dtype=np.int32)
+            we = np.array([x for b in docs for x in spans[b][1]], dtype=np.int32)
+            for j, (sur, (front, back)) in enumerate(pointer_cases.SURROUNDINGS.items()):
+                for shift in ((0, 1, 8, 15)[(k + j) % 4],):                      # (every shift in every surrounding 13 times over the batches)
+                    arena, view, before = pointer_cases.host_place(text, shift, front, back)
+                    for nw, nr in (((1, 1), (2, 0))[(k // 4) % 2],):
+                        r, ids, ido, _ = flat_batch(ht, h, view, off, 512, 100, nw, nr)
+                        assert r >= 0 and np.array_equal(ido, goff) and np.array_equal(ids, gids), (name, sur, shift, nw, nr)
+                        r, ids, sts, ens, ido, _ = flat_batch_offsets(ht, h, view, off, 512, 100, nw, nr)
+                        assert r >= 0 and np.array_equal(ido, goff) and np.array_equal(ids, gids) and np.array_equal(sts, ws) and np.array_equal(ens, we), (name, sur, shift, nw, nr)
+                    assert np.array_equal(arena, before), (name, sur, shift)
+    finally:
+        ora.free(ho)
+        ht.bft_free(h)
+
+
+_GUARD_PAGE_CHILD = r"""
+import ctypes, mmap, sys
+import numpy as np
+import bfutil, flat_cases, pointer_cases, test_flat_emu
+PAGE = mmap.PAGESIZE
+libc = ctypes.CDLL(None, use_errno=True)
+libc.mprotect.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+if len(sys.argv) > 1:
+    bfutil.HOSTTEST_LIB = sys.argv[1]          # (another build of tests/hosttest, for trying the test on a changed source)
+ht = test_flat_emu.load_hosttest()
+model = bfutil.model_path(bfutil.bert_model_name())
+h = ht.bft_load(model.encode())
+ora = bfutil.oracle()
+ho = ora.load(model)
+n = 0
+for name, docs in pointer_cases.edge_batches():
+    text, off = flat_cases.pack(docs)
+    size = (len(text) + PAGE - 1) // PAGE * PAGE + PAGE
+    mm = mmap.mmap(-1, size)
+    base = ctypes.addressof(ctypes.c_char.from_buffer(mm))
+    assert libc.mprotect(base + size - PAGE, PAGE, 0) == 0          # PROT_NONE: a read of one byte behind the text ends the process
+    view = np.frombuffer(mm, dtype=np.uint8, count=size - PAGE)[size - PAGE - len(text):]
+    view[:] = text
+    assert view.ctypes.data + len(text) == base + size - PAGE
+    gids, goff = ora.batch(ho, text, off, 512, 100)
+    for nw, nr in ((1, 1), (2, 0)):
+        r, ids, ido, _ = test_flat_emu.flat_batch(ht, h, view, off, 512, 100, nw, nr)
+        assert r >= 0 and np.array_equal(ido, goff) and np.array_equal(ids, gids), name
+        r, ids, sts, ens, ido, _ = test_flat_emu.flat_batch_offsets(ht, h, view, off, 512, 100, nw, nr)
+        assert r >= 0 and np.array_equal(ido, goff) and np.array_equal(ids, gids), name
+        n += 1
+print("read nothing behind the text in %d runs" % n)
+sys.stdout.flush()
+import os
+os._exit(0)
+"""
+
+
+def test_nothing_behind_the_text_is_read():
+    """on the GPU an over-read of a few bytes lands in mapped memory and, where the bytes are masked afterwards, changes nothing; here the flat
+    program runs in a child process with the end of the text against a page without access: every END_CASE batch (the last word inside the last
+    16 bytes, the end of the text at 0, 1, 7, 8, 9, 15 bytes past a multiple of 16 from the start) gives the oracle's answer and the child ends
+    normally -- wf_units' `pa + 16 <= total_bytes`, and every other load of the shared sources near the end of the text"""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = dict(os.environ, PYTHONPATH=here + os.pathsep + bfutil.ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", _GUARD_PAGE_CHILD], cwd=here, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0 and b"read nothing behind the text in 104 runs" in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-1500:])
+
+
+@pytest.mark.parametrize("model,max_ids,unk", [("bert_base_tok.bin", 512, 100), ("xlm_roberta_base.bin", 1024, 3), ("gpt2.bin", 2048, 0)])
+def test_pointer_cases_prove_themselves(model, max_ids, unk):
+    """the END_CASES / START_CASES of tests/pointer_cases.py (the GPU tier places them inside hostile buffers) do change their answer when a
+    neighbouring byte of the completing surrounding is taken in -- for a model of every kind, ids and byte offsets, on the CPU checker"""
+    ck = bfutil.reference() if bfutil.have_ref() else bfutil.oracle()
+    name = "TextToIdsWithOffsets" if bfutil.have_ref() else "bfo_text_to_ids_with_offsets"
+    hck = ck.load(bfutil.model_path(model))
+
+    def ids_only(b):
+        c, buf = ck.text_to_ids(hck, b, max_ids, unk)
+        return c, tuple(buf[:c])
+
+    def with_offsets(b):
+        c, i, s, e = ck.with_offsets(hck, b, max_ids, unk, name)
+        return c, tuple(i), tuple(s), tuple(e)
+
+    try:
+        assert pointer_cases.prove(ids_only) > 700 and pointer_cases.prove(with_offsets) > 700
+    finally:
+        ck.free(hck)
 
 
 def test_any_batch_hypothesis(ht):
