@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <condition_variable>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -49,6 +50,10 @@ bool hip_ok(hipError_t e, const char *what)
 
 struct DevBuf {
     void *p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     // Grow-only.  Growing is a hipMalloc + hipFree (both synchronise the device): callers that must not synchronise size the
     // workspaces once with BfReserve.
     bool reserve(size_t bytes)
@@ -80,6 +85,10 @@ template <class T> bool upload(DevBuf &b, const std::vector<T> &v, size_t pad_el
 // page-locked host memory (grow-only), the staging side of the chunked host-buffer path
 struct PinBuf {
     void *p = nullptr; size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
     bool reserve(size_t bytes)
     {
         if (bytes <= cap) return true;
@@ -116,16 +125,13 @@ struct HostPipe {
         if (!pin_status.reserve(64)) return false;
         ready = true; return true;
     }
-    void release()
+    ~HostPipe()                         // (the buffers free themselves afterwards)
     {
         for (int i = 0; i < NS; ++i) {
-            pin_text[i].release(); pin_off[i].release(); pin_idoff[i].release(); pin_ids[i].release();
-            dev_text[i].release(); dev_off[i].release(); dev_ids[i].release(); dev_idoff[i].release();
             if (ev_h2d[i]) (void)hipEventDestroy(ev_h2d[i]);
             if (ev_cmp[i]) (void)hipEventDestroy(ev_cmp[i]);
             if (ev_d2h[i]) (void)hipEventDestroy(ev_d2h[i]);
         }
-        pin_status.release();
         if (s_in) (void)hipStreamDestroy(s_in);
         if (s_out) (void)hipStreamDestroy(s_out);
         if (s_meta) (void)hipStreamDestroy(s_meta);
@@ -200,13 +206,12 @@ struct Handle {
     int small_status = -1;                                     // status word of the last batch when it took that path (BfLastStatus), else -1
     HostPipe pipe;                                              // chunked host-buffer path (run_host_chunked)
     int64_t host_chunk_bytes = 128ll << 20;                     // its largest chunk (BfSetHostChunkBytes; 0 = never chunk); batches of at least this size take it
+    // every buffer above frees itself behind this body (DevBuf, PinBuf, HostPipe), inside the same delete and under the same current device;
+    // m_small_dev is only the device-side name of m_small's memory and is never used without it
     ~Handle()
     {
         for (Handle *c : shards) if (c && c != this) { DeviceGuard dg(c->device); (void)hipDeviceSynchronize(); delete c; }
         shards.clear();
-        pipe.release(); m_small.release();
-        for (DevBuf *b : {&w_rowseq, &w_rowfirst, &t_w2h, &t_w2h_pats, &t_w2h_l1, &t_w2h_pages, &w_hcls, &w_hnch, &w_hsrc, &t_segscore, &t_segid, &t_bpetab, &t_bpe_prio, &t_bpe_place, &t_dk_l1, &t_dk_pages, &t_dn_l1, &t_dn_pages, &t_dn_pool, &t_k2i, &t_rows, &w_keys, &w_keyoff, &w_dids, &w_dret, &w_vals, &t_i2w_off, &t_i2w_data, &t_kind, &t_wbd, &t_info, &t_acts, &t_cp_l1, &t_cp_pages, &t_multi, &t_wcp_l1, &t_wcp_pages, &t_dict, &t_seginfo, &w_s1, &w_s2, &w_s3, &w_s4, &w_big, &w_perm, &w_hist, &w_narcs, &w_bwflags, &w_cls, &w_nchars, &w_tmp, &w_counts, &w_flags, &w_out, &w_outoff,
-                          &w_bsums, &w_misc, &w_text, &w_docoff, &w_ids, &w_idoff, &w_starts, &w_ends, &w_srcoff, &w_span, &w_long, &w_preplong, &w_w2tlong, &w_ent, &w_home, &w_entoff, &w_entcnt, &w_dstat, &w_ranges, &w_list, &w_wrec, &t_flat, &w_espan, &w_hspan, &w_chard}) b->release();
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         magic = 0;
@@ -1027,59 +1032,83 @@ int run_i2t_device(Handle *h, const int32_t *d_ids, const int64_t *d_id_off, int
     return hip_ok(hipGetLastError(), "IdsToText kernels") ? 0 : BF_E_DEVICE;
 }
 
+// ---- the secondary calls on host buffers: one staging helper, one two-pass driver ----
+//
+// A ragged host batch on its way to the device.  `rel` (the caller's offsets, rebased to their first entry) is the source of an asynchronous
+// copy: the object stays in the caller's frame until the caller's first synchronisation of the stream.
+struct Staged { std::vector<int64_t> rel; int64_t total = 0; };
+
+// Validates (data, off, n), reserves d_data / d_off and queues the copies of the payload behind off[0] and of the rebased offsets: 0 or BF_E_*.
+// elem: bytes per element (1 text, 4 ids and keys).  The payload is off[n] - off[0] elements, or `len` of them where the caller counts them
+// itself (IdsToRowsBatch: up to the largest offset).  Synchronises only where it fails with a copy queued.
+int stage_ragged(Staged &st, const void *data, size_t elem, const int64_t *off, int64_t n, DevBuf &d_data, DevBuf &d_off, hipStream_t s, int64_t len = -1)
+{
+    if (n < 0 || !off) return BF_E_ARG;
+    const int64_t base = off[0];
+    st.total = len >= 0 ? len : (n > 0 ? off[n] - base : 0);
+    if (st.total < 0 || (st.total > 0 && !data)) return BF_E_ARG;
+    if (!d_data.reserve(elem == 1 ? (size_t)st.total + 16 : (size_t)(st.total + 1) * elem) || !d_off.reserve((size_t)(n + 1) * 8)) return BF_E_DEVICE;
+    st.rel.resize((size_t)n + 1);
+    for (int64_t i = 0; i <= n; ++i) st.rel[(size_t)i] = off[i] - base;
+    if (st.total > 0 && !hip_ok(hipMemcpyAsync(d_data.p, (const char *)data + base * (int64_t)elem, (size_t)st.total * elem, hipMemcpyHostToDevice, s), "H2D payload")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemcpyAsync(d_off.p, st.rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
+    return 0;
+}
+
+// Behind stage_ragged, for a call whose output is as ragged as its input: size pass, offsets to the caller, capacity check, fill pass, output
+// to the caller.  Returns the output total or BF_E_*.
+//   pass(d_out, cap)  wraps the call's run_*_device: the size pass (which leaves the n + 1 output offsets in d_off) when d_out is NULL,
+//                     else the fill pass into d_out (d_out_buf, the call's output staging of `elem` bytes per element)
+//   after_size        optional: queues further copies to the host behind the size pass (a status word, per-item results); false = it failed
+// The contract of every caller: the offsets are complete before BF_E_CAPACITY is answered and the output is untouched then; a NULL output
+// with a non-empty result answers BF_E_ARG; a NULL off_out is served from a temporary; whatever ends the call early after work was queued
+// synchronises the stream first (the kernels write the handle's workspaces, which the caller's lock protects only until it returns, and
+// the copies read `Staged` and write the caller's arrays).
+// Locks stay with the callers.  All take h->mu; a call also takes h->defer_mu (before h->mu) exactly when it stages through w_ids, w_starts or
+// w_ends, which may hold a sharded range's ids that wait for their copy out: words, sentences, ids-to-text, hashes, hyphenation and rows do,
+// normalize-spaces and the dictionary lookup do not.
+int64_t two_pass_host(hipStream_t s, int64_t n, DevBuf &d_off, DevBuf &d_out_buf, size_t elem, void *out, int64_t cap, int64_t *off_out,
+                      const std::function<int(void *d_out, int64_t out_cap)> &pass, const std::function<bool()> &after_size = nullptr)
+{
+    auto fail = [s](int64_t rc) { (void)hipStreamSynchronize(s); return rc; };
+    if (!d_off.reserve((size_t)(n + 1) * 8)) return fail(BF_E_DEVICE);
+    int rc = pass(nullptr, 0);
+    if (rc != 0) return fail(rc);
+    std::vector<int64_t> tmp_off;
+    if (!off_out) { tmp_off.resize((size_t)n + 1); off_out = tmp_off.data(); }
+    if (!hip_ok(hipMemcpyAsync(off_out, d_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") || (after_size && !after_size())) return fail(BF_E_DEVICE);
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    const int64_t total = off_out[n];
+    if (total > cap) return BF_E_CAPACITY;
+    if (total <= 0) return total;
+    if (!out) return BF_E_ARG;
+    if (!d_out_buf.reserve((size_t)total * elem + 16)) return BF_E_DEVICE;
+    rc = pass(d_out_buf.p, total);
+    if (rc != 0) return fail(rc);
+    if (!hip_ok(hipMemcpyAsync(out, d_out_buf.p, (size_t)total * elem, hipMemcpyDeviceToHost, s), "D2H output")) return fail(BF_E_DEVICE);
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? total : BF_E_DEVICE;
+}
+
 // host buffers: text of sequence d = text_out[text_off_out[d] .. text_off_out[d+1]); returns the total byte count
 int64_t run_i2t_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, char *text_out, int64_t text_cap,
                      int64_t *text_off_out, int skip_special, bool *unknown_id = nullptr)
 {
     if (!h->m.has_i2w) return BF_E_UNSUPPORTED;
-    if (nseq < 0 || !id_off || (nseq > 0 && id_off[nseq] > id_off[0] && !ids)) return BF_E_ARG;
-    const int64_t base = id_off[0], total_ids = nseq > 0 ? id_off[nseq] - base : 0;
-    if (total_ids < 0) return BF_E_ARG;
-    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (the id buffers this call uses may hold a sharded range's ids that wait for their copy out)
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    if (!h->w_ids.reserve((size_t)(total_ids + 1) * 4) || !h->w_docoff.reserve((size_t)(nseq + 1) * 8) || !h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
-    std::vector<int64_t> rel((size_t)nseq + 1);
-    for (int64_t i = 0; i <= nseq; ++i) rel[(size_t)i] = id_off[i] - base;
-    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
-    if (total_ids > 0 && !hip_ok(hipMemcpyAsync(h->w_ids.p, ids + base, (size_t)total_ids * 4, hipMemcpyHostToDevice, s), "H2D ids")) return BF_E_DEVICE;
-    if (!hip_ok(hipMemcpyAsync(h->w_docoff.p, rel.data(), (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) return BF_E_DEVICE;
-    int rc = run_i2t_device(h, h->w_ids.as<int32_t>(), h->w_docoff.as<int64_t>(), nseq, nullptr, 0, h->w_idoff.as<int64_t>(), skip_special, s);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    std::vector<int64_t> tmp_off;
-    int64_t *dst_off = text_off_out;
-    if (!dst_off) { tmp_off.resize((size_t)nseq + 1); dst_off = tmp_off.data(); }
+    Staged st;
     int status = 0;
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
-        !hip_ok(hipMemcpyAsync(&status, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost, s), "D2H status") ||
-        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;      // the status word the size pass reports an unknown id in
+    const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s);
+    if (rc != 0) return rc;
+    const int64_t total = two_pass_host(s, nseq, h->w_idoff, h->w_text, 1, text_out, text_cap, text_off_out,
+        [&](void *d_out, int64_t out_cap) {
+            return run_i2t_device(h, h->w_ids.as<int32_t>(), h->w_docoff.as<int64_t>(), nseq, (char *)d_out, out_cap, h->w_idoff.as<int64_t>(), skip_special, s);
+        },
+        [&]() { return hip_ok(hipMemcpyAsync(&status, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost, s), "D2H status"); });
     if (unknown_id) *unknown_id = (status & 4) != 0;
-    const int64_t total = dst_off[nseq];
-    if (total > text_cap) return BF_E_CAPACITY;
-    if (total > 0) {
-        if (!text_out) return BF_E_ARG;
-        if (!h->w_text.reserve((size_t)total + 16)) return BF_E_DEVICE;
-        rc = run_i2t_device(h, h->w_ids.as<int32_t>(), h->w_docoff.as<int64_t>(), nseq, h->w_text.as<char>(), total, h->w_idoff.as<int64_t>(), skip_special, s);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(text_out, h->w_text.p, (size_t)total, hipMemcpyDeviceToHost, s), "D2H text") ||
-            !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return total;
-}
-
-// upload a batch of documents (host buffers) into the handle's text / offset buffers; returns the byte total or BF_E_*
-int64_t upload_docs(Handle *h, const char *text, const int64_t *doc_off, int64_t ndocs, hipStream_t s)
-{
-    if (ndocs < 0 || !doc_off || (ndocs > 0 && !text && doc_off[ndocs] > doc_off[0])) return BF_E_ARG;
-    const int64_t base = doc_off[0], total = ndocs > 0 ? doc_off[ndocs] - base : 0;
-    if (total < 0) return BF_E_ARG;
-    if (!h->w_text.reserve((size_t)total + 16) || !h->w_docoff.reserve((size_t)(ndocs + 1) * 8) || !h->w_outoff.reserve((size_t)(ndocs + 1) * 8)) return BF_E_DEVICE;
-    std::vector<int64_t> rel((size_t)ndocs + 1);
-    for (int64_t i = 0; i <= ndocs; ++i) rel[(size_t)i] = doc_off[i] - base;
-    if (total > 0 && !hip_ok(hipMemcpyAsync(h->w_text.p, text + base, (size_t)total, hipMemcpyHostToDevice, s), "H2D text")) return BF_E_DEVICE;
-    if (!hip_ok(hipMemcpyAsync(h->w_docoff.p, rel.data(), (size_t)(ndocs + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) return BF_E_DEVICE;
-    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;     // `rel` goes out of scope
     return total;
 }
 
@@ -1218,12 +1247,11 @@ int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int6
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    if (!h->w_ids.reserve((size_t)(ids_len + 1) * 4) || !h->w_docoff.reserve((size_t)(nseq + 1) * 8) || !h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
-    std::vector<int64_t> rel((size_t)nseq + 1);
-    for (int64_t i = 0; i <= nseq; ++i) rel[(size_t)i] = id_off[i] - base;
-    if (ids_len > 0 && !hip_ok(hipMemcpyAsync(h->w_ids.p, ids + base, (size_t)ids_len * 4, hipMemcpyHostToDevice, s), "H2D ids")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
-    if (!hip_ok(hipMemcpyAsync(h->w_docoff.p, rel.data(), (size_t)(nseq + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
-    int rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, nullptr, nullptr, nullptr, nullptr, 0, h->w_idoff.as<int64_t>(), s);
+    if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
+    Staged st;
+    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, nullptr, nullptr, nullptr, nullptr, 0, h->w_idoff.as<int64_t>(), s);
     if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
     if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
         !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
@@ -1529,36 +1557,16 @@ int64_t text_batch_host(void *p, const char *text, const int64_t *doc_off, int64
 {
     Handle *h = p ? as_handle(p) : (mode == 2 ? default_sbd() : default_wbd());
     if (!h) return BF_E_ARG;
-    if (ndocs < 0 || !doc_off || (ndocs > 0 && !text && doc_off[ndocs] > doc_off[0])) return BF_E_ARG;
-    const int64_t base = doc_off[0], total = ndocs > 0 ? doc_off[ndocs] - base : 0;
-    if (total < 0) return BF_E_ARG;
-    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (the id buffers this call uses may hold a sharded range's ids that wait for their copy out)
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    if (!h->w_text.reserve((size_t)total + 16) || !h->w_docoff.reserve((size_t)(ndocs + 1) * 8) || !h->w_outoff.reserve((size_t)(ndocs + 1) * 8)) return BF_E_DEVICE;
-    std::vector<int64_t> rel((size_t)ndocs + 1);
-    for (int64_t i = 0; i <= ndocs; ++i) rel[(size_t)i] = doc_off[i] - base;
-    if (total > 0 && !hip_ok(hipMemcpyAsync(h->w_text.p, text + base, (size_t)total, hipMemcpyHostToDevice, s), "H2D text")) return BF_E_DEVICE;
-    if (!hip_ok(hipMemcpyAsync(h->w_docoff.p, rel.data(), (size_t)(ndocs + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) return BF_E_DEVICE;
-    int rc = run_words_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, total, nullptr, 0, h->w_outoff.as<int64_t>(), s, true, mode);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    std::vector<int64_t> tmp_off;
-    int64_t *dst_off = text_off_out;
-    if (!dst_off) { tmp_off.resize((size_t)ndocs + 1); dst_off = tmp_off.data(); }
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(ndocs + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
-        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t nout = dst_off[ndocs];
-    if (nout > text_cap) return BF_E_CAPACITY;
-    if (nout > 0) {
-        if (!text_out) return BF_E_ARG;
-        if (!h->w_out.reserve((size_t)nout + 16)) return BF_E_DEVICE;
-        rc = run_words_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, total, h->w_out.as<char>(), nout, h->w_outoff.as<int64_t>(), s, false, mode);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(text_out, h->w_out.p, (size_t)nout, hipMemcpyDeviceToHost, s), "D2H text") ||
-            !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return nout;
+    Staged st;
+    const int rc = stage_ragged(st, text, 1, doc_off, ndocs, h->w_text, h->w_docoff, s);
+    if (rc != 0) return rc;
+    return two_pass_host(s, ndocs, h->w_outoff, h->w_out, 1, text_out, text_cap, text_off_out, [&](void *d_out, int64_t out_cap) {
+        return run_words_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, st.total, (char *)d_out, out_cap, h->w_outoff.as<int64_t>(), s, !d_out, mode);
+    });
 }
 
 } // namespace
@@ -1752,11 +1760,12 @@ int NormalizeSpaces(const char *s, int n, char *out, const int max_out, const in
     DeviceGuard dg(h->device); if (!dg.ok) return -1;
     hipStream_t st = h->stream;
     const int64_t off[2] = {0, n};
-    if (upload_docs(h, s, off, 1, st) < 0) return -1;
-    if (run_normsp_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, u_space, nullptr, 0, h->w_outoff.as<int64_t>(), st, true) != 0) return -1;
+    Staged in;
+    if (!h->w_outoff.reserve(16) || stage_ragged(in, s, 1, off, 1, h->w_text, h->w_docoff, st) != 0) return -1;
+    if (run_normsp_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, u_space, nullptr, 0, h->w_outoff.as<int64_t>(), st, true) != 0) { (void)hipStreamSynchronize(st); return -1; }
     int32_t len = 0, aux = 0;
-    if (!hip_ok(hipMemcpyAsync(&len, h->w_counts.p, 4, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(hipMemcpyAsync(&aux, h->w_nchars.p, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-        !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return -1;
+    const bool copied = hip_ok(hipMemcpyAsync(&len, h->w_counts.p, 4, hipMemcpyDeviceToHost, st), "D2H") && hip_ok(hipMemcpyAsync(&aux, h->w_nchars.p, 4, hipMemcpyDeviceToHost, st), "D2H");
+    if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !copied) return -1;
     if (aux & 1) return -1;                                                    // invalid UTF-8 / nothing decoded (tokdll:646-648)
     unsigned char ub[4];
     if ((aux >> 1) > 0 && utf8_encode(u_space, ub) == 0) return -1;            // a uSpace that cannot be encoded (FAUtf8Utils.cpp:549-552)
@@ -1777,22 +1786,12 @@ int64_t NormalizeSpacesBatch(const char *text, const int64_t *doc_off, int64_t n
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    const int64_t total = upload_docs(h, text, doc_off, ndocs, s);
-    if (total < 0) return total;
-    int rc = run_normsp_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, u_space, nullptr, 0, h->w_outoff.as<int64_t>(), s, true);
+    Staged st;
+    const int rc = stage_ragged(st, text, 1, doc_off, ndocs, h->w_text, h->w_docoff, s);
     if (rc != 0) return rc;
-    std::vector<int64_t> tmp_off; int64_t *dst_off = text_off_out;
-    if (!dst_off) { tmp_off.resize((size_t)ndocs + 1); dst_off = tmp_off.data(); }
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(ndocs + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t nout = dst_off[ndocs];
-    if (nout > text_cap) return BF_E_CAPACITY;
-    if (nout > 0) {
-        if (!text_out || !h->w_out.reserve((size_t)nout + 16)) return text_out ? BF_E_DEVICE : BF_E_ARG;
-        rc = run_normsp_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, u_space, h->w_out.as<char>(), nout, h->w_outoff.as<int64_t>(), s, false);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(text_out, h->w_out.p, (size_t)nout, hipMemcpyDeviceToHost, s), "D2H text") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return nout;
+    return two_pass_host(s, ndocs, h->w_outoff, h->w_out, 1, text_out, text_cap, text_off_out, [&](void *d_out, int64_t out_cap) {
+        return run_normsp_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, u_space, (char *)d_out, out_cap, h->w_outoff.as<int64_t>(), s, !d_out);
+    });
 }
 
 /* ---- TextToHashes (reference tokdll:683-815), model-free */
@@ -1810,10 +1809,12 @@ int TextToHashes(const char *s, int n, int32_t *hashes, const int max_hashes, in
     DeviceGuard dg(h->device); if (!dg.ok) return -1;
     hipStream_t st = h->stream;
     const int64_t off[2] = {0, n};
-    if (upload_docs(h, s, off, 1, st) < 0) return -1;
-    if (run_hashes_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, ngrams, bucket, nullptr, 0, h->w_outoff.as<int64_t>(), st, true) != 0) return -1;
+    Staged in;
+    if (!h->w_outoff.reserve(16) || stage_ragged(in, s, 1, off, 1, h->w_text, h->w_docoff, st) != 0) return -1;
+    if (run_hashes_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, ngrams, bucket, nullptr, 0, h->w_outoff.as<int64_t>(), st, true) != 0) { (void)hipStreamSynchronize(st); return -1; }
     int32_t cnt = 0;
-    if (!hip_ok(hipMemcpyAsync(&cnt, h->w_counts.p, 4, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return -1;
+    const bool copied = hip_ok(hipMemcpyAsync(&cnt, h->w_counts.p, 4, hipMemcpyDeviceToHost, st), "D2H");
+    if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !copied) return -1;
     tokens = n == 0 ? 0 : cnt / ngrams;                                         // GetTokenCount (tokdll:718-737): 0 for an empty string
     if ((int64_t)tokens * ngrams >= max_hashes) return n * ngrams;             // tokdll:795-798: "requested memory amount"
     if (cnt > max_hashes || !hashes) return -1;                                // (n == 0: one empty token is hashed, tokdll:743-771)
@@ -1833,22 +1834,12 @@ int64_t TextToHashesBatch(const char *text, const int64_t *doc_off, int64_t ndoc
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    const int64_t total = upload_docs(h, text, doc_off, ndocs, s);
-    if (total < 0) return total;
-    int rc = run_hashes_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, ngrams, bucket, nullptr, 0, h->w_outoff.as<int64_t>(), s, true);
+    Staged st;
+    const int rc = stage_ragged(st, text, 1, doc_off, ndocs, h->w_text, h->w_docoff, s);
     if (rc != 0) return rc;
-    std::vector<int64_t> tmp_off; int64_t *dst_off = hash_off_out;
-    if (!dst_off) { tmp_off.resize((size_t)ndocs + 1); dst_off = tmp_off.data(); }
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(ndocs + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t nout = dst_off[ndocs];
-    if (nout > hashes_cap) return BF_E_CAPACITY;
-    if (nout > 0) {
-        if (!hashes_out || !h->w_ids.reserve((size_t)nout * 4 + 16)) return hashes_out ? BF_E_DEVICE : BF_E_ARG;
-        rc = run_hashes_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, ngrams, bucket, h->w_ids.as<int32_t>(), nout, h->w_outoff.as<int64_t>(), s, false);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(hashes_out, h->w_ids.p, (size_t)nout * 4, hipMemcpyDeviceToHost, s), "D2H hashes") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return nout;
+    return two_pass_host(s, ndocs, h->w_outoff, h->w_ids, 4, hashes_out, hashes_cap, hash_off_out, [&](void *d_out, int64_t out_cap) {
+        return run_hashes_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), ndocs, ngrams, bucket, (int32_t *)d_out, out_cap, h->w_outoff.as<int64_t>(), s, !d_out);
+    });
 }
 
 /* ---- IdsToText (reference tokdll:1689-1745) and its batch forms: a variable-length byte gather on the GPU */
@@ -1935,34 +1926,20 @@ int64_t DictGetInfoBatch(void *p, const int32_t *keys, const int64_t *key_offset
 {
     Handle *h = as_handle(p);
     if (!h) return BF_E_ARG;
-    if (nkeys < 0 || !key_offsets || (nkeys > 0 && key_offsets[nkeys] > key_offsets[0] && !keys)) return BF_E_ARG;
-    const int64_t base = key_offsets[0], total = nkeys > 0 ? key_offsets[nkeys] - base : 0;
-    if (total < 0) return BF_E_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
-    if (!h->w_keys.reserve((size_t)(total + 1) * 4) || !h->w_keyoff.reserve((size_t)(nkeys + 1) * 8) || !h->w_outoff.reserve((size_t)(nkeys + 1) * 8)) return BF_E_DEVICE;
-    std::vector<int64_t> rel((size_t)nkeys + 1);
-    for (int64_t i = 0; i <= nkeys; ++i) rel[(size_t)i] = key_offsets[i] - base;
-    if (total > 0 && !hip_ok(hipMemcpyAsync(h->w_keys.p, keys + base, (size_t)total * 4, hipMemcpyHostToDevice, s), "H2D keys")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
-    if (!hip_ok(hipMemcpyAsync(h->w_keyoff.p, rel.data(), (size_t)(nkeys + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
-    int rc = run_dict_device(h, h->w_keys.as<int32_t>(), h->w_keyoff.as<int64_t>(), nkeys, nullptr, nullptr, nullptr, 0, h->w_outoff.as<int64_t>(), s, true);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    std::vector<int64_t> tmp_off; int64_t *dst_off = value_offsets_out;
-    if (!dst_off) { tmp_off.resize((size_t)nkeys + 1); dst_off = tmp_off.data(); }
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(nkeys + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
-        (ret_out && nkeys > 0 && !hip_ok(hipMemcpyAsync(ret_out, h->w_dret.p, (size_t)nkeys * 4, hipMemcpyDeviceToHost, s), "D2H ret")) ||
-        (info_ids_out && nkeys > 0 && !hip_ok(hipMemcpyAsync(info_ids_out, h->w_dids.p, (size_t)nkeys * 4, hipMemcpyDeviceToHost, s), "D2H ids")) ||
-        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t nvals = dst_off[nkeys];
-    if (nvals > values_cap) return BF_E_CAPACITY;
-    if (nvals > 0) {
-        if (!values_out || !h->w_vals.reserve((size_t)nvals * 4 + 16)) return values_out ? BF_E_DEVICE : BF_E_ARG;
-        rc = run_dict_device(h, h->w_keys.as<int32_t>(), h->w_keyoff.as<int64_t>(), nkeys, nullptr, nullptr, h->w_vals.as<int32_t>(), nvals, h->w_outoff.as<int64_t>(), s, false);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(values_out, h->w_vals.p, (size_t)nvals * 4, hipMemcpyDeviceToHost, s), "D2H values") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return nvals;
+    Staged st;
+    const int rc = stage_ragged(st, keys, 4, key_offsets, nkeys, h->w_keys, h->w_keyoff, s);
+    if (rc != 0) return rc;
+    return two_pass_host(s, nkeys, h->w_outoff, h->w_vals, 4, values_out, values_cap, value_offsets_out,
+        [&](void *d_out, int64_t out_cap) {
+            return run_dict_device(h, h->w_keys.as<int32_t>(), h->w_keyoff.as<int64_t>(), nkeys, nullptr, nullptr, (int32_t *)d_out, out_cap, h->w_outoff.as<int64_t>(), s, !d_out);
+        },
+        [&]() {         // the per-key results of the size pass
+            return (!ret_out || nkeys == 0 || hip_ok(hipMemcpyAsync(ret_out, h->w_dret.p, (size_t)nkeys * 4, hipMemcpyDeviceToHost, s), "D2H ret")) &&
+                   (!info_ids_out || nkeys == 0 || hip_ok(hipMemcpyAsync(info_ids_out, h->w_dids.p, (size_t)nkeys * 4, hipMemcpyDeviceToHost, s), "D2H ids"));
+        });
 }
 
 /* reference tokdll:818-911 over FAHyphInterpreter_core_t.h:136-267, as a batch of one on the GPU (bf_w2h.h, bf_kernels_w2h.hip) */
@@ -1983,11 +1960,13 @@ int WordHyphenationWithModel(const char *s, int n, char *out, const int max_out,
     constexpr int64_t full_cap = 8 * W2H_MAX_CHARS + 16;
     uint8_t full[full_cap];
     int64_t out_off[2] = {0, 0};
-    if (upload_docs(h, s, off, 1, st) < 0 || !h->w_out.reserve((size_t)full_cap)) return -1;
-    if (run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, up, h->w_out.as<char>(), full_cap, h->w_outoff.as<int64_t>(), u_hy, st, true) != 0) return -1;
+    Staged in;
+    if (!h->w_outoff.reserve(16) || !h->w_out.reserve((size_t)full_cap) || stage_ragged(in, s, 1, off, 1, h->w_text, h->w_docoff, st) != 0) return -1;
+    if (run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), 1, up, h->w_out.as<char>(), full_cap, h->w_outoff.as<int64_t>(), u_hy, st, true) != 0) { (void)hipStreamSynchronize(st); return -1; }
     int32_t nch = 0;
-    if (!hip_ok(hipMemcpyAsync(out_off, h->w_outoff.p, 16, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(hipMemcpyAsync(&nch, h->w_hnch.p, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-        !hip_ok(hipMemcpyAsync(full, h->w_out.p, (size_t)full_cap, hipMemcpyDeviceToHost, st), "D2H text") || !hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return -1;
+    const bool copied = hip_ok(hipMemcpyAsync(out_off, h->w_outoff.p, 16, hipMemcpyDeviceToHost, st), "D2H") && hip_ok(hipMemcpyAsync(&nch, h->w_hnch.p, 4, hipMemcpyDeviceToHost, st), "D2H") &&
+                        hip_ok(hipMemcpyAsync(full, h->w_out.p, (size_t)full_cap, hipMemcpyDeviceToHost, st), "D2H text");
+    if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize") || !copied) return -1;
     if (nch <= 0 || out_off[1] <= 0 || out_off[1] > full_cap) return -1;       // invalid UTF-8 / nothing decoded (tokdll:846-849)
     return w2h_finish(full, (int)out_off[1], out, max_out);
 }
@@ -2003,22 +1982,12 @@ int64_t WordHyphenationBatch(void *p, const char *text, const int64_t *word_off,
     if (!h->m.w2h_ready) { g_last_error = "WordHyphenation: the model has no usable [w2h] section"; return BF_E_UNSUPPORTED; }
     uint32_t hyb = 0;
     if (w2h_encode(u_hy, &hyb) == 0) return BF_E_ARG;
-    const int64_t total = upload_docs(h, text, word_off, nwords, s);
-    if (total < 0) return total;
-    int rc = run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), nwords, total, nullptr, 0, h->w_outoff.as<int64_t>(), u_hy, s, true);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    std::vector<int64_t> tmp_off; int64_t *dst_off = text_off_out;
-    if (!dst_off) { tmp_off.resize((size_t)nwords + 1); dst_off = tmp_off.data(); }
-    if (!hip_ok(hipMemcpyAsync(dst_off, h->w_outoff.p, (size_t)(nwords + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t nout = dst_off[nwords];
-    if (nout > text_cap) return BF_E_CAPACITY;
-    if (nout > 0) {
-        if (!text_out || !h->w_out.reserve((size_t)nout + 16)) return text_out ? BF_E_DEVICE : BF_E_ARG;
-        rc = run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), nwords, total, h->w_out.as<char>(), nout, h->w_outoff.as<int64_t>(), u_hy, s, false);
-        if (rc != 0) return rc;
-        if (!hip_ok(hipMemcpyAsync(text_out, h->w_out.p, (size_t)nout, hipMemcpyDeviceToHost, s), "D2H text") || !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    }
-    return nout;
+    Staged st;
+    const int rc = stage_ragged(st, text, 1, word_off, nwords, h->w_text, h->w_docoff, s);
+    if (rc != 0) return rc;
+    return two_pass_host(s, nwords, h->w_outoff, h->w_out, 1, text_out, text_cap, text_off_out, [&](void *d_out, int64_t out_cap) {
+        return run_w2h_device(h, h->w_text.as<char>(), h->w_docoff.as<int64_t>(), nwords, st.total, (char *)d_out, out_cap, h->w_outoff.as<int64_t>(), u_hy, s, !d_out);
+    });
 }
 
 int WordHyphenationBatchDevice(void *p, const char *d_text, const int64_t *d_word_off, int64_t nwords, int64_t total_bytes, char *d_text_out, int64_t text_cap,
