@@ -102,6 +102,41 @@ struct PinBuf {
     template <class T> T *as() const { return (T *)p; }
 };
 
+// The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
+// kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
+//   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
+//                            size pass of run_w2h_device and in run_rows_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
+//                            w2t_copy_long_n once more by run_words_device in front of its copy pass
+//   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
+//   flat program [192, 224)  enqueue_flat(), on the stream, behind begin_launch(): no other program reads or writes them
+//   big_need     [224, 232)  run_host, once per attempt and only for BPE models: the chunks of a pipelined host call add up in it
+struct MiscWords {
+    unsigned long long next_doc;         // work counter of the persistent kernels
+    unsigned long long pad0;
+    int status;                          // the batch's status word (Batch::status, BF_STATUS_*; BfLastStatus)
+    int pad1[3];
+    unsigned long long big_used;         // BPE: bytes of the arc pool handed out (k_bpe_seg)
+    unsigned long long long_hdr;         // words modes: cursor of the long-document list (LexLongParams::hdr)
+    unsigned int prep_long_n;            // documents k_prep_wp hands to k_prep_wp_long
+    unsigned int w2t_copy_long_n;        // documents the k_w2t_copy / k_s2t_copy kernels hand to k_w2t_copy_long
+    unsigned int w2t_len_long_n;         // the same of the length kernels
+    unsigned int pad2;
+    unsigned long long stats[16];        // BF_LEX_STATS counters (bf_internal.h BfLexStats)
+    unsigned long long next_range;       // the flat program: work counter of the ranges
+    int unsafe;                          //   "the batch is not fit for the flat program" (k_wp_pre)
+    unsigned int list_n;                 //   documents handed back to the wave program (k_wp_hardlist)
+    unsigned long long pad3[2];
+    unsigned long long big_need;         // BPE: bytes the arc pool lacked (BF_STATUS_POOL)
+    unsigned long long pad4[3];
+};
+constexpr size_t MISC_LAUNCH_BYTES = offsetof(MiscWords, stats), MISC_STATS_BYTES = sizeof(MiscWords::stats), MISC_FLAT_BYTES = offsetof(MiscWords, big_need) - offsetof(MiscWords, next_range);
+static_assert(sizeof(MiscWords) == 256 && MISC_LAUNCH_BYTES == 64 && MISC_STATS_BYTES == 128 && MISC_FLAT_BYTES == 32, "the control block's layout is fixed");
+static_assert(offsetof(MiscWords, next_doc) == 0 && offsetof(MiscWords, status) == 16 && offsetof(MiscWords, big_used) == 32 && offsetof(MiscWords, long_hdr) == 40, "");
+static_assert(offsetof(MiscWords, prep_long_n) == 48 && offsetof(MiscWords, w2t_copy_long_n) == 52 && offsetof(MiscWords, w2t_len_long_n) == 56, "");
+static_assert(offsetof(MiscWords, stats) == 64 && offsetof(MiscWords, next_range) == 192 && offsetof(MiscWords, unsafe) == 200 && offsetof(MiscWords, list_n) == 204, "");
+static_assert(offsetof(MiscWords, big_need) == 224, "");
+
 enum { EV_BEGIN = 0, EV_PREP, EV_TOK, EV_SCAN, EV_COMPACT, EV_DOM0, EV_DOM1, EV_COUNT };      // EV_DOM0 / 1: around the dominant kernel of the step (the one a roofline is about)
 
 // TextToIdsBatch on host buffers, large batches: the batch is cut into chunks that flow through NS slots of page-locked staging
@@ -181,7 +216,7 @@ struct Handle {
     size_t bpe_pool_bytes = (size_t)64 << 20;                    // its size (BfSetBpePoolBytes; the host-buffer calls grow it when a batch needs more)
     DevBuf t_bpe_prio, t_bpe_place;                              // BPE with merges: the arc order as integers (bf_model.h bpe_prio / bpe_place_id)
     // workspaces
-    DevBuf w_cls, w_nchars, w_tmp, w_counts, w_bsums, w_misc, w_flags, w_out, w_outoff;   // w_misc: [0] next_doc (u64), [2] status (int)
+    DevBuf w_cls, w_nchars, w_tmp, w_counts, w_bsums, w_misc, w_flags, w_out, w_outoff;   // w_misc: the control block (MiscWords, misc())
     DevBuf w_text, w_docoff, w_ids, w_idoff, w_starts, w_ends;  // host-API staging
     DevBuf w_srcoff, w_span;                                    // offsets API: source-offset stream, staged id spans
     DevBuf w_preplong, w_w2tlong;                               // k_prep_wp_long / k_w2t_copy_long: the documents of more than 2048 bytes / 1024 tokens
@@ -193,6 +228,7 @@ struct Handle {
     struct OneReq { const char *s; int n; int32_t *ids; int max_ids, unk; int32_t *starts, *ends; int result; std::atomic<int> state; };
     std::mutex q_mu; std::vector<OneReq *> q; bool q_leader = false; std::atomic<int> q_spinners{0}, q_sleepers{0};
     std::atomic<long long> one_rounds{0}, one_reqs{0}, one_ns{0};          // BF_TRACE_ONE=1: launches for single-document calls, requests served, time inside them
+    MiscWords *misc() const { return w_misc.as<MiscWords>(); }
     hipStream_t stream = nullptr;
     hipEvent_t ev[EV_COUNT] = {};
     bool ev_valid = false;
@@ -265,7 +301,7 @@ Handle *util_handle()
     if (hipGetDevice(&u->device) != hipSuccess) u->device = 0;
     bool ok = hip_ok(hipStreamCreateWithFlags(&u->stream, hipStreamNonBlocking), "hipStreamCreate");
     for (auto &e : u->ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate");
-    ok = ok && u->w_misc.reserve(256) && hip_ok(hipMemset(u->w_misc.p, 0, 256), "hipMemset");
+    ok = ok && u->w_misc.reserve(sizeof(MiscWords)) && hip_ok(hipMemset(u->w_misc.p, 0, sizeof(MiscWords)), "hipMemset");
     if (!ok) { fprintf(stderr, "[blingfire_amd] %s\n", g_last_error.c_str()); delete u; return nullptr; }
     h = u;
     return h;
@@ -319,9 +355,27 @@ Handle *make_handle(const uint8_t *img, size_t size)
     if (m.w2h_ready) ok = ok && upload(h->t_w2h, m.w2h.t64, 16) && upload(h->t_w2h_pats, m.w2h_pats, 16) && upload(h->t_w2h_l1, m.w2h_cpmap.l1) && upload(h->t_w2h_pages, m.w2h_cpmap.pages);
     ok = ok && hip_ok(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "hipStreamCreate");
     for (auto &e : h->ev) ok = ok && hip_ok(hipEventCreate(&e), "hipEventCreate");
-    ok = ok && h->w_misc.reserve(256) && hip_ok(hipMemset(h->w_misc.p, 0, 256), "hipMemset");
+    ok = ok && h->w_misc.reserve(sizeof(MiscWords)) && hip_ok(hipMemset(h->w_misc.p, 0, sizeof(MiscWords)), "hipMemset");
     if (!ok) { fprintf(stderr, "[blingfire_amd] %s\n", g_last_error.c_str()); delete h; return nullptr; }
     return h;
+}
+
+// Clears the per-launch words of the control block (MiscWords) on stream s.
+bool clear_launch_words(Handle *h, hipStream_t s) { return hip_ok(hipMemsetAsync(h->misc(), 0, MISC_LAUNCH_BYTES, s), "hipMemsetAsync"); }
+
+// Begins a launch: the per-launch words cleared, and the device status word is the one BfLastStatus reports from here on.  (The two IdsToText
+// calls only clear the words: BfLastStatus keeps answering for the batch before them, as it always did.)
+bool begin_launch(Handle *h, hipStream_t s)
+{
+    if (!clear_launch_words(h, s)) return false;
+    h->small_status = -1;
+    return true;
+}
+
+// the exclusive scan of w_counts[0 .. n) into d_off[0 .. n] (every call's step between counting and writing)
+void scan_counts(Handle *h, int64_t n, int64_t *d_off, hipStream_t s)
+{
+    launch_scan(ScanParams{h->w_counts.as<int32_t>(), n, d_off, h->w_bsums.as<int64_t>(), scan_nblocks(n)}, s);
 }
 
 // the Unigram lane program (bf_seg.h UniLane) keeps `depth` window entries in LDS and packs id + 1 into 20 bits
@@ -395,43 +449,316 @@ LongCaps long_caps(const Handle *h, int64_t ndocs, int64_t total_bytes, int word
     return c;
 }
 
-bool reserve_ids_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off, int words = 0, bool with_long = true)
+// the flat program (bf_flat.h): entries, homes, per-document records, the handed-back list, ranges, word records; the offsets API: their spans
+bool reserve_flat_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off)
 {
-    if (const LongCaps lc = long_caps(h, ndocs, total_bytes, words); with_long && lc.thresh > 0 && !h->w_long.reserve(lc.bytes)) return false;
+    const size_t nranges = (size_t)wp_flat_ranges(ndocs, total_bytes);
+    if (!h->w_ent.reserve((size_t)(total_bytes + 64) * 4) || !h->w_home.reserve((size_t)(total_bytes + 64) * 4) || !h->w_entoff.reserve((size_t)(ndocs + 1) * 8) ||
+        !h->w_entcnt.reserve((size_t)(ndocs + 1) * 4) || !h->w_dstat.reserve((size_t)(ndocs + 1) * 4) || !h->w_list.reserve((size_t)(ndocs + 1) * 4) ||
+        !h->w_ranges.reserve((nranges + 2) * 8) || !h->w_wrec.reserve((size_t)((total_bytes >> WF_REC_SHIFT) + 64) * 16 + (nranges + 2) * 8)) return false;
+    return !want_off || (h->w_espan.reserve((size_t)(total_bytes + 64) * 4) && h->w_hspan.reserve((size_t)(total_bytes + 64) * 8) && h->w_chard.reserve((size_t)(ndocs + 1) * 4));
+}
+
+// the lane-per-document lexer (bf_lex.h): class stream, dirty flags; the offsets API and the words modes: source offsets and spans
+bool reserve_lane_lexer_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off)
+{
+    if (!h->w_cls.reserve((size_t)(total_bytes + 64) * 2) || !h->w_flags.reserve((size_t)((total_bytes >> 10) + 2) * 8)) return false;
+    return !want_off || (h->w_srcoff.reserve((size_t)(total_bytes + 64) * 4) && h->w_span.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 8));
+}
+
+// _sp: element stream and staging by stream elements, then the segmenter's scratch: Unigram records; the BPE wave program + k_bpe_seg; the lane BPE kernels
+bool reserve_sp_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off)
+{
     const Model &m = h->m;
-    const int nblocks = scan_nblocks(ndocs);
-    if (!h->w_nchars.reserve((size_t)(ndocs + 1) * 4) || !h->w_counts.reserve((size_t)(ndocs + 1) * 4) ||
-        !h->w_bsums.reserve((size_t)(nblocks + 1) * 8) || !h->w_tmp.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 4)) return false;
-    if (m.kind == KIND_WP) {
-        if (use_flat(h, want_off, words, ndocs, total_bytes) &&
-            (!h->w_ent.reserve((size_t)(total_bytes + 64) * 4) || !h->w_home.reserve((size_t)(total_bytes + 64) * 4) || !h->w_entoff.reserve((size_t)(ndocs + 1) * 8) ||
-             !h->w_entcnt.reserve((size_t)(ndocs + 1) * 4) || !h->w_dstat.reserve((size_t)(ndocs + 1) * 4) || !h->w_list.reserve((size_t)(ndocs + 1) * 4) ||
-             !h->w_ranges.reserve((size_t)(wp_flat_ranges(ndocs, total_bytes) + 2) * 8) || !h->w_wrec.reserve((size_t)((total_bytes >> WF_REC_SHIFT) + 64) * 16 + (size_t)(wp_flat_ranges(ndocs, total_bytes) + 2) * 8) ||
-             (want_off && (!h->w_espan.reserve((size_t)(total_bytes + 64) * 4) || !h->w_hspan.reserve((size_t)(total_bytes + 64) * 8) || !h->w_chard.reserve((size_t)(ndocs + 1) * 4))))) return false;
-        if (use_wave(h, want_off, words))                              // no class stream, no dirty flags
-            return !want_off || h->w_span.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 8);
-        if (!h->w_cls.reserve((size_t)(total_bytes + 64) * 2) || !h->w_flags.reserve((size_t)((total_bytes >> 10) + 2) * 8)) return false;
-        if (want_off && (!h->w_srcoff.reserve((size_t)(total_bytes + 64) * 4) || !h->w_span.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 8))) return false;
-        return true;
-    }
     const size_t cap = (size_t)(m.dict_has_charmap ? 2 : 1) * (size_t)(total_bytes + ndocs) + 64;      // stream elements over all documents
     if (!h->w_cls.reserve(cap * 2 + 512) || !h->w_tmp.reserve(cap * 4)) return false;      // + the sector buffers of the Unigram lane program read up to two sectors past a document
     if (want_off && (!h->w_srcoff.reserve(cap * 4) || !h->w_span.reserve(cap * 8))) return false;
+    const bool bwave = use_bpe_wave(h, want_off);
     if (m.kind == KIND_UNIGRAM) {
         // one packed 4-byte record per stream element (bf_seg.h uni_rec; 8 bytes reserved); the sequential / flat variants keep 16-byte records
-        const bool lane_form = uni_lane_ok(m);
-        if (!h->w_s1.reserve(cap * (lane_form ? 4 : 16) + 256)) return false;
+        if (!h->w_s1.reserve(cap * (uni_lane_ok(m) ? 4 : 16) + 256)) return false;
+    } else if (bwave) {
+        // six words per stream cell for a word of more than 64 arcs (unit_huge), the arc pool of k_bpe_seg -- not the 96 + 9 bytes per cell of
+        // the lane kernels' arc lists and work arrays (round 6: 111 -> 30 bytes of workspace per stream element)
+        if (!h->w_s1.reserve(cap * 24 + 256) || !h->w_big.reserve(h->bpe_pool_bytes)) return false;
     } else {
         const size_t bm_words = (cap >> 5) + (size_t)ndocs + 4;
-        if (use_bpe_wave(h, want_off)) {
-            // the wave program + k_bpe_seg: six words per stream cell for a word of more than 64 arcs (unit_huge), the arc pool of k_bpe_seg -- not the
-            // 96 + 9 bytes per cell of the lane kernels' arc lists and work arrays (round 6: 111 -> 30 bytes of workspace per stream element)
-            if (!h->w_s1.reserve(cap * 24 + 256) || !h->w_big.reserve(h->bpe_pool_bytes)) return false;
-        } else if (!h->w_s1.reserve((6 * cap + 32 * (size_t)ndocs + 64) * 16) || !h->w_s2.reserve(std::max(cap * 4, 2 * bm_words * 4) + ((size_t)ndocs + 16) * 4) ||
+        if (!h->w_s1.reserve((6 * cap + 32 * (size_t)ndocs + 64) * 16) || !h->w_s2.reserve(std::max(cap * 4, 2 * bm_words * 4) + ((size_t)ndocs + 16) * 4) ||
             !h->w_s3.reserve(cap * 4) || !h->w_s4.reserve(cap) || !h->w_big.reserve(h->bpe_pool_bytes)) return false;
     }
-    if (use_bpe_wave(h, want_off) && !h->w_bwflags.reserve((size_t)(ndocs + 1) * 4)) return false;
+    if (bwave && !h->w_bwflags.reserve((size_t)(ndocs + 1) * 4)) return false;
     return h->w_perm.reserve((size_t)(ndocs + 1) * 4) && h->w_hist.reserve(2048 * 4) && h->w_narcs.reserve((size_t)(ndocs + 1) * 4);
+}
+
+// Every workspace of one launch, by the program the batch will take (the same choice run_device makes).  BfReserve and run_host_chunked rely on
+// "no allocation later": sizes and order are part of that contract.
+bool reserve_ids_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off, int words = 0, bool with_long = true)
+{
+    if (const LongCaps lc = long_caps(h, ndocs, total_bytes, words); with_long && lc.thresh > 0 && !h->w_long.reserve(lc.bytes)) return false;
+    if (!h->w_nchars.reserve((size_t)(ndocs + 1) * 4) || !h->w_counts.reserve((size_t)(ndocs + 1) * 4) ||
+        !h->w_bsums.reserve((size_t)(scan_nblocks(ndocs) + 1) * 8) || !h->w_tmp.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 4)) return false;
+    if (h->m.kind != KIND_WP) return reserve_sp_workspaces(h, ndocs, total_bytes, want_off);
+    if (use_flat(h, want_off, words, ndocs, total_bytes) && !reserve_flat_workspaces(h, ndocs, total_bytes, want_off)) return false;
+    if (use_wave(h, want_off, words)) return !want_off || h->w_span.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 8);      // the wave program: no class stream, no dirty flags
+    return reserve_lane_lexer_workspaces(h, ndocs, total_bytes, want_off);
+}
+
+// ---- one TextToIds / words / sentences launch on a batch resident on the device: run_device validates, reserves, begins the launch and hands
+//      it to the program the batch takes; each program below builds its own parameter blocks, records its own events and launches its kernels
+struct Step {
+    Handle *h; hipStream_t s; Batch b;
+    int32_t *ids_out; int64_t ids_cap; int64_t *id_off; int max_ids, unk;
+    int32_t *starts, *ends; bool want_off;      // the offsets API: both arrays or neither
+    int words;                                  // 0 ids, 1 words, 2 sentences
+    void record(int e) const { (void)hipEventRecord(h->ev[e], s); }
+};
+
+// what a program leaves to the shared tail (finish_step): which kernel moves its staged ids to the caller's array, and how its staging slots are laid out
+struct StepTail {
+    enum Kind { COMPACT, UNI_IDS, BPE_HOME } kind = COMPACT;
+    int slot_mul = 0;                   // CompactParams::slot_mul (0: _wp slots)
+    const int32_t *first = nullptr;     // CompactParams::first
+};
+
+// EV_COMPACT and the launch check: the end of every program
+int end_step(const Step &st)
+{
+    st.record(EV_COMPACT);
+    st.h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "kernel launch") ? 0 : BF_E_DEVICE;
+}
+
+// The parameter blocks of the wave program on the handle's tables and device workspaces.  A caller sets only what differs: the hand-back list and no
+// counters (the flat program); buffers in mapped memory and no work counter (run_host_mapped).
+WpWaveCold wave_cold(const Handle *h, int *status)
+{
+    WpWaveCold c;
+    c.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()};
+    c.kind = h->t_kind.as<uint8_t>(); c.nclasses = h->m.wbd.nclasses; c.status = status; c.no_fast = 0;
+    c.stats = h->lex_stats ? h->misc()->stats : nullptr;
+    return c;
+}
+
+WpWaveParams wave_params(const Handle *h, const Batch &b, int max_ids, int unk, bool want_off)
+{
+    const Model &m = h->m;
+    WpWaveParams wp;
+    wp.T = h->t_wbd.as<uint64_t>(); wp.acts = h->t_acts.as<int32_t>(); wp.acts_n = (int)m.acts_pool.size();
+    wp.initial = m.wbd.initial_base; wp.loop_info = m.loop_info; wp.solo_info = m.wave_solo_info; wp.max_token_length = m.max_token_length;
+    wp.text = b.text; wp.doc_off = b.doc_off; wp.ndocs = b.ndocs; wp.total_bytes = b.total_bytes;
+    wp.ids_tmp = h->w_tmp.as<int32_t>(); wp.counts = h->w_counts.as<int32_t>(); wp.max_ids = max_ids; wp.unk = unk;
+    wp.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr;
+    wp.next_doc = &h->misc()->next_doc;
+    wp.cold = wave_cold(h, b.status);
+    return wp;
+}
+
+// The flat program (bf_flat.h).  It keeps its own tail: its scan sits between k_wp_count and k_wp_merge.
+int enqueue_flat(const Step &st)
+{
+    Handle *h = st.h; const Model &m = h->m; const Batch &b = st.b; hipStream_t s = st.s; MiscWords *misc = h->misc();
+    const int64_t ndocs = b.ndocs, total_bytes = b.total_bytes;
+    if (!hip_ok(hipMemsetAsync(&misc->next_range, 0, MISC_FLAT_BYTES, s), "hipMemsetAsync") || !hip_ok(hipMemsetAsync(h->w_dstat.p, 0, (size_t)ndocs * 4, s), "hipMemsetAsync") ||
+        !hip_ok(hipMemsetAsync(h->w_counts.p, 0, (size_t)ndocs * 4, s), "hipMemsetAsync")) return BF_E_DEVICE;
+    const int nranges = wp_flat_ranges(ndocs, total_bytes);
+    launch_wp_pre(b.doc_off, ndocs, total_bytes, nranges, h->w_ranges.as<int64_t>(), &misc->unsafe, s);
+    st.record(EV_PREP);
+    WfParams fp;
+    fp.T = h->t_wbd.as<uint64_t>(); fp.W = h->t_flat.as<uint64_t>(); fp.wbits = m.flat_bits; fp.m0 = m.flat_m0; fp.m1 = m.flat_m1; fp.m2 = m.flat_m2;
+    fp.ini = m.flat_ini; fp.ini_l = m.flat_ini_l; fp.max_token_length = m.max_token_length; fp.unk = st.unk;
+    fp.text = b.text; fp.doc_off = b.doc_off; fp.ndocs = ndocs; fp.total_bytes = total_bytes;
+    fp.range_doc = h->w_ranges.as<int64_t>(); fp.nranges = nranges; fp.next_range = &misc->next_range; fp.unsafe = &misc->unsafe;
+    fp.ent = h->w_ent.as<uint32_t>(); fp.home = h->w_home.as<int32_t>(); fp.ent_off = h->w_entoff.as<int64_t>(); fp.ent_cnt = h->w_entcnt.as<int32_t>();
+    fp.dstat = h->w_dstat.as<int32_t>(); fp.cold = wave_cold(h, b.status); fp.espan = st.want_off ? h->w_espan.as<uint32_t>() : nullptr;
+    fp.wrec = h->w_wrec.as<uint32_t>(); fp.wrec_cnt = (int32_t *)(h->w_wrec.as<char>() + (size_t)((total_bytes >> WF_REC_SHIFT) + 64) * 16);
+    if (!hip_ok(hipMemsetAsync(fp.wrec_cnt, 0, (size_t)nranges * 8, s), "hipMemsetAsync")) return BF_E_DEVICE;      // (a range without documents writes nothing)
+#ifdef BF_EXPERIMENTS
+    fp.dbg = (h->variant >> 20) & 0xf;
+#endif
+    st.record(EV_DOM0);
+    launch_wp_flat(fp, h->variant, s);
+    st.record(EV_DOM1);
+    // the words the table did not answer: walked by a kernel of their own
+    WfUnitParams up;
+    up.T = fp.T; up.ini = fp.ini; up.ini_l = fp.ini_l; up.max_token_length = fp.max_token_length; up.text = b.text; up.total_bytes = total_bytes;
+    up.wrec = fp.wrec; up.wrec_cnt = fp.wrec_cnt; up.range_doc = fp.range_doc; up.doc_off = b.doc_off; up.nranges = nranges; up.ent = fp.ent; up.home = fp.home;
+    up.extra = h->w_counts.as<int32_t>(); up.espan = fp.espan; up.hspan = st.want_off ? h->w_hspan.as<uint32_t>() : nullptr;
+    up.cpmap = fp.cold.cpmap; up.kind = fp.cold.kind; up.nclasses = fp.cold.nclasses; up.stats = fp.cold.stats;
+    launch_wp_units(up, h->variant, s);
+    st.record(EV_TOK);
+    // the documents it hands back: the wave program, one document at a time
+    launch_wp_hardlist(fp.dstat, &misc->unsafe, ndocs, h->w_list.as<int32_t>(), &misc->list_n, s);
+    WpWaveParams wp = wave_params(h, b, st.max_ids, st.unk, st.want_off);
+    wp.doc_list = h->w_list.as<int32_t>(); wp.list_n = &misc->list_n; wp.cold.stats = nullptr;
+    launch_wp_wave(wp, h->variant & ~0x3f000000, s);
+    WfMergeParams mp;
+    mp.doc_off = b.doc_off; mp.ndocs = ndocs; mp.ent = fp.ent; mp.home = fp.home; mp.ent_off = fp.ent_off; mp.ent_cnt = fp.ent_cnt; mp.dstat = fp.dstat; mp.unsafe = &misc->unsafe;
+    mp.ids_tmp = wp.ids_tmp; mp.counts = wp.counts; mp.id_off = st.id_off; mp.ids_out = st.ids_out; mp.ids_cap = st.ids_cap; mp.status = b.status; mp.max_ids = st.max_ids; mp.unk = st.unk;
+    mp.espan = fp.espan; mp.hspan = up.hspan; mp.starts_out = st.starts; mp.ends_out = st.ends; mp.counts_hard = st.want_off ? h->w_chard.as<int32_t>() : nullptr;
+    launch_wp_count(mp, s);
+    scan_counts(h, ndocs, st.id_off, s);
+    st.record(EV_SCAN);
+    launch_wp_merge(mp, s);
+    if (st.want_off) {
+        // the documents the wave program tokenised: their ids, and the byte offsets from the characters it staged (usually there are none)
+        CompactParams cp{b, wp.ids_tmp, mp.counts_hard, st.id_off, st.ids_out, st.ids_cap, b.status, 0, nullptr, wp.span_tmp, nullptr, st.starts, st.ends, &misc->list_n};
+        launch_compact(cp, s);
+    }
+    return end_step(st);
+}
+
+// The wave program (bf_wave.h): decoding is part of it, so EV_PREP comes first.
+StepTail enqueue_wave(const Step &st)
+{
+    Handle *h = st.h;
+    st.record(EV_PREP);
+    const WpWaveParams wp = wave_params(h, st.b, st.max_ids, st.unk, st.want_off);
+    st.record(EV_DOM0);
+    if (st.b.ndocs > 0) launch_wp_wave(wp, h->variant, st.s);
+    st.record(EV_DOM1);
+    st.record(EV_TOK);
+    return StepTail{};
+}
+
+// The lane-per-document lexer (bf_lex.h) with its long-document form: ids (lexers outside the unit form, variant 2), words and sentences.
+StepTail enqueue_lane_lexer(const Step &st)
+{
+    Handle *h = st.h; const Model &m = h->m; const Batch &b = st.b; hipStream_t s = st.s; MiscWords *misc = h->misc();
+    const int64_t ndocs = b.ndocs, total_bytes = b.total_bytes; const int words = st.words;
+    WpPrepParams pp{b, DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()}, h->t_multi.as<uint16_t>(),
+                    m.wbd_charmap_multi ? 1 : 0, h->w_cls.as<uint16_t>(), st.want_off ? h->w_srcoff.as<int32_t>() : nullptr, h->w_nchars.as<int32_t>()};
+    if (words) { pp.cpmap = DevCpMap{h->t_wcp_l1.as<uint16_t>(), h->t_wcp_pages.as<uint32_t>()}; pp.has_multi = 0; }   // no charmap (tokdll:476-499)
+    // long documents are decoded by sixteen waves each (k_prep_wp_long)
+    pp.long_cap = total_bytes / 2048 + 1;
+    pp.long_list = h->w_preplong.reserve((size_t)pp.long_cap * 8) ? h->w_preplong.as<int64_t>() : nullptr;
+    pp.long_count = &misc->prep_long_n;
+    if (ndocs > 0) launch_prep_wp(pp, total_bytes, h->w_flags.as<unsigned long long>(), s);
+    st.record(EV_PREP);
+    WpLexParams lp;
+    lp.L.T = h->t_wbd.as<uint64_t>(); lp.L.acts = h->t_acts.as<int32_t>();
+    lp.L.initial = m.wbd.initial_base; lp.L.initial_l = m.initial_l; lp.L.cls_any = m.cls_any; lp.L.cls_l = m.cls_l; lp.L.cls_r = m.cls_r;
+    lp.L.max_depth = m.max_depth; lp.L.max_token_length = m.max_token_length; lp.L.max_frames = m.lex_frames;
+    lp.L.loop_state = m.loop_base;
+    lp.L.loop_info = m.loop_info; lp.L.loop_final = m.loop_final ? 1 : 0;
+    lp.L.fn_no_ra = m.fn_no_ra ? 1 : 0;
+    lp.L.two_level = m.two_level ? 1 : 0;
+    lp.b = b; lp.cls = h->w_cls.as<uint16_t>(); lp.nchars = h->w_nchars.as<int32_t>();
+    lp.ids_tmp = h->w_tmp.as<int32_t>(); lp.counts = h->w_counts.as<int32_t>(); lp.span_tmp = st.want_off ? h->w_span.as<int32_t>() : nullptr;
+    lp.max_ids = st.max_ids; lp.unk = st.unk; lp.next_doc = &misc->next_doc; lp.status = b.status; lp.ev_thresh = 0; lp.fetch_thresh = 0; lp.acts_n = (int)m.acts_pool.size(); lp.words = words;
+    lp.table_n = (int)(m.wbd_t2.size() > (size_t)LX_T_CLS_MASK + 1 ? m.wbd_t2.size() - ((size_t)LX_T_CLS_MASK + 1) : 0);
+    lp.stats = h->lex_stats ? misc->stats : nullptr;
+    const LongCaps lc = long_caps(h, ndocs, total_bytes, words);
+    char *lg = h->w_long.as<char>();
+    lp.lg = LexLongParams{lc.thresh, (words && (h->variant & 0x20000000)) ? 3 : 0, lc.docs, lc.chunks, &misc->long_hdr,
+                          (LexLongDoc *)(lg + lc.list_off), (int32_t *)(lg + lc.spec_off), (int32_t *)(lg + lc.jump_off), (int32_t *)(lg + lc.tok2_off), lc.big_cells,
+                          (int32_t *)(lg + lc.jump2_off), (int32_t *)(lg + lc.entry2_off), (int32_t *)(lg + lc.entry_off)};
+    st.record(EV_DOM0);
+    if (ndocs > 0) {
+        launch_lex_long_list(lp, s);
+        launch_lex_wp(lp, words ? (h->variant & ~0x7800F000) : h->variant, s);
+        launch_lex_long(lp, s);
+    }
+    st.record(EV_DOM1);
+    st.record(EV_TOK);
+    return StepTail{};
+}
+
+// _sp, its second half for the models the BPE wave program admits: words that are one vocabulary entry (most are) and short words that are not take
+// the wave program; the documents it hands back (flags: a word of more than 62 elements, a symbol outside the alphabet, ...) one wave each (bf_bpe_seg_body.h)
+StepTail enqueue_bpe_wave(const Step &st, const SpSegParams &sg)
+{
+    Handle *h = st.h; const Model &m = h->m; hipStream_t s = st.s;
+    const int tune = (h->variant >> 8) & 0xf;
+    BpeWaveParams bw;
+    bw.T = sg.S.T; bw.info = sg.S.info; bw.initial = sg.S.initial; bw.cls_delim = sg.S.cls_delim; bw.id_offset = sg.S.id_offset;
+    bw.prio = sg.bpe_prio; bw.place_id = sg.bpe_place_id;
+    if (!m.bpe_tab.empty() && (h->variant & 0x100000) == 0) { bw.W = h->t_bpetab.as<uint64_t>(); bw.wbits = m.bpe_tab_bits; bw.m0 = m.bpe_tab_m0; bw.m1 = m.bpe_tab_m1; bw.m2 = m.bpe_tab_m2; }      // (BfSetVariant bit 20: A/B runs without the word table)
+    bw.stream = sg.stream; bw.lens = sg.lens; bw.doc_off = st.b.doc_off; bw.slot_mul = sg.slot_mul; bw.ndocs = st.b.ndocs;
+    bw.ids_tmp = sg.ids_tmp; bw.counts = sg.counts; bw.flags = h->w_bwflags.as<int32_t>(); bw.max_ids = st.max_ids; bw.next_doc = sg.next_doc; bw.status = st.b.status;
+    bw.scratch = (uint32_t *)sg.arcs; bw.stats = h->lex_stats ? h->misc()->stats : nullptr;
+    st.record(EV_DOM0);
+    launch_bpe_wave(bw, tune, s);
+    st.record(EV_DOM1);
+    launch_bpe_seg_flags(sg, bw.flags, h->w_perm.as<int32_t>(), h->w_hist.as<unsigned int>(), s);
+    return StepTail{bpe_wave_home(tune) ? StepTail::BPE_HOME : StepTail::COMPACT, sg.slot_mul, nullptr};
+}
+
+// The _sp family: Unigram (cut form, lane form) and BPE (the wave program above, the lane kernels).
+StepTail enqueue_sp(const Step &st)
+{
+    Handle *h = st.h; const Model &m = h->m; const Batch &b = st.b; hipStream_t s = st.s; MiscWords *misc = h->misc();
+    const int64_t ndocs = b.ndocs; const bool want_off = st.want_off;
+    const int mul = m.dict_has_charmap ? 2 : 1;
+    const size_t cap = (size_t)mul * (size_t)(b.total_bytes + ndocs) + 64;      // elements over all documents
+    SpPrepParams pp;
+    pp.b = b; pp.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()}; pp.multi_pool = h->t_multi.as<uint16_t>();
+    pp.has_multi = m.sp_has_multi ? 1 : 0; pp.use_bytes = m.use_bytes ? 1 : 0; pp.has_charmap = m.dict_has_charmap ? 1 : 0;
+    pp.delim_code = m.sp_delim_code;
+    pp.prefix_n = m.no_dummy_prefix ? 0 : (int)m.sp_prefix.size();
+    for (int k = 0; k < 10; ++k) pp.prefix[k] = k < pp.prefix_n ? m.sp_prefix[(size_t)k] : 0;
+    pp.old_form = (h->variant & 0x80) ? 1 : 0;
+    pp.waves = (h->variant >> 24) & 0xf;
+    pp.slot_mul = mul; pp.stream = h->w_cls.as<uint16_t>(); pp.lens = h->w_nchars.as<int32_t>(); pp.src_off = want_off ? h->w_srcoff.as<int32_t>() : nullptr;
+    if (ndocs > 0) launch_prep_sp(pp, s);
+    st.record(EV_PREP);
+    SpSegParams sg;
+    sg.S.T = h->t_dict.as<uint64_t>(); sg.S.info = h->t_seginfo.as<SegInfo>(); sg.S.initial = m.dict.initial_base;
+    sg.S.cls_delim = m.sp_delim_code; sg.S.kind = m.kind; sg.S.id_offset = m.id_offset; sg.S.score = m.kind == KIND_UNIGRAM ? h->t_segscore.as<uint32_t>() : nullptr; sg.S.leaf_lo = m.dict.leaf_lo; sg.S.leaf_n = m.dict.leaf_n;
+    sg.b = b; sg.stream = h->w_cls.as<uint16_t>(); sg.lens = h->w_nchars.as<int32_t>(); sg.slot_mul = mul;
+    sg.ids_tmp = h->w_tmp.as<int32_t>(); sg.counts = h->w_counts.as<int32_t>(); sg.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr; sg.max_ids = st.max_ids; sg.unk = st.unk; sg.status = b.status;
+    sg.best = nullptr; sg.arcs = nullptr; sg.tos = nullptr; sg.idsv = nullptr; sg.inter = nullptr; sg.bm_words = 0; sg.fb_list = nullptr; sg.fb_count = nullptr;
+    sg.big_pool = nullptr; sg.big_cap = 0; sg.big_used = &misc->big_used; sg.big_need = &misc->big_need;
+    sg.bpe_prio = nullptr; sg.bpe_place_id = nullptr; sg.bpe_unk_prio = 0; sg.bpe_prio_bits = m.bpe_prio_bits; sg.seg_stats = nullptr;
+    if (m.kind == KIND_UNIGRAM) sg.best = h->w_s1.as<SegBest>();
+    else {
+        sg.bm_words = (int64_t)((cap >> 5) + (size_t)ndocs + 4);         // per bitmap: capacity + 1 bits per document (k_bpe_apply_flat)
+        sg.arcs = h->w_s1.as<SegArc>(); sg.tos = h->w_s2.as<int32_t>(); sg.idsv = h->w_s3.as<int32_t>(); sg.inter = h->w_s4.as<uint8_t>();
+        sg.big_pool = h->w_big.as<uint8_t>(); sg.big_cap = h->w_big.cap;
+        if (m.kind == KIND_BPE_MERGES) { sg.bpe_prio = h->t_bpe_prio.as<uint32_t>(); sg.bpe_place_id = h->t_bpe_place.as<int32_t>(); }
+        sg.bpe_unk_prio = bpe_unk_prio(m, st.unk);
+    }
+    sg.narcs = h->w_narcs.as<int32_t>(); sg.next_doc = &misc->next_doc; sg.trie_depth = m.trie_max_depth; sg.variant = h->variant & 0xff; sg.tune = (h->variant >> 8) & 0xff; sg.tune2 = (h->variant >> 16) & 0xff;
+    sg.lane_ok = uni_lane_ok(m) ? 1 : 0;
+    // ids only: the cut form (bf_seg.h UniCut; BfSetVariant 6: the forward / backward kernels of round 4, which the offsets API still takes)
+    const bool uni_lane = m.kind == KIND_UNIGRAM && sg.lane_ok;
+    sg.uni_cut = (uni_lane && !want_off && (h->variant & 0xff) != 6) ? 1 : 0;
+    h->last_uni_cut = sg.uni_cut != 0;
+    sg.perm = h->w_perm.as<int32_t>(); sg.hist = h->w_hist.as<unsigned int>();
+    // the cut form leaves tokens, not ids (k_uni_ids is its compaction); the lane form writes its ids right-aligned (their first index: w_narcs)
+    StepTail tail{sg.uni_cut ? StepTail::UNI_IDS : StepTail::COMPACT, mul, uni_lane && !sg.uni_cut ? h->w_narcs.as<int32_t>() : nullptr};
+    if (use_bpe_wave(h, want_off) && ndocs > 0) tail = enqueue_bpe_wave(st, sg);
+    else {
+        // (the Unigram lane program records the two events around its forward kernel itself: the sort of the documents comes before it)
+        sg.ev_dom0 = h->ev[EV_DOM0]; sg.ev_dom1 = h->ev[EV_DOM1];
+        if (!uni_lane || ndocs <= 0) st.record(EV_DOM0);
+        if (ndocs > 0) launch_seg_sp(sg, s);
+        if (!uni_lane || ndocs <= 0) st.record(EV_DOM1);
+    }
+    st.record(EV_TOK);
+    return tail;
+}
+
+// The shared tail: scan of the counts, then the program's staged ids (and spans) to their place in the caller's arrays.
+int finish_step(const Step &st, const StepTail &t)
+{
+    Handle *h = st.h; const Model &m = h->m; const Batch &b = st.b; hipStream_t s = st.s;
+    scan_counts(h, b.ndocs, st.id_off, s);
+    st.record(EV_SCAN);
+    if (t.kind == StepTail::UNI_IDS) {
+        // the ids of the cut form's tokens go straight to the caller's array
+        UniIdsParams up{b, h->t_dict.as<uint64_t>(), m.dict.initial_base, h->t_segid.as<int32_t>(), h->w_cls.as<uint16_t>(), h->w_nchars.as<int32_t>(), t.slot_mul,
+                        h->w_tmp.as<int32_t>(), h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, st.unk, m.id_offset, b.status};
+        if (b.ndocs > 0) launch_uni_ids(up, s);
+    } else if (t.kind == StepTail::BPE_HOME) {
+        BpeHomeParams hp{b, h->w_tmp.as<int32_t>(), h->w_nchars.as<int32_t>(), h->w_bwflags.as<int32_t>(), t.slot_mul, h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, st.max_ids, b.status};
+        if (b.ndocs > 0) launch_bpe_home_gather(hp, s);
+    } else if (b.ndocs > 0) {
+        const bool want_off = st.want_off;
+        CompactParams cp{b, h->w_tmp.as<int32_t>(), h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, b.status, t.slot_mul, t.first,
+                         want_off ? h->w_span.as<int32_t>() : nullptr, want_off && !use_wave(h, want_off, st.words) ? h->w_srcoff.as<int32_t>() : nullptr, want_off ? st.starts : nullptr, want_off ? st.ends : nullptr};
+        launch_compact(cp, s);
+    }
+    return end_step(st);
 }
 
 // Enqueue the whole pipeline for a batch resident on the device.
@@ -444,215 +771,14 @@ int run_device(Handle *h, const char *d_text, const int64_t *d_doc_off, int64_t 
     if (words && (h->m.kind != KIND_WP || !want_off)) return BF_E_ARG;
     if (ndocs < 0 || total_bytes < 0 || !d_doc_off || !d_id_off || (ids_cap > 0 && !d_ids_out) || (total_bytes > 0 && !d_text)) return BF_E_ARG;
     if (max_ids < 0) max_ids = 0;
-    Model &m = h->m;
-    const int nblocks = scan_nblocks(ndocs);
     if (!reserve_ids_workspaces(h, ndocs, total_bytes, want_off, words)) return BF_E_DEVICE;
-    int slot_mul = 0; const int32_t *first = nullptr; bool uni_cut_keys = false, bpe_home = false;
-    unsigned long long *next_doc = h->w_misc.as<unsigned long long>();
-    int *status = (int *)(h->w_misc.as<char>() + 16);
-    Batch b{(const uint8_t *)d_text, d_doc_off, ndocs, total_bytes, status};
-    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
-    h->small_status = -1;
-    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    const Step st{h, s, Batch{(const uint8_t *)d_text, d_doc_off, ndocs, total_bytes, &h->misc()->status},
+                  d_ids_out, ids_cap, d_id_off, max_ids, unk, d_starts, d_ends, want_off, words};
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    st.record(EV_BEGIN);
     h->last_flat = use_flat(h, want_off, words, ndocs, total_bytes);
-    if (h->last_flat) {
-        // w_misc: [192] work counter of the ranges, [200] "the batch is not fit for the flat program", [204] documents handed back
-        char *misc = h->w_misc.as<char>();
-        if (!hip_ok(hipMemsetAsync(misc + 192, 0, 32, s), "hipMemsetAsync") || !hip_ok(hipMemsetAsync(h->w_dstat.p, 0, (size_t)ndocs * 4, s), "hipMemsetAsync") ||
-            !hip_ok(hipMemsetAsync(h->w_counts.p, 0, (size_t)ndocs * 4, s), "hipMemsetAsync")) return BF_E_DEVICE;
-        int *unsafe = (int *)(misc + 200); unsigned int *list_n = (unsigned int *)(misc + 204);
-        const int nranges = wp_flat_ranges(ndocs, total_bytes);
-        launch_wp_pre(d_doc_off, ndocs, total_bytes, nranges, h->w_ranges.as<int64_t>(), unsafe, s);
-        (void)hipEventRecord(h->ev[EV_PREP], s);
-        WpWaveCold cold;
-        cold.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()};
-        cold.kind = h->t_kind.as<uint8_t>(); cold.nclasses = m.wbd.nclasses; cold.status = status; cold.no_fast = 0;
-        cold.stats = h->lex_stats ? (unsigned long long *)(misc + 64) : nullptr;
-        WfParams fp;
-        fp.T = h->t_wbd.as<uint64_t>(); fp.W = h->t_flat.as<uint64_t>(); fp.wbits = m.flat_bits; fp.m0 = m.flat_m0; fp.m1 = m.flat_m1; fp.m2 = m.flat_m2;
-        fp.ini = m.flat_ini; fp.ini_l = m.flat_ini_l; fp.max_token_length = m.max_token_length; fp.unk = unk;
-        fp.text = b.text; fp.doc_off = b.doc_off; fp.ndocs = ndocs; fp.total_bytes = total_bytes;
-        fp.range_doc = h->w_ranges.as<int64_t>(); fp.nranges = nranges; fp.next_range = (unsigned long long *)(misc + 192); fp.unsafe = unsafe;
-        fp.ent = h->w_ent.as<uint32_t>(); fp.home = h->w_home.as<int32_t>(); fp.ent_off = h->w_entoff.as<int64_t>(); fp.ent_cnt = h->w_entcnt.as<int32_t>();
-        fp.dstat = h->w_dstat.as<int32_t>(); fp.cold = cold; fp.espan = want_off ? h->w_espan.as<uint32_t>() : nullptr;
-        fp.wrec = h->w_wrec.as<uint32_t>(); fp.wrec_cnt = (int32_t *)(h->w_wrec.as<char>() + (size_t)((total_bytes >> WF_REC_SHIFT) + 64) * 16);
-        if (!hip_ok(hipMemsetAsync(fp.wrec_cnt, 0, (size_t)nranges * 8, s), "hipMemsetAsync")) return BF_E_DEVICE;      // (a range without documents writes nothing)
-#ifdef BF_EXPERIMENTS
-        fp.dbg = (h->variant >> 20) & 0xf;
-#endif
-        (void)hipEventRecord(h->ev[EV_DOM0], s);
-        launch_wp_flat(fp, h->variant, s);
-        (void)hipEventRecord(h->ev[EV_DOM1], s);
-        // the words the table did not answer: walked by a kernel of their own
-        WfUnitParams up;
-        up.T = fp.T; up.ini = fp.ini; up.ini_l = fp.ini_l; up.max_token_length = fp.max_token_length; up.text = b.text; up.total_bytes = total_bytes;
-        up.wrec = fp.wrec; up.wrec_cnt = fp.wrec_cnt; up.range_doc = fp.range_doc; up.doc_off = b.doc_off; up.nranges = nranges; up.ent = fp.ent; up.home = fp.home; up.extra = h->w_counts.as<int32_t>(); up.espan = fp.espan; up.hspan = want_off ? h->w_hspan.as<uint32_t>() : nullptr; up.cpmap = cold.cpmap; up.kind = cold.kind; up.nclasses = cold.nclasses; up.stats = cold.stats;
-        launch_wp_units(up, h->variant, s);
-        (void)hipEventRecord(h->ev[EV_TOK], s);
-        // the documents it hands back: the wave program, one document at a time
-        launch_wp_hardlist(fp.dstat, unsafe, ndocs, h->w_list.as<int32_t>(), list_n, s);
-        WpWaveParams wp;
-        wp.T = fp.T; wp.acts = h->t_acts.as<int32_t>(); wp.acts_n = (int)m.acts_pool.size();
-        wp.initial = m.wbd.initial_base; wp.loop_info = m.loop_info; wp.solo_info = m.wave_solo_info; wp.max_token_length = m.max_token_length;
-        wp.text = b.text; wp.doc_off = b.doc_off; wp.ndocs = ndocs; wp.total_bytes = total_bytes;
-        wp.ids_tmp = h->w_tmp.as<int32_t>(); wp.counts = h->w_counts.as<int32_t>(); wp.max_ids = max_ids; wp.unk = unk; wp.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr;
-        wp.next_doc = next_doc; wp.doc_list = h->w_list.as<int32_t>(); wp.list_n = list_n;
-        wp.cold = cold; wp.cold.stats = nullptr;
-        launch_wp_wave(wp, h->variant & ~0x3f000000, s);
-        WfMergeParams mp;
-        mp.doc_off = b.doc_off; mp.ndocs = ndocs; mp.ent = fp.ent; mp.home = fp.home; mp.ent_off = fp.ent_off; mp.ent_cnt = fp.ent_cnt; mp.dstat = fp.dstat; mp.unsafe = unsafe;
-        mp.ids_tmp = wp.ids_tmp; mp.counts = wp.counts; mp.id_off = d_id_off; mp.ids_out = d_ids_out; mp.ids_cap = ids_cap; mp.status = status; mp.max_ids = max_ids; mp.unk = unk;
-        mp.espan = fp.espan; mp.hspan = up.hspan; mp.starts_out = d_starts; mp.ends_out = d_ends; mp.counts_hard = want_off ? h->w_chard.as<int32_t>() : nullptr;
-        launch_wp_count(mp, s);
-        ScanParams sp{h->w_counts.as<int32_t>(), ndocs, d_id_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
-        (void)hipEventRecord(h->ev[EV_SCAN], s);
-        launch_wp_merge(mp, s);
-        if (want_off) {
-            // the documents the wave program tokenised: their ids, and the byte offsets from the characters it staged (usually there are none)
-            CompactParams cp{b, wp.ids_tmp, mp.counts_hard, d_id_off, d_ids_out, ids_cap, status, 0, nullptr, wp.span_tmp, nullptr, d_starts, d_ends, list_n};
-            launch_compact(cp, s);
-        }
-        (void)hipEventRecord(h->ev[EV_COMPACT], s);
-        h->ev_valid = true;
-        if (!hip_ok(hipGetLastError(), "kernel launch")) return BF_E_DEVICE;
-        return 0;
-    }
-    if (use_wave(h, want_off, words)) {
-        (void)hipEventRecord(h->ev[EV_PREP], s);                       // decoding is part of the wave program
-        WpWaveParams wp;
-        wp.T = h->t_wbd.as<uint64_t>(); wp.acts = h->t_acts.as<int32_t>(); wp.acts_n = (int)m.acts_pool.size();
-        wp.initial = m.wbd.initial_base; wp.loop_info = m.loop_info; wp.solo_info = m.wave_solo_info; wp.max_token_length = m.max_token_length;
-        wp.text = b.text; wp.doc_off = b.doc_off; wp.ndocs = b.ndocs; wp.total_bytes = b.total_bytes;
-        wp.ids_tmp = h->w_tmp.as<int32_t>(); wp.counts = h->w_counts.as<int32_t>(); wp.max_ids = max_ids; wp.unk = unk;
-        wp.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr;
-        wp.next_doc = next_doc;
-        wp.cold.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()};
-        wp.cold.kind = h->t_kind.as<uint8_t>(); wp.cold.nclasses = m.wbd.nclasses; wp.cold.status = status; wp.cold.no_fast = 0;
-        wp.cold.stats = h->lex_stats ? (unsigned long long *)(h->w_misc.as<char>() + 64) : nullptr;
-        (void)hipEventRecord(h->ev[EV_DOM0], s);
-        if (ndocs > 0) launch_wp_wave(wp, h->variant, s);
-        (void)hipEventRecord(h->ev[EV_DOM1], s);
-        (void)hipEventRecord(h->ev[EV_TOK], s);
-    } else if (m.kind == KIND_WP) {
-        WpPrepParams pp{b, DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()}, h->t_multi.as<uint16_t>(),
-                        m.wbd_charmap_multi ? 1 : 0, h->w_cls.as<uint16_t>(), want_off ? h->w_srcoff.as<int32_t>() : nullptr, h->w_nchars.as<int32_t>()};
-        if (words) { pp.cpmap = DevCpMap{h->t_wcp_l1.as<uint16_t>(), h->t_wcp_pages.as<uint32_t>()}; pp.has_multi = 0; }   // no charmap (tokdll:476-499)
-        // long documents are decoded by sixteen waves each (k_prep_wp_long); w_misc + 48: their number, zeroed with the status word above
-        pp.long_cap = total_bytes / 2048 + 1;
-        pp.long_list = h->w_preplong.reserve((size_t)pp.long_cap * 8) ? h->w_preplong.as<int64_t>() : nullptr;
-        pp.long_count = (unsigned int *)(h->w_misc.as<char>() + 48);
-        if (ndocs > 0) launch_prep_wp(pp, total_bytes, h->w_flags.as<unsigned long long>(), s);
-        (void)hipEventRecord(h->ev[EV_PREP], s);
-        WpLexParams lp;
-        lp.L.T = h->t_wbd.as<uint64_t>(); lp.L.acts = h->t_acts.as<int32_t>();
-        lp.L.initial = m.wbd.initial_base; lp.L.initial_l = m.initial_l; lp.L.cls_any = m.cls_any; lp.L.cls_l = m.cls_l; lp.L.cls_r = m.cls_r;
-        lp.L.max_depth = m.max_depth; lp.L.max_token_length = m.max_token_length; lp.L.max_frames = m.lex_frames;
-        lp.L.loop_state = m.loop_base;
-        lp.L.loop_info = m.loop_info; lp.L.loop_final = m.loop_final ? 1 : 0;
-        lp.L.fn_no_ra = m.fn_no_ra ? 1 : 0;
-        lp.L.two_level = m.two_level ? 1 : 0;
-        lp.b = b; lp.cls = h->w_cls.as<uint16_t>(); lp.nchars = h->w_nchars.as<int32_t>();
-        lp.ids_tmp = h->w_tmp.as<int32_t>(); lp.counts = h->w_counts.as<int32_t>(); lp.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr;
-        lp.max_ids = max_ids; lp.unk = unk; lp.next_doc = next_doc; lp.status = status; lp.ev_thresh = 0; lp.fetch_thresh = 0; lp.acts_n = (int)m.acts_pool.size(); lp.words = words;
-        lp.table_n = (int)(m.wbd_t2.size() > (size_t)LX_T_CLS_MASK + 1 ? m.wbd_t2.size() - ((size_t)LX_T_CLS_MASK + 1) : 0);
-        lp.stats = h->lex_stats ? (unsigned long long *)(h->w_misc.as<char>() + 64) : nullptr;
-        const LongCaps lc = long_caps(h, ndocs, total_bytes, words);
-        lp.lg = LexLongParams{lc.thresh, (words && (h->variant & 0x20000000)) ? 3 : 0, lc.docs, lc.chunks, (unsigned long long *)(h->w_misc.as<char>() + 40) /* zeroed with the status word above */,
-                              (LexLongDoc *)(h->w_long.as<char>() + lc.list_off), (int32_t *)(h->w_long.as<char>() + lc.spec_off), (int32_t *)(h->w_long.as<char>() + lc.jump_off),
-                              (int32_t *)(h->w_long.as<char>() + lc.tok2_off), lc.big_cells, (int32_t *)(h->w_long.as<char>() + lc.jump2_off),
-                              (int32_t *)(h->w_long.as<char>() + lc.entry2_off), (int32_t *)(h->w_long.as<char>() + lc.entry_off)};
-        (void)hipEventRecord(h->ev[EV_DOM0], s);
-        if (ndocs > 0) {
-            launch_lex_long_list(lp, s);
-            launch_lex_wp(lp, words ? (h->variant & ~0x7800F000) : h->variant, s);
-            launch_lex_long(lp, s);
-        }
-        (void)hipEventRecord(h->ev[EV_DOM1], s);
-        (void)hipEventRecord(h->ev[EV_TOK], s);
-    } else {
-        const int mul = m.dict_has_charmap ? 2 : 1;
-        slot_mul = mul;
-        const size_t cap = (size_t)mul * (size_t)(total_bytes + ndocs) + 64;      // elements over all documents
-        SpPrepParams pp;
-        pp.b = b; pp.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()}; pp.multi_pool = h->t_multi.as<uint16_t>();
-        pp.has_multi = m.sp_has_multi ? 1 : 0; pp.use_bytes = m.use_bytes ? 1 : 0; pp.has_charmap = m.dict_has_charmap ? 1 : 0;
-        pp.delim_code = m.sp_delim_code;
-        pp.prefix_n = m.no_dummy_prefix ? 0 : (int)m.sp_prefix.size();
-        for (int k = 0; k < 10; ++k) pp.prefix[k] = k < pp.prefix_n ? m.sp_prefix[(size_t)k] : 0;
-        pp.old_form = (h->variant & 0x80) ? 1 : 0;
-        pp.waves = (h->variant >> 24) & 0xf;
-        pp.slot_mul = mul; pp.stream = h->w_cls.as<uint16_t>(); pp.lens = h->w_nchars.as<int32_t>(); pp.src_off = want_off ? h->w_srcoff.as<int32_t>() : nullptr;
-        if (ndocs > 0) launch_prep_sp(pp, s);
-        (void)hipEventRecord(h->ev[EV_PREP], s);
-        SpSegParams sg;
-        sg.S.T = h->t_dict.as<uint64_t>(); sg.S.info = h->t_seginfo.as<SegInfo>(); sg.S.initial = m.dict.initial_base;
-        sg.S.cls_delim = m.sp_delim_code; sg.S.kind = m.kind; sg.S.id_offset = m.id_offset; sg.S.score = m.kind == KIND_UNIGRAM ? h->t_segscore.as<uint32_t>() : nullptr; sg.S.leaf_lo = m.dict.leaf_lo; sg.S.leaf_n = m.dict.leaf_n;
-        sg.b = b; sg.stream = h->w_cls.as<uint16_t>(); sg.lens = h->w_nchars.as<int32_t>(); sg.slot_mul = mul;
-        sg.ids_tmp = h->w_tmp.as<int32_t>(); sg.counts = h->w_counts.as<int32_t>(); sg.span_tmp = want_off ? h->w_span.as<int32_t>() : nullptr; sg.max_ids = max_ids; sg.unk = unk; sg.status = status;
-        sg.best = nullptr; sg.arcs = nullptr; sg.tos = nullptr; sg.idsv = nullptr; sg.inter = nullptr; sg.bm_words = 0; sg.fb_list = nullptr; sg.fb_count = nullptr;
-        sg.big_pool = nullptr; sg.big_cap = 0; sg.big_used = (unsigned long long *)(h->w_misc.as<char>() + 32);     // zeroed with the status word above
-        sg.big_need = (unsigned long long *)(h->w_misc.as<char>() + 224);      // (not among the words a launch clears: the chunks of a pipelined host call add up in it, run_host clears it)
-        sg.bpe_prio = nullptr; sg.bpe_place_id = nullptr; sg.bpe_unk_prio = 0; sg.bpe_prio_bits = m.bpe_prio_bits; sg.seg_stats = nullptr;
-        if (m.kind == KIND_UNIGRAM) sg.best = h->w_s1.as<SegBest>();
-        else {
-            const size_t bm_words = (cap >> 5) + (size_t)ndocs + 4;         // per bitmap: capacity + 1 bits per document (k_bpe_apply_flat)
-            sg.bm_words = (int64_t)bm_words;
-            sg.arcs = h->w_s1.as<SegArc>(); sg.tos = h->w_s2.as<int32_t>(); sg.idsv = h->w_s3.as<int32_t>(); sg.inter = h->w_s4.as<uint8_t>();
-            sg.big_pool = h->w_big.as<uint8_t>(); sg.big_cap = h->w_big.cap;
-            if (m.kind == KIND_BPE_MERGES) { sg.bpe_prio = h->t_bpe_prio.as<uint32_t>(); sg.bpe_place_id = h->t_bpe_place.as<int32_t>(); }
-            sg.bpe_unk_prio = bpe_unk_prio(m, unk);
-        }
-        sg.narcs = h->w_narcs.as<int32_t>(); sg.next_doc = next_doc; sg.trie_depth = m.trie_max_depth; sg.variant = h->variant & 0xff; sg.tune = (h->variant >> 8) & 0xff; sg.tune2 = (h->variant >> 16) & 0xff;
-        sg.lane_ok = uni_lane_ok(m) ? 1 : 0;
-        // ids only: the cut form (bf_seg.h UniCut; BfSetVariant 6: the forward / backward kernels of round 4, which the offsets API still takes)
-        sg.uni_cut = (m.kind == KIND_UNIGRAM && sg.lane_ok && !want_off && (h->variant & 0xff) != 6) ? 1 : 0;
-        if (m.kind == KIND_UNIGRAM && sg.lane_ok && !sg.uni_cut) first = h->w_narcs.as<int32_t>();
-        uni_cut_keys = sg.uni_cut != 0;
-        h->last_uni_cut = uni_cut_keys;
-        sg.perm = h->w_perm.as<int32_t>(); sg.hist = h->w_hist.as<unsigned int>();
-        const bool bwave = use_bpe_wave(h, want_off);
-        if (bwave && ndocs > 0) {
-            // words that are one vocabulary entry (most are) and short words that are not: the wave program; the documents it hands back
-            // (flags: a word of more than 62 elements, a symbol outside the alphabet, ...): one wave per document (bf_bpe_seg_body.h)
-            BpeWaveParams bw;
-            bw.T = sg.S.T; bw.info = sg.S.info; bw.initial = sg.S.initial; bw.cls_delim = sg.S.cls_delim; bw.id_offset = sg.S.id_offset;
-            bw.prio = sg.bpe_prio; bw.place_id = sg.bpe_place_id;
-            if (!m.bpe_tab.empty() && (h->variant & 0x100000) == 0) { bw.W = h->t_bpetab.as<uint64_t>(); bw.wbits = m.bpe_tab_bits; bw.m0 = m.bpe_tab_m0; bw.m1 = m.bpe_tab_m1; bw.m2 = m.bpe_tab_m2; }      // (BfSetVariant bit 20: A/B runs without the word table)
-            bw.stream = sg.stream; bw.lens = sg.lens; bw.doc_off = b.doc_off; bw.slot_mul = mul; bw.ndocs = ndocs;
-            bw.ids_tmp = sg.ids_tmp; bw.counts = sg.counts; bw.flags = h->w_bwflags.as<int32_t>(); bw.max_ids = max_ids; bw.next_doc = next_doc; bw.status = status; bw.scratch = (uint32_t *)sg.arcs; bw.stats = h->lex_stats ? (unsigned long long *)(h->w_misc.as<char>() + 64) : nullptr;
-            (void)hipEventRecord(h->ev[EV_DOM0], s);
-            launch_bpe_wave(bw, (h->variant >> 8) & 0xf, s);
-            (void)hipEventRecord(h->ev[EV_DOM1], s);
-            launch_bpe_seg_flags(sg, bw.flags, h->w_perm.as<int32_t>(), h->w_hist.as<unsigned int>(), s);
-            bpe_home = bpe_wave_home((h->variant >> 8) & 0xf);
-        } else {
-            // (the Unigram lane program records the two events around its forward kernel itself: the sort of the documents comes before it)
-            sg.ev_dom0 = h->ev[EV_DOM0]; sg.ev_dom1 = h->ev[EV_DOM1];
-            if (m.kind != KIND_UNIGRAM || !sg.lane_ok || ndocs <= 0) (void)hipEventRecord(h->ev[EV_DOM0], s);
-            if (ndocs > 0) launch_seg_sp(sg, s);
-            if (m.kind != KIND_UNIGRAM || !sg.lane_ok || ndocs <= 0) (void)hipEventRecord(h->ev[EV_DOM1], s);
-        }
-        (void)hipEventRecord(h->ev[EV_TOK], s);
-    }
-    ScanParams sp{h->w_counts.as<int32_t>(), ndocs, d_id_off, h->w_bsums.as<int64_t>(), nblocks};
-    launch_scan(sp, s);
-    (void)hipEventRecord(h->ev[EV_SCAN], s);
-    CompactParams cp{b, h->w_tmp.as<int32_t>(), h->w_counts.as<int32_t>(), d_id_off, d_ids_out, ids_cap, status, slot_mul, first,
-                     want_off ? h->w_span.as<int32_t>() : nullptr, want_off && !use_wave(h, want_off, words) ? h->w_srcoff.as<int32_t>() : nullptr, want_off ? d_starts : nullptr, want_off ? d_ends : nullptr};
-    if (uni_cut_keys) {
-        // the cut form left tokens, not ids: their ids go straight to the caller's array (k_uni_ids is the compaction of this path)
-        UniIdsParams up{b, h->t_dict.as<uint64_t>(), m.dict.initial_base, h->t_segid.as<int32_t>(), h->w_cls.as<uint16_t>(), h->w_nchars.as<int32_t>(), slot_mul,
-                        h->w_tmp.as<int32_t>(), h->w_counts.as<int32_t>(), d_id_off, d_ids_out, ids_cap, unk, m.id_offset, status};
-        if (ndocs > 0) launch_uni_ids(up, s);
-    } else if (bpe_home) {
-        BpeHomeParams hp{b, h->w_tmp.as<int32_t>(), h->w_nchars.as<int32_t>(), h->w_bwflags.as<int32_t>(), slot_mul, h->w_counts.as<int32_t>(), d_id_off, d_ids_out, ids_cap, max_ids, status};
-        if (ndocs > 0) launch_bpe_home_gather(hp, s);
-    } else if (ndocs > 0) launch_compact(cp, s);
-    (void)hipEventRecord(h->ev[EV_COMPACT], s);
-    h->ev_valid = true;
-    if (!hip_ok(hipGetLastError(), "kernel launch")) return BF_E_DEVICE;
-    return 0;
+    if (h->last_flat) return enqueue_flat(st);
+    return finish_step(st, use_wave(h, want_off, words) ? enqueue_wave(st) : h->m.kind == KIND_WP ? enqueue_lane_lexer(st) : enqueue_sp(st));
 }
 
 // memcpy with a few threads: one core moves ~10 GB/s, PCIe wants ~50
@@ -672,6 +798,13 @@ void par_memcpy(void *dst, const void *src, size_t n)
     }
     memcpy(dst, src, part < n ? part : n);
     for (auto &x : th) x.join();
+}
+
+// worst-case id count of a batch: _wp ids cover >= 1 byte each; _sp tokens cover >= 1 element of <= mul * (n + 1) elements; max_ids >= 0 caps every document
+int64_t worst_ids(const Model &m, int64_t bytes, int64_t ndocs, int max_ids)
+{
+    const int64_t w = m.kind == KIND_WP ? bytes : (int64_t)(m.dict_has_charmap ? 2 : 1) * (bytes + ndocs);
+    return max_ids >= 0 && ndocs * (int64_t)max_ids < w ? ndocs * (int64_t)max_ids : w;
 }
 
 constexpr int64_t BF_RETRY_POOL = INT64_MIN + 1;            // internal: a BPE document did not fit the arc pool (BF_STATUS_POOL); the need is in w_misc
@@ -704,13 +837,8 @@ int64_t run_host_chunked(Handle *h, const char *text, const int64_t *doc_off, in
         max_bytes = std::max(max_bytes, doc_off[e] - doc_off[d]); max_docs = std::max(max_docs, e - d);
         d = e;
     }
-    auto worst_ids = [&](int64_t bytes, int64_t nd) {
-        int64_t w = h->m.kind == KIND_WP ? bytes : (int64_t)(h->m.dict_has_charmap ? 2 : 1) * (bytes + nd);
-        if (max_ids >= 0 && nd * (int64_t)max_ids < w) w = nd * (int64_t)(max_ids < 0 ? 0 : max_ids);
-        return w;
-    };
     int64_t max_worst = 0;
-    for (const Chunk &c : chunks) max_worst = std::max(max_worst, worst_ids(doc_off[c.d1] - doc_off[c.d0], c.d1 - c.d0));
+    for (const Chunk &c : chunks) max_worst = std::max(max_worst, worst_ids(h->m, doc_off[c.d1] - doc_off[c.d0], c.d1 - c.d0, max_ids));
     for (int i = 0; i < NS; ++i)
         if (!P.pin_text[i].reserve((size_t)max_bytes + 16) || !P.pin_off[i].reserve((size_t)(max_docs + 1) * 8) || !P.pin_idoff[i].reserve((size_t)(max_docs + 1) * 8) ||
             !P.dev_text[i].reserve((size_t)max_bytes + 16) || !P.dev_off[i].reserve((size_t)(max_docs + 1) * 8) || !P.dev_idoff[i].reserve((size_t)(max_docs + 1) * 8) ||
@@ -805,10 +933,10 @@ int64_t run_host_chunked(Handle *h, const char *text, const int64_t *doc_off, in
                 if (meta_fail) { lk.unlock(); return fail2(rc_err ? rc_err : BF_E_DEVICE); }
             }
             if (k >= NS && !hip_ok(hipStreamWaitEvent(s, P.ev_d2h[sl], 0), "hipStreamWaitEvent")) return fail2(BF_E_DEVICE);        // the ids of chunk k-NS have left dev_ids[sl]
-            const int rc = run_device(h, P.dev_text[sl].as<char>(), P.dev_off[sl].as<int64_t>(), nd, bytes, P.dev_ids[sl].as<int32_t>(), worst_ids(bytes, nd),
+            const int rc = run_device(h, P.dev_text[sl].as<char>(), P.dev_off[sl].as<int64_t>(), nd, bytes, P.dev_ids[sl].as<int32_t>(), worst_ids(h->m, bytes, nd, max_ids),
                                       P.dev_idoff[sl].as<int64_t>(), max_ids, unk, s);
             if (rc != 0) return fail2(rc);
-            if (!hip_ok(hipMemcpyAsync(P.pin_status.as<int>() + sl, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost, s), "D2H status") ||
+            if (!hip_ok(hipMemcpyAsync(P.pin_status.as<int>() + sl, &h->misc()->status, 4, hipMemcpyDeviceToHost, s), "D2H status") ||
                 !hip_ok(hipEventRecord(P.ev_cmp[sl], s), "hipEventRecord")) return fail2(BF_E_DEVICE);
             t_enq += now() - t0e;
             { std::lock_guard<std::mutex> lk(wmu); enq = k + 1; }
@@ -848,7 +976,6 @@ bool small_ready(Handle *h)
 // caller holds h->mu and has made h->device current; the batch fits SmallLayout.  Returns the id count or BF_E_*.
 int64_t run_host_mapped(Handle *h, const char *text, const int64_t *doc_off, int64_t ndocs, int32_t *ids_out, int64_t ids_cap, int64_t *id_off_out, int max_ids, int unk)
 {
-    const Model &m = h->m;
     char *hp = h->m_small.as<char>(), *dp = (char *)h->m_small_dev;
     const int64_t base = doc_off[0], total = doc_off[ndocs] - base;
     h->last_flat = false;                                          // (the wave program: what BfTokeniseKernel / BfStepKernels report)
@@ -856,15 +983,12 @@ int64_t run_host_mapped(Handle *h, const char *text, const int64_t *doc_off, int
     int64_t *off = (int64_t *)(hp + SmallLayout::off);
     for (int64_t i = 0; i <= ndocs; ++i) off[i] = doc_off[i] - base;
     if (total > 0) memcpy(hp + SmallLayout::text, text + base, (size_t)total);
-    WpWaveParams wp;
-    wp.T = h->t_wbd.as<uint64_t>(); wp.acts = h->t_acts.as<int32_t>(); wp.acts_n = (int)m.acts_pool.size();
-    wp.initial = m.wbd.initial_base; wp.loop_info = m.loop_info; wp.solo_info = m.wave_solo_info; wp.max_token_length = m.max_token_length;
-    wp.text = (const uint8_t *)(dp + SmallLayout::text); wp.doc_off = (const int64_t *)(dp + SmallLayout::off); wp.ndocs = ndocs; wp.total_bytes = total;
-    wp.ids_tmp = (int32_t *)(dp + SmallLayout::ids); wp.counts = (int32_t *)(dp + SmallLayout::counts); wp.max_ids = max_ids < 0 ? 0 : max_ids; wp.unk = unk;
-    wp.span_tmp = nullptr;
+    // the wave program on the block: text, offsets, counts, id staging and the status word in mapped memory
+    WpWaveParams wp = wave_params(h, Batch{(const uint8_t *)(dp + SmallLayout::text), (const int64_t *)(dp + SmallLayout::off), ndocs, total, (int *)(dp + SmallLayout::ctrl + 16)},
+                                  max_ids < 0 ? 0 : max_ids, unk, false);
+    wp.ids_tmp = (int32_t *)(dp + SmallLayout::ids); wp.counts = (int32_t *)(dp + SmallLayout::counts);
     wp.next_doc = nullptr;              // no work counter: an atomic on host memory costs every wave a trip over the bus
-    wp.cold.cpmap = DevCpMap{h->t_cp_l1.as<uint16_t>(), h->t_cp_pages.as<uint32_t>()};
-    wp.cold.kind = h->t_kind.as<uint8_t>(); wp.cold.nclasses = m.wbd.nclasses; wp.cold.status = (int *)(dp + SmallLayout::ctrl + 16); wp.cold.no_fast = 0; wp.cold.stats = nullptr;
+    wp.cold.stats = nullptr;
     launch_wp_wave(wp, h->variant, h->stream);
     h->ev_valid = false;
     if (!hip_ok(hipGetLastError(), "kernel launch") || !hip_ok(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) return BF_E_DEVICE;
@@ -905,12 +1029,12 @@ int64_t run_host(Handle *h, const char *text, const int64_t *doc_off, int64_t nd
     // std::vector, ..._bpe_t.h:143-144)
     for (int attempt = 0; attempt < 8; ++attempt) {
         const bool is_bpe = h->m.kind == KIND_BPE || h->m.kind == KIND_BPE_OPT || h->m.kind == KIND_BPE_MERGES;
-        if (is_bpe && !hip_ok(hipMemset(h->w_misc.as<char>() + 224, 0, 8), "hipMemset")) return BF_E_DEVICE;      // bytes the pool lacked, over all launches of this attempt
+        if (is_bpe && !hip_ok(hipMemset(&h->misc()->big_need, 0, 8), "hipMemset")) return BF_E_DEVICE;      // bytes the pool lacked, over all launches of this attempt
         const int64_t r = run_host_locked(h, text, doc_off, ndocs, ids_out, ids_cap, id_off_out, max_ids, unk, starts_out, ends_out, words, first_doc_nonempty, defer_ids);
         if (r != BF_RETRY_POOL) return r;
         (void)hipDeviceSynchronize();
         unsigned long long need = 0;
-        if (!hip_ok(hipMemcpy(&need, h->w_misc.as<char>() + 224, 8, hipMemcpyDeviceToHost), "D2H pool need")) return BF_E_DEVICE;
+        if (!hip_ok(hipMemcpy(&need, &h->misc()->big_need, 8, hipMemcpyDeviceToHost), "D2H pool need")) return BF_E_DEVICE;
         const size_t want = std::max(h->w_big.cap * 2, h->w_big.cap + (size_t)need + (size_t)(need >> 2) + ((size_t)1 << 20));
         h->bpe_pool_bytes = want;
         if (!h->w_big.reserve(want)) { g_last_error = "the arc pool of a BPE document does not fit the device memory"; return BF_E_DEVICE; }
@@ -931,9 +1055,7 @@ int64_t run_host_locked(Handle *h, const char *text, const int64_t *doc_off, int
         const int64_t r = run_host_chunked(h, text, doc_off, ndocs, ids_out, ids_cap, id_off_out, max_ids, unk);
         if (r != HOST_PIPE_UNAVAILABLE) return r;
     }
-    // worst-case id count: _wp ids cover >= 1 byte each; _sp tokens cover >= 1 element of <= mul*(n+1) elements
-    int64_t worst = h->m.kind == KIND_WP ? total : (int64_t)(h->m.dict_has_charmap ? 2 : 1) * (total + ndocs);
-    if (max_ids >= 0 && ndocs * (int64_t)max_ids < worst) worst = ndocs * (int64_t)(max_ids < 0 ? 0 : max_ids);
+    const int64_t worst = worst_ids(h->m, total, ndocs, max_ids);
     if (!h->w_text.reserve((size_t)total + 16) || !h->w_docoff.reserve((size_t)(ndocs + 1) * 8) ||
         !h->w_idoff.reserve((size_t)(ndocs + 1) * 8) || !h->w_ids.reserve((size_t)(worst + 1) * 4)) return BF_E_DEVICE;
     if (want_off && (!h->w_starts.reserve((size_t)(worst + 1) * 4) || !h->w_ends.reserve((size_t)(worst + 1) * 4))) return BF_E_DEVICE;
@@ -955,7 +1077,7 @@ int64_t run_host_locked(Handle *h, const char *text, const int64_t *doc_off, int
     int64_t nids_word = 0;
     if (!hip_ok(hipMemcpyAsync(&nids_word, h->w_idoff.as<int64_t>() + ndocs, 8, hipMemcpyDeviceToHost, s), "D2H id count")) return BF_E_DEVICE;
     int status = 0;
-    if (!hip_ok(hipMemcpyAsync(&status, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost, s), "D2H status")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemcpyAsync(&status, &h->misc()->status, 4, hipMemcpyDeviceToHost, s), "D2H status")) return BF_E_DEVICE;
     int32_t nch0 = 0;
     if (words && ndocs == 1 && !hip_ok(hipMemcpyAsync(&nch0, h->w_nchars.p, 4, hipMemcpyDeviceToHost, s), "D2H nchars")) return BF_E_DEVICE;
     if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
@@ -989,21 +1111,19 @@ int run_words_device(Handle *h, const char *d_text, const int64_t *d_doc_off, in
                             h->w_starts.as<int32_t>(), h->w_ends.as<int32_t>(), mode);
         if (rc != 0) return rc;
     }
-    const int nblocks = scan_nblocks(ndocs);
     W2tParams p{(const uint8_t *)d_text, d_doc_off, ndocs, h->w_idoff.as<int64_t>(), h->w_starts.as<int32_t>(), h->w_ends.as<int32_t>(),
                 h->w_counts.as<int32_t>(), d_out_off, (uint8_t *)d_out, out_cap, mode == 2 ? h->w_nchars.as<int32_t>() : nullptr};
-    // documents of many tokens are measured and assembled by sixteen waves each (k_w2t_len_long / k_w2t_copy_long); w_misc + 56 / + 52: their number
-    // (+ 56 zeroed with the status word by run_device above, + 52 below)
+    // documents of many tokens are measured and assembled by sixteen waves each (k_w2t_len_long / k_w2t_copy_long); their numbers: w2t_len_long_n
+    // (cleared by run_device's begin_launch above) and w2t_copy_long_n (cleared below)
     p.long_cap = total_bytes / 1024 + 2;
     p.long_list = h->w_w2tlong.reserve((size_t)p.long_cap * 8) ? h->w_w2tlong.as<int64_t>() : nullptr;
-    p.long_count = (unsigned int *)(h->w_misc.as<char>() + 56);
+    p.long_count = &h->misc()->w2t_len_long_n;
     if (tokenise) {
         if (ndocs > 0) { if (mode == 2) launch_s2t_len(p, s); else launch_w2t_len(p, s); }
-        ScanParams sp{h->w_counts.as<int32_t>(), ndocs, d_out_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
+        scan_counts(h, ndocs, d_out_off, s);
     }
     if (d_out && ndocs > 0) {
-        p.long_count = (unsigned int *)(h->w_misc.as<char>() + 52);
+        p.long_count = &h->misc()->w2t_copy_long_n;
         if (!p.long_list || !hip_ok(hipMemsetAsync(p.long_count, 0, 4, s), "hipMemsetAsync")) p.long_list = nullptr;
         if (mode == 2) launch_s2t_copy(p, s); else launch_w2t_copy(p, s);
     }
@@ -1023,11 +1143,10 @@ int run_i2t_device(Handle *h, const int32_t *d_ids, const int64_t *d_id_off, int
     p.tok_off = h->t_i2w_off.as<uint32_t>(); p.tok_data = h->t_i2w_data.as<uint8_t>(); p.ntok = (int)m.i2w_off.size() - 1;
     p.min_id = m.min_token_id; p.max_id = m.max_token_id; p.skip_special = skip_special ? 1 : 0;
     p.ids = d_ids; p.id_off = d_id_off; p.nseq = nseq; p.lens = h->w_counts.as<int32_t>();
-    p.text_off = d_text_off; p.text = (uint8_t *)d_text; p.text_cap = text_cap; p.status = (int *)(h->w_misc.as<char>() + 16);
+    p.text_off = d_text_off; p.text = (uint8_t *)d_text; p.text_cap = text_cap; p.status = &h->misc()->status;
     if (nseq > 0 && !d_text) launch_i2t_len(p, s);
     if (!d_text) {
-        ScanParams sp{h->w_counts.as<int32_t>(), nseq, d_text_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
+        scan_counts(h, nseq, d_text_off, s);
     } else if (nseq > 0) launch_i2t_copy(p, s);
     return hip_ok(hipGetLastError(), "IdsToText kernels") ? 0 : BF_E_DEVICE;
 }
@@ -1100,14 +1219,14 @@ int64_t run_i2t_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64
     hipStream_t s = h->stream;
     Staged st;
     int status = 0;
-    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;      // the status word the size pass reports an unknown id in
+    if (!clear_launch_words(h, s)) return BF_E_DEVICE;      // the status word the size pass reports an unknown id in
     const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s);
     if (rc != 0) return rc;
     const int64_t total = two_pass_host(s, nseq, h->w_idoff, h->w_text, 1, text_out, text_cap, text_off_out,
         [&](void *d_out, int64_t out_cap) {
             return run_i2t_device(h, h->w_ids.as<int32_t>(), h->w_docoff.as<int64_t>(), nseq, (char *)d_out, out_cap, h->w_idoff.as<int64_t>(), skip_special, s);
         },
-        [&]() { return hip_ok(hipMemcpyAsync(&status, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost, s), "D2H status"); });
+        [&]() { return hip_ok(hipMemcpyAsync(&status, &h->misc()->status, 4, hipMemcpyDeviceToHost, s), "D2H status"); });
     if (unknown_id) *unknown_id = (status & 4) != 0;
     return total;
 }
@@ -1136,8 +1255,7 @@ int run_normsp_device(Handle *h, const char *d_text, const int64_t *d_doc_off, i
     p.lens = h->w_counts.as<int32_t>(); p.aux = h->w_nchars.as<int32_t>(); p.out_off = d_out_off; p.out = (uint8_t *)d_out; p.out_cap = out_cap;
     if (size) {
         if (ndocs > 0) launch_normsp(p, false, s);
-        ScanParams sp{h->w_counts.as<int32_t>(), ndocs, d_out_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
+        scan_counts(h, ndocs, d_out_off, s);
     }
     if (d_out && ndocs > 0) launch_normsp(p, true, s);
     return hip_ok(hipGetLastError(), "NormalizeSpaces kernels") ? 0 : BF_E_DEVICE;
@@ -1152,8 +1270,7 @@ int run_hashes_device(Handle *h, const char *d_text, const int64_t *d_doc_off, i
     HashParams p{(const uint8_t *)d_text, d_doc_off, ndocs, ngrams, bucket, h->w_counts.as<int32_t>(), d_out_off, d_out, out_cap};
     if (size) {
         if (ndocs > 0) launch_hash_count(p, s);
-        ScanParams sp{h->w_counts.as<int32_t>(), ndocs, d_out_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
+        scan_counts(h, ndocs, d_out_off, s);
     }
     if (d_out && ndocs > 0) launch_hash_fill(p, s);
     return hip_ok(hipGetLastError(), "TextToHashes kernels") ? 0 : BF_E_DEVICE;
@@ -1178,12 +1295,11 @@ int run_w2h_device(Handle *h, const char *d_text, const int64_t *d_word_off, int
     if (!reserve_w2h_workspaces(h, nwords, total_bytes)) return BF_E_DEVICE;
     p.t.T = h->t_w2h.as<uint64_t>(); p.t.pats = h->t_w2h_pats.as<uint8_t>(); p.t.cp_l1 = h->t_w2h_l1.as<uint16_t>(); p.t.cp_pages = h->t_w2h_pages.as<uint32_t>();
     p.t.initial = m.w2h.initial_base; p.t.cls_l = m.w2h_cls_l; p.t.cls_r = m.w2h_cls_r; p.t.min_pat_len = m.w2h_min_pat_len; p.t.no_hyph_len = m.w2h_no_hyph_len;
-    p.text = (const uint8_t *)d_text; p.word_off = d_word_off; p.nwords = nwords; p.total_bytes = total_bytes; p.status = (int *)(h->w_misc.as<char>() + 16);
+    p.text = (const uint8_t *)d_text; p.word_off = d_word_off; p.nwords = nwords; p.total_bytes = total_bytes; p.status = &h->misc()->status;
     p.cls = h->w_hcls.as<uint16_t>(); p.nch = h->w_hnch.as<int32_t>(); p.srcb = h->w_hsrc.as<int32_t>(); p.lens = h->w_counts.as<int32_t>();
     p.out_off = d_out_off; p.out = (uint8_t *)d_out; p.out_cap = out_cap;
     if (size) {
-        if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
-        h->small_status = -1;
+        if (!begin_launch(h, s)) return BF_E_DEVICE;
         (void)hipEventRecord(h->ev[EV_BEGIN], s);
         if (nwords > 0) launch_w2h_prep(p, s);
         (void)hipEventRecord(h->ev[EV_PREP], s);
@@ -1191,8 +1307,7 @@ int run_w2h_device(Handle *h, const char *d_text, const int64_t *d_word_off, int
         if (nwords > 0) launch_w2h_walk(p, s);
         (void)hipEventRecord(h->ev[EV_DOM1], s);
         (void)hipEventRecord(h->ev[EV_TOK], s);
-        ScanParams sp{h->w_counts.as<int32_t>(), nwords, d_out_off, h->w_bsums.as<int64_t>(), scan_nblocks(nwords)};
-        launch_scan(sp, s);
+        scan_counts(h, nwords, d_out_off, s);
         (void)hipEventRecord(h->ev[EV_SCAN], s);
     }
     if (d_out && nwords > 0) launch_w2h_copy(p, s);
@@ -1213,18 +1328,16 @@ int run_rows_device(Handle *h, const int32_t *d_ids, int64_t ids_len, const int6
 {
     if (nseq < 0 || ids_len < 0 || rows_cap < 0 || !d_id_off || !d_row_off || (ids_len > 0 && !d_ids)) return BF_E_ARG;
     if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
-    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
-    h->small_status = -1;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
     RowsParams p;
-    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = (int *)(h->w_misc.as<char>() + 16);
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
     p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap; p.rows = d_rows; p.mask = d_mask;
     // a row's sequence and first id go to the caller's arrays or, for the fill, to as much workspace as the handle has (the rows of a batch
     // that is truncated to one row per sequence always fit; growing it here would be a hipMalloc the reserved call must not make)
     p.row_seq = d_row_seq ? d_row_seq : h->w_rowseq.as<int32_t>(); p.seq_rows = d_row_seq ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
     p.row_first = d_row_first ? d_row_first : h->w_rowfirst.as<int32_t>(); p.first_rows = d_row_first ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
     if (nseq > 0) launch_rows_count(p, s);
-    ScanParams sp{h->w_counts.as<int32_t>(), nseq, d_row_off, h->w_bsums.as<int64_t>(), scan_nblocks(nseq)};
-    launch_scan(sp, s);
+    scan_counts(h, nseq, d_row_off, s);
     if (nseq > 0 && (d_rows || d_mask || d_row_seq || d_row_first)) {
         launch_rows_map(p, s);
         if (rows_cap > 0 && (d_rows || d_mask)) launch_rows_fill(p, s);
@@ -1313,8 +1426,7 @@ int run_dict_device(Handle *h, const int32_t *d_keys, const int64_t *d_key_off, 
     p.val_off = d_val_off; p.vals = d_vals; p.vals_cap = vals_cap;
     if (size) {
         if (nkeys > 0) launch_dict_ids(p, s);
-        ScanParams sp{h->w_counts.as<int32_t>(), nkeys, d_val_off, h->w_bsums.as<int64_t>(), nblocks};
-        launch_scan(sp, s);
+        scan_counts(h, nkeys, d_val_off, s);
     }
     if (d_vals && nkeys > 0) launch_dict_fill(p, s);
     return hip_ok(hipGetLastError(), "dictionary lookup kernels") ? 0 : BF_E_DEVICE;
@@ -1880,7 +1992,7 @@ int IdsToTextBatchDevice(void *p, const int32_t *d_ids, const int64_t *d_id_offs
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    if (!hip_ok(hipMemsetAsync(h->w_misc.p, 0, 64, s), "hipMemsetAsync")) return BF_E_DEVICE;
+    if (!clear_launch_words(h, s)) return BF_E_DEVICE;
     int rc = run_i2t_device(h, d_ids, d_id_offsets, nseq, nullptr, 0, d_text_offsets_out, skip_special, s);
     if (rc != 0 || !d_text_out) return rc;
     return run_i2t_device(h, d_ids, d_id_offsets, nseq, d_text_out, text_cap, d_text_offsets_out, skip_special, s);
@@ -2169,7 +2281,7 @@ int BfLastStatus(void *p)
     if (h->small_status >= 0) return h->small_status;
     if (h->ev_valid) (void)hipEventSynchronize(h->ev[EV_COMPACT]);
     int status = 0;
-    if (!hip_ok(hipMemcpy(&status, h->w_misc.as<char>() + 16, 4, hipMemcpyDeviceToHost), "D2H status")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemcpy(&status, &h->misc()->status, 4, hipMemcpyDeviceToHost), "D2H status")) return BF_E_DEVICE;
     return status;
 }
 
@@ -2183,7 +2295,7 @@ int BfLexStats(void *p, unsigned long long *out, int n)
     std::lock_guard<std::mutex> lock(h->mu);
     (void)hipDeviceSynchronize();
     if (n > 16) n = 16;
-    if (!hip_ok(hipMemcpy(out, h->w_misc.as<char>() + 64, (size_t)n * 8, hipMemcpyDeviceToHost), "D2H stats")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemcpy(out, h->misc()->stats, (size_t)n * 8, hipMemcpyDeviceToHost), "D2H stats")) return BF_E_DEVICE;
     return n;
 }
 
@@ -2225,7 +2337,7 @@ int BfSetLexStats(void *p, int on)
     (void)hipDeviceSynchronize();
     const int old = h->lex_stats ? 1 : 0;
     h->lex_stats = on != 0;
-    if (!hip_ok(hipMemset(h->w_misc.as<char>() + 64, 0, 128), "hipMemset(stats)")) return BF_E_DEVICE;
+    if (!hip_ok(hipMemset(h->misc()->stats, 0, MISC_STATS_BYTES), "hipMemset(stats)")) return BF_E_DEVICE;
     return old;
 }
 

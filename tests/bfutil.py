@@ -479,3 +479,39 @@ def fuzz_docs(n, seed=1, maxwords=60):
         if b:
             docs.append(b)
     return docs
+
+
+# ------------------------------------------------------------------------------------------------
+# TextToWords / TextToSentences checkers (tests/test_words.py and the GPU batch tests)
+# ------------------------------------------------------------------------------------------------
+def words_call(fn, args_before, b, mx, args_after=()):
+    """one ...WithOffsets call into sentinel-filled buffers -> (return value, raw output, starts, ends)"""
+    o = ctypes.create_string_buffer(b"\x7f" * (max(mx, 1) + 4))
+    s = (ctypes.c_int32 * max(mx, 1))(*([-7] * max(mx, 1)))
+    e = (ctypes.c_int32 * max(mx, 1))(*([-7] * max(mx, 1)))
+    r = fn(*args_before, b, len(b), o, s, e, mx, *args_after)
+    return r, o.raw, list(s), list(e)
+
+
+def oracle_words_fn(mode):
+    """(oracle, its bfo_text_to_words_with_offsets (mode 1) or bfo_text_to_sentences_with_offsets (mode 2))"""
+    ora = oracle()
+    f = ora.lib.bfo_text_to_words_with_offsets if mode == 1 else ora.lib.bfo_text_to_sentences_with_offsets
+    f.restype = ctypes.c_int
+    f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    return ora, f
+
+
+def words_checker(model, mode):
+    """the checker of the GPU batch tests: ask(b, mx) -> the words_call tuple of the compiled reference's TextToWords / TextToSentences
+    ...WithOffsetsWithModel where oracle/_ref is built (model None = its built-in model), else of the oracle; close() frees the model"""
+    if have_ref():
+        ref = reference()
+        g = getattr(ref.lib, "TextToWordsWithOffsetsWithModel" if mode == 1 else "TextToSentencesWithOffsetsWithModel")
+        g.restype = ctypes.c_int
+        g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        hr = ref.load(model_path(model)) if model else None
+        return (lambda b, mx: words_call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,))), (lambda: ref.free(hr) if hr else None)
+    ora, f = oracle_words_fn(mode)
+    ho = ora.load(model_path(model or ("wbd.bin" if mode == 1 else "sbd.bin")))
+    return (lambda b, mx: words_call(f, (ctypes.c_void_p(ho),), b, mx)), (lambda: ora.free(ho))

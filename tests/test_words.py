@@ -14,12 +14,7 @@ def _docs(n, seed):
     return list(bfutil.ADVERSARIAL) + bfutil.fuzz_docs(n, seed=seed) + [b"Hello world . This is a test ."]
 
 
-def _call(fn, args_before, b, mx, args_after=()):
-    o = ctypes.create_string_buffer(b"\x7f" * (max(mx, 1) + 4))
-    s = (ctypes.c_int32 * max(mx, 1))(*([-7] * max(mx, 1)))
-    e = (ctypes.c_int32 * max(mx, 1))(*([-7] * max(mx, 1)))
-    r = fn(*args_before, b, len(b), o, s, e, mx, *args_after)
-    return r, o.raw, list(s), list(e)
+_call = bfutil.words_call
 
 
 def _stored(r):
@@ -32,11 +27,7 @@ def _stored(r):
 
 
 def _oracle_fn():
-    ora = bfutil.oracle()
-    f = ora.lib.bfo_text_to_words_with_offsets
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    return ora, f
+    return bfutil.oracle_words_fn(1)
 
 
 def test_readme_known_answer():
@@ -171,11 +162,7 @@ SENT_DOCS = [b"Hello world. This is a test! Is it? Yes.\nNew line here. And Mr. 
 
 
 def _oracle_sent_fn():
-    ora = bfutil.oracle()
-    f = ora.lib.bfo_text_to_sentences_with_offsets
-    f.restype = ctypes.c_int
-    f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    return ora, f
+    return bfutil.oracle_words_fn(2)
 
 
 def test_sentences_readme_known_answer():
@@ -225,19 +212,7 @@ def test_gpu_text_to_sentences(model):
         ora.free(ho)
 
 
-def _gpu_checker(model, mode):
-    """the checker of the GPU batch tests: ask(b, mx) -> the _call tuple of the compiled reference's TextToWords / TextToSentences
-    ...WithOffsetsWithModel where oracle/_ref is built (model None = its built-in model), else of the oracle; close() frees the model"""
-    if bfutil.have_ref():
-        ref = bfutil.reference()
-        g = getattr(ref.lib, "TextToWordsWithOffsetsWithModel" if mode == 1 else "TextToSentencesWithOffsetsWithModel")
-        g.restype = ctypes.c_int
-        g.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        hr = ref.load(bfutil.model_path(model)) if model else None
-        return (lambda b, mx: _call(g, (), b, mx, (ctypes.c_void_p(hr) if hr else None,))), (lambda: ref.free(hr) if hr else None)
-    ora, f = _oracle_fn() if mode == 1 else _oracle_sent_fn()
-    ho = ora.load(bfutil.model_path(model or ("wbd.bin" if mode == 1 else "sbd.bin")))
-    return (lambda b, mx: _call(f, (ctypes.c_void_p(ho),), b, mx)), (lambda: ora.free(ho))
+_gpu_checker = bfutil.words_checker
 
 
 @pytest.mark.gpu
