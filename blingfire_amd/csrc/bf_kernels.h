@@ -1,4 +1,4 @@
-// bf_kernels.h -- device-side parameter blocks + launch wrappers (implemented in bf_kernels.hip).
+// bf_kernels.h -- device-side parameter blocks + launch wrappers (implemented in the bf_kernels*.hip units).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>

@@ -557,16 +557,9 @@ void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s)
     q.fetch_thresh = (variant >> 16) & 0xf; if (q.fetch_thresh == 0) q.fetch_thresh = 8;
     q.acts_n = p.acts_n;                                          // <= 4096 ints, checked at LoadModel
     int waves_per_cu = (variant >> 24) & 0x3f;
-    if (waves_per_cu == 0) {                                      // persistent: exactly the resident waves
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lex_wp_flat<64, ClsWin, false, 3, false>, 64, lex_lds_bytes(q, 64)) != hipSuccess || per_cu <= 0) per_cu = 16;
-        waves_per_cu = per_cu;
-        (void)hipGetLastError();
-    }
-    int64_t blocks = (int64_t)device_cus() * (int64_t)waves_per_cu;
+    if (waves_per_cu == 0) waves_per_cu = resident_per_cu(k_lex_wp_flat<64, ClsWin, false, 3, false>, 64, lex_lds_bytes(q, 64), 16);      // persistent: exactly the resident waves
     const int64_t need = (p.b.ndocs + 63) / 64;
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = resident_blocks(waves_per_cu, need);
     const bool has_any = p.L.cls_any != LX_CLS_NONE;
     // small models (wbd.bin: TextToWords): the whole table lives in LDS, one copy per workgroup of 512 threads -- or of 256 when the
     // lanes' frames and id buffers leave no room for it beside 512 (wbd.bin: 41 + 27 KB; a table gather from L2 is 250+ ns, the lane
@@ -575,13 +568,7 @@ void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s)
         auto go = [&](auto th) {
             constexpr int TH = decltype(th)::value;
             const size_t lds = lex_lds_bytes(q, TH, true);
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lex_wp_flat<TH, ClsWin, false, 3, false, true>, TH, lds) != hipSuccess || per_cu <= 0) per_cu = 2;
-            (void)hipGetLastError();
-            int64_t nb = (int64_t)device_cus() * per_cu;
-            const int64_t need_b = (p.b.ndocs + TH - 1) / TH;
-            if (nb > need_b) nb = need_b;
-            if (nb < 1) nb = 1;
+            const int64_t nb = resident_blocks(resident_per_cu(k_lex_wp_flat<TH, ClsWin, false, 3, false, true>, TH, lds, 2), (p.b.ndocs + TH - 1) / TH);
             if (has_any) hipLaunchKernelGGL((k_lex_wp_flat<TH, ClsWin, true, 1, false, true>), dim3((unsigned)nb), dim3(TH), lds, s, q);
             else hipLaunchKernelGGL((k_lex_wp_flat<TH, ClsWin, false, 3, false, true>), dim3((unsigned)nb), dim3(TH), lds, s, q);
         };
@@ -597,16 +584,9 @@ void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s)
         // transitions per vote: swept on MI355X with the two-level event code (2: 8.50 ms, 3: 7.67, 4: 6.86 on the 1.25 M-doc shard)
         const int un = (variant >> 20) & 0xf; (void)un;
         const bool plain = !has_any && !q2.words && !q2.span_tmp;
-        int per_cu = 0;
-        const hipError_t oe = plain ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lex_wp_plain<4>, 64, lds2)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lex_wp_flat<64, ClsWin, false, 4, false, false, true>, 64, lds2);
-        if (oe != hipSuccess || per_cu <= 0) per_cu = 16;
-        (void)hipGetLastError();
+        int per_cu = plain ? resident_per_cu(k_lex_wp_plain<4>, 64, lds2, 16) : resident_per_cu(k_lex_wp_flat<64, ClsWin, false, 4, false, false, true>, 64, lds2, 16);
         if (((variant >> 24) & 0x3f) != 0) per_cu = (variant >> 24) & 0x3f;
-        int64_t nb = (int64_t)device_cus() * per_cu;
-        if (nb > need) nb = need;
-        if (nb < 1) nb = 1;
-        const dim3 g2((unsigned)nb), t2(64);
+        const dim3 g2((unsigned)resident_blocks(per_cu, need)), t2(64);
         if (has_any) hipLaunchKernelGGL((k_lex_wp_flat<64, ClsWin, true, 1, false, false, true>), g2, t2, lds2, s, q2);
 #ifdef BF_EXPERIMENTS
         else if (plain && un == 5) hipLaunchKernelGGL(k_lex_wp_plain<5>, g2, t2, lds2, s, q2);
@@ -946,13 +926,7 @@ void launch_lex_long(const WpLexParams &p, hipStream_t s)
     const size_t lds = lex_long_lds_bytes(p, tlds);
     // the number of chunks is on the device: a grid that fills the chip (the resident workgroups: LDS -- frames and the table -- bounds them),
     // workgroups without a chunk leave at once
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lex_long<false, false, false>, LEX_LONG_THREADS, lds) != hipSuccess || per_cu <= 0) per_cu = 4;
-    (void)hipGetLastError();
-    int64_t nb = (int64_t)device_cus() * per_cu;
-    const int64_t most = (p.lg.cap_chunks + 3) / 4;
-    if (nb > most) nb = most;
-    if (nb < 1) nb = 1;
+    const int64_t nb = resident_blocks(resident_per_cu(k_lex_long<false, false, false>, LEX_LONG_THREADS, lds, 4), (p.lg.cap_chunks + 3) / 4);
     int64_t nc = p.lg.cap_docs < (int64_t)device_cus() * 8 ? p.lg.cap_docs : (int64_t)device_cus() * 8;
     if (nc < 1) nc = 1;
     const dim3 g((unsigned)nb), t(LEX_LONG_THREADS);
@@ -1024,10 +998,10 @@ void launch_wp_wave(const WpWaveParams &p, int variant, hipStream_t s)
     typedef WvLds<1024, 256, 8, true> LO;
     static int pc_ids = 0, pc_off = 0, pc_list = 0, pc_list_off = 0;
     int per_cu;
-    if (p.doc_list && p.span_tmp) { per_cu = wp_blocks_per_cu(k_wp_wave<LO, 1, 3, 6, false, 4, true, 15, true>, pc_list_off); grab = 1; }
-    else if (p.doc_list) { per_cu = wp_blocks_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15, true>, pc_list); grab = 1; }
-    else if (p.span_tmp) per_cu = wp_blocks_per_cu(k_wp_wave<LO, 1, 3, 6, false, 4, true, 15>, pc_off);
-    else per_cu = wp_blocks_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15>, pc_ids);
+    if (p.doc_list && p.span_tmp) { per_cu = wave_program_per_cu(k_wp_wave<LO, 1, 3, 6, false, 4, true, 15, true>, pc_list_off); grab = 1; }
+    else if (p.doc_list) { per_cu = wave_program_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15, true>, pc_list); grab = 1; }
+    else if (p.span_tmp) per_cu = wave_program_per_cu(k_wp_wave<LO, 1, 3, 6, false, 4, true, 15>, pc_off);
+    else per_cu = wave_program_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15>, pc_ids);
     if (per_cu_override > 0) per_cu = per_cu_override;
     int64_t blocks = (int64_t)device_cus() * per_cu;
     if (!p.doc_list) {                      // (the number of listed documents is known to the device only)
@@ -1168,12 +1142,9 @@ template <int WPE>
 static void launch_wp_flat_wpe(const WfParams &p, int per_cu_override, hipStream_t s)
 {
     static int pc = 0;
-    int per_cu = wp_blocks_per_cu(k_wp_flat<WPE, false>, pc);
+    int per_cu = wave_program_per_cu(k_wp_flat<WPE, false>, pc);
     if (per_cu_override > 0) per_cu = per_cu_override;
-    int64_t blocks = (int64_t)device_cus() * per_cu;
-    const int64_t need = ((int64_t)p.nranges + 3) / 4;
-    if (blocks > need) blocks = need;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = resident_blocks(per_cu, ((int64_t)p.nranges + 3) / 4);
     if (p.cold.stats) hipLaunchKernelGGL((k_wp_flat<WPE, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((k_wp_flat<WPE, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
@@ -1195,7 +1166,7 @@ template <int WPE, int NU>
 static void launch_wp_units_cfg(const WfUnitParams &p, int per_cu_override, hipStream_t s)
 {
     static int pc = 0;
-    int per_cu = wp_blocks_per_cu(k_wp_units<WPE, NU, false>, pc);
+    int per_cu = wave_program_per_cu(k_wp_units<WPE, NU, false>, pc);
     if (per_cu_override > 0) per_cu = per_cu_override;
     const int64_t blocks = (int64_t)device_cus() * per_cu;
     if (p.hspan) hipLaunchKernelGGL((k_wp_units<WPE, NU, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);      // the offsets API: the pieces carry their spans
@@ -1226,22 +1197,16 @@ void launch_wp_hardlist(const int32_t *dstat, const int *unsafe, int64_t ndocs, 
 
 void launch_wp_count(const WfMergeParams &p, hipStream_t s)
 {
-    int64_t blocks = (p.ndocs + 255) / 256;
     static int pc = 0;
-    const int64_t resident = (int64_t)device_cus() * wp_blocks_per_cu(k_wp_count, pc);
-    if (blocks > resident) blocks = resident;
-    if (blocks < 1) blocks = 1;
+    const int64_t blocks = resident_blocks(wave_program_per_cu(k_wp_count, pc), (p.ndocs + 255) / 256);
     hipLaunchKernelGGL(k_wp_count, dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
 void launch_wp_merge(const WfMergeParams &p, hipStream_t s)
 {
-    static int pc = 0;
-    int64_t blocks = (p.ndocs + 255) / 256;
-    static int pc_off = 0;
-    const int64_t resident = (int64_t)device_cus() * (p.espan ? wp_blocks_per_cu(k_wp_merge<true>, pc_off) : wp_blocks_per_cu(k_wp_merge<false>, pc));      // one round of workgroups: every wave has the same share
-    if (blocks > resident) blocks = resident;
-    if (blocks < 1) blocks = 1;
+    static int pc = 0, pc_off = 0;
+    const int per_cu = p.espan ? wave_program_per_cu(k_wp_merge<true>, pc_off) : wave_program_per_cu(k_wp_merge<false>, pc);
+    const int64_t blocks = resident_blocks(per_cu, (p.ndocs + 255) / 256);      // at most one round of workgroups: every wave has the same share
     if (p.espan) hipLaunchKernelGGL(k_wp_merge<true>, dim3((unsigned)blocks), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_wp_merge<false>, dim3((unsigned)blocks), dim3(256), 0, s, p);
 }

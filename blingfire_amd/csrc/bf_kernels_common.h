@@ -165,16 +165,28 @@ __device__ __forceinline__ uint32_t mbcnt(unsigned long long m) { return __built
 } // namespace wv
 namespace bfa {
 
+// Workgroups of a persistent kernel that are resident on one CU: what the runtime says fits, `fallback` when it cannot say (the error is cleared)
 template <class K>
-static int wp_blocks_per_cu(K kernel, int &cached)
+static int resident_per_cu(K kernel, int threads, size_t lds, int fallback)
 {
-    if (cached <= 0) {
-        int q = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, 256, 0) != hipSuccess || q <= 0) q = 2;
-        (void)hipGetLastError();
-        cached = q;
-    }
+    int q = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, kernel, threads, lds) != hipSuccess || q <= 0) q = fallback;
+    (void)hipGetLastError();
+    return q;
+}
+// the same for the wave programs (256 threads, static LDS only), asked once: `cached` is the call site's static
+template <class K>
+static int wave_program_per_cu(K kernel, int &cached)
+{
+    if (cached <= 0) cached = resident_per_cu(kernel, 256, 0, 2);
     return cached;
+}
+// the grid of a persistent launch: every CU full, but not more workgroups than the work needs, and at least one
+static inline int64_t resident_blocks(int per_cu, int64_t need)
+{
+    int64_t blocks = (int64_t)device_cus() * per_cu;
+    if (blocks > need) blocks = need;
+    return blocks < 1 ? 1 : blocks;
 }
 
 } // namespace bfa

@@ -14,9 +14,9 @@
 #include "bf_bpe_wave_body.h"
 namespace bfa {
 
-// k_bpe_wave: the BPE wave program (bf_bpe_wave_body.h) on the class streams k_prep_sp wrote.  The program is validated in the test
-// simulator (tests/test_bpe_wave_emu.py); the device path (bf_capi.cpp, behind BfSetVariant bit 0x40 until it has had its GPU parity
-// and timing runs) redoes the documents it hands back (flags[d] = 1) with the lane-per-document kernels.
+// k_bpe_wave: the BPE wave program (bf_bpe_wave_body.h) on the class streams k_prep_sp8 wrote.  The same source runs in the test simulator
+// (tests/test_bpe_wave_emu.py).  It is what a model it admits runs by default (bf_capi.cpp enqueue_bpe_wave; BfSetVariant bit 0x40: without it);
+// the documents it hands back (flags[d] = 1) are redone one wave each by k_bpe_seg (launch_bpe_seg_flags).
 __host__ __device__ __forceinline__ int64_t sp_slot(int64_t doc_off_d, int64_t d, int mul) { return (int64_t)mul * (doc_off_d + d); }
 
 template <class LDS, int WPE, int STEPS, int UMIN, bool HOME>
@@ -519,8 +519,8 @@ void launch_prep_sp(const SpPrepParams &p, hipStream_t s)
 }
 
 // ------------------------------------------------------------------------------------------
-// k_seg_sp: one document per lane, the sequential programs of bf_seg.h with lane-private global scratch.
-// (First correct version: static assignment, compiler-managed divergence.)
+// The lane-per-document segmenters (Unigram, plain BPE): the programs of bf_seg.h with lane-private scratch.  They take the documents by
+// stream length (a counting sort in three kernels), so that the 64 documents of a wave are of similar size: perm[i] = the document of thread i.
 // ------------------------------------------------------------------------------------------
 // length bucketing: key = min(len / 4, 1023)
 __device__ __forceinline__ int sp_len_bucket(int len) { int k = len >> 2; return k > 1023 ? 1023 : k; }

@@ -1,8 +1,9 @@
-"""Registers, scratch, LDS and occupancy of every kernel of bf_kernels.hip / bf_kernels_sp.hip as the compiler reports them
-(-Rpass-analysis=kernel-resource-usage, device side only, nothing is linked).  usage: python tools/kernel_resources.py [name filter]"""
-import os, re, subprocess, sys
+"""Registers, scratch, LDS and occupancy of every kernel of the bf_kernels*.hip units (BF_KSRC: a comma-separated list of them instead) as the compiler
+reports them (-Rpass-analysis=kernel-resource-usage, device side only, nothing is linked).  usage: python tools/kernel_resources.py [name filter]"""
+import glob, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-srcs = [os.path.join(ROOT, "blingfire_amd", "csrc", f) for f in os.environ.get("BF_KSRC", "bf_kernels.hip,bf_kernels_sp.hip").split(",")]
+CSRC = os.path.join(ROOT, "blingfire_amd", "csrc")
+srcs = [os.path.join(CSRC, f) for f in os.environ["BF_KSRC"].split(",")] if os.environ.get("BF_KSRC") else sorted(glob.glob(os.path.join(CSRC, "bf_kernels*.hip")))
 procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-c"] +
                           (["-DBF_EXPERIMENTS"] if os.environ.get("BF_EXPERIMENTS") else []) +
                           ["-Rpass-analysis=kernel-resource-usage", src, "-o", "/dev/null"], stderr=subprocess.PIPE, text=True) for src in srcs]
