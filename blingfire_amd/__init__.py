@@ -92,6 +92,11 @@ def lib():
         L.IdsToRowsBatchDevice.restype = c_int
         L.IdsToRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+        L.IdsToPairRowsBatch.restype = c_int64
+        L.IdsToPairRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [c_int64, c_void_p]
+        L.IdsToPairRowsBatchDevice.restype = c_int
+        L.IdsToPairRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [
+            c_int64, c_void_p, c_void_p]
         L.BfLastKernelMs.restype = c_int
         L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
         L.BfLastStatus.restype = c_int
@@ -540,6 +545,115 @@ def encode_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_p
     d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
     d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
     return encode_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, stride, max_rows_per_doc, pad_left)
+
+
+def _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep):
+    return (int(L), _special(cls_id), _special(sep_id), int(pad_id), int(mode), int(max_a), int(stride), int(max_rows_per_pair),
+            (1 if pad_left else 0) | (2 if double_sep else 0))
+
+
+def ids_to_pair_rows_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
+                           pad_left=False, double_sep=False):
+    """additive: pairs of ragged ids (two int32 arrays + two int64 offsets[nseq+1]) -> [cls] A [sep] B [sep] rows with type ids
+    (IdsToPairRowsBatch).  mode 1: one row per pair, ids dropped from the end of the longer side until both fit (max_a, stride and
+    max_rows_per_pair stay at their defaults).  mode 0: the first max_a ids of A in every row, B cut into windows that share `stride` ids
+    (max_rows_per_pair: 1 = truncate B, 0 = every window).  double_sep: two separators between A and B.  Returns (rows int32[R, L],
+    mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[nseq+1]): the rows of pair q are
+    [row_offsets[q], row_offsets[q+1]), row_first_b is the index within B of a row's first B id."""
+    ids_a = np.ascontiguousarray(ids_a, dtype=np.int32); off_a = np.ascontiguousarray(off_a, dtype=np.int64)
+    ids_b = np.ascontiguousarray(ids_b, dtype=np.int32); off_b = np.ascontiguousarray(off_b, dtype=np.int64)
+    nseq = len(off_a) - 1
+    if len(off_b) != nseq + 1:
+        raise ValueError("ids_to_pair_rows_batch: off_a and off_b name different numbers of sequences")
+    r_off = np.zeros(nseq + 1, dtype=np.int64)
+    pre = (c_void_p(h), ids_a.ctypes.data, off_a.ctypes.data, ids_b.ctypes.data, off_b.ctypes.data, nseq) + _pair_args(
+        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+    fn = lib().IdsToPairRowsBatch
+    n = fn(*pre, None, None, None, None, None, 0, r_off.ctypes.data)          # the size query
+    if n < 0:
+        raise RuntimeError("IdsToPairRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    rows = np.empty((n, L), dtype=np.int32)
+    mask = np.empty((n, L), dtype=np.uint8)
+    typ = np.empty((n, L), dtype=np.uint8)
+    seq = np.empty(n, dtype=np.int32)
+    first = np.empty(n, dtype=np.int32)
+    if n > 0:
+        r = fn(*pre, rows.ctypes.data, mask.ctypes.data, typ.ctypes.data, seq.ctypes.data, first.ctypes.data, n, r_off.ctypes.data)
+        if r != n:
+            raise RuntimeError("IdsToPairRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return rows, mask, typ, seq, first, r_off
+
+
+def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0,
+                                  max_rows_per_pair=1, pad_left=False, double_sep=False, rows_cap=None, stream=None):
+    """Device-resident ids_to_pair_rows_batch: torch int32 ids + int64 offsets of both sides on one GPU (the results of two
+    text_to_ids_batch_device calls as they are; the same tensor may serve both sides) -> the same six results as tensors on that device,
+    enqueued on torch's current stream (or `stream`).  rows_cap None: nseq rows when one row per pair is certain (mode 1, or
+    max_rows_per_pair 1: nothing is read back); otherwise a size query whose total is read back (one synchronisation).  With a rows_cap of
+    the caller's the tensors have rows_cap rows, row_offsets[-1] of them valid; rows beyond it are dropped (BfLastStatus bit 0)."""
+    import torch
+    nseq = d_off_a.numel() - 1
+    if d_off_b.numel() != nseq + 1:
+        raise ValueError("ids_to_pair_rows_batch_device: d_off_a and d_off_b name different numbers of sequences")
+    dev = d_ids_a.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
+    pre = (c_void_p(h), d_ids_a.data_ptr(), d_ids_a.numel(), d_off_a.data_ptr(), d_ids_b.data_ptr(), d_ids_b.numel(), d_off_b.data_ptr(), nseq) + _pair_args(
+        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+    fn = lib().IdsToPairRowsBatchDevice
+    if rows_cap is None:
+        if mode == 1 or max_rows_per_pair == 1:
+            rows_cap = nseq
+        else:
+            r = fn(*pre, None, None, None, None, None, 0, r_off.data_ptr(), c_void_p(s))
+            if r != 0:
+                raise RuntimeError("IdsToPairRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+            if stream is not None:
+                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
+            rows_cap = int(r_off[-1].item())
+    rows = torch.empty((rows_cap, L), dtype=torch.int32, device=dev)
+    mask = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
+    typ = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
+    seq = torch.empty(rows_cap, dtype=torch.int32, device=dev)
+    first = torch.empty(rows_cap, dtype=torch.int32, device=dev)
+    r = fn(*pre, rows.data_ptr(), mask.data_ptr(), typ.data_ptr(), seq.data_ptr(), first.data_ptr(), rows_cap, r_off.data_ptr(), c_void_p(s))
+    if r != 0:
+        raise RuntimeError("IdsToPairRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return rows, mask, typ, seq, first, r_off
+
+
+def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
+                              pad_left=False, double_sep=False):
+    """Two texts in HBM -> the tensors a pair model takes, nothing on the host: two text_to_ids_batch_device calls and
+    ids_to_pair_rows_batch_device on one stream.  Each side is tokenised up to the ids its rows can hold: T = L - specials for both in mode 1
+    (cutting both to T first does not change what longest-first keeps); in mode 0 max_a for A and T + (max_rows_per_pair - 1) * (T - stride)
+    for B (all of B when max_rows_per_pair is 0).
+    Returns (rows int32[R, L], mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[npairs+1])."""
+    nsep = 0 if _special(sep_id) < 0 else 3 if double_sep else 2
+    T = int(L) - (1 if _special(cls_id) >= 0 else 0) - nsep
+    if T < 1 or mode not in (0, 1) or (mode == 0 and not (0 <= max_a <= T - 1 and 0 <= stride < T - max_a and max_rows_per_pair >= 0)):
+        raise ValueError("encode_pairs_batch_device: L leaves no room for ids, or mode / max_a / stride / max_rows_per_pair are out of range")
+    if mode == 1:
+        len_a = len_b = T
+    else:
+        len_a = int(max_a)
+        len_b = min(T + (max_rows_per_pair - 1) * (T - int(stride)), 2 ** 31 - 1) if max_rows_per_pair > 0 else 2 ** 31 - 1
+    d_ids_a, d_idoff_a = text_to_ids_batch_device(h, d_text_a, d_off_a, len_a, unk)
+    d_ids_b, d_idoff_b = text_to_ids_batch_device(h, d_text_b, d_off_b, len_b, unk)
+    return ids_to_pair_rows_batch_device(h, d_ids_a, d_idoff_a, d_ids_b, d_idoff_b, L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair,
+                                         pad_left, double_sep)
+
+
+def encode_pairs_batch(h, docs_a, docs_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1, pad_left=False, double_sep=False):
+    """encode_pairs_batch_device for two lists of str / bytes (or two (uint8 array, int64 offsets) pairs): packed, uploaded with torch to the
+    current device, encoded there."""
+    import torch
+    d = []
+    for docs in (docs_a, docs_b):
+        text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
+        d.append(torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda())
+        d.append(torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda())
+    return encode_pairs_batch_device(h, d[0], d[1], d[2], d[3], L, cls_id, sep_id, pad_id, unk, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
 
 
 def dict_get_info_batch(h, keys):

@@ -105,7 +105,7 @@ struct PinBuf {
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device and in run_rows_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            size pass of run_w2h_device, in run_rows_device and in run_pairs_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
 //                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
@@ -200,7 +200,7 @@ struct Handle {
     DevBuf t_wbd, t_info, t_acts, t_cp_l1, t_cp_pages, t_multi, t_i2w_off, t_i2w_data;
     DevBuf t_w2h, t_w2h_pats, t_w2h_l1, t_w2h_pages;             // [w2h]: pattern automaton, pattern pool, code point -> class (bf_w2h.h)
     DevBuf w_hcls, w_hnch, w_hsrc;                               // WordHyphenationBatch: position stream, characters and source bytes per word
-    DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch: sequence and first id of every row, where the caller takes neither
+    DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch / IdsToPairRowsBatch: sequence (pair) and first id of every row, where the caller takes neither
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -1386,6 +1386,81 @@ int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int6
     return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && ok ? total : BF_E_DEVICE;
 }
 
+// IdsToPairRowsBatch on device buffers (bf_pairs.h, bf_kernels_pairs.hip): the steps and the workspaces of run_rows_device, over two sources
+int run_pairs_device(Handle *h, const int32_t *d_ids_a, int64_t len_a, const int64_t *d_off_a, const int32_t *d_ids_b, int64_t len_b, const int64_t *d_off_b,
+                     int64_t nseq, const PairsSpec &spec, int32_t *d_rows, uint8_t *d_mask, uint8_t *d_type, int32_t *d_row_seq, int32_t *d_row_first,
+                     int64_t rows_cap, int64_t *d_row_off, hipStream_t s)
+{
+    if (nseq < 0 || len_a < 0 || len_b < 0 || rows_cap < 0 || !d_off_a || !d_off_b || !d_row_off || (len_a > 0 && !d_ids_a) || (len_b > 0 && !d_ids_b)) return BF_E_ARG;
+    if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    PairsParams p;
+    p.spec = spec; p.ids_a = d_ids_a; p.len_a = len_a; p.off_a = d_off_a; p.ids_b = d_ids_b; p.len_b = len_b; p.off_b = d_off_b; p.nseq = nseq;
+    p.status = &h->misc()->status; p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap;
+    p.rows = d_rows; p.mask = d_mask; p.type = d_type;
+    // (the caller's arrays or as much workspace as the handle has: run_rows_device)
+    p.row_seq = d_row_seq ? d_row_seq : h->w_rowseq.as<int32_t>(); p.seq_rows = d_row_seq ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
+    p.row_first = d_row_first ? d_row_first : h->w_rowfirst.as<int32_t>(); p.first_rows = d_row_first ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
+    if (nseq > 0) launch_pairs_count(p, s);
+    scan_counts(h, nseq, d_row_off, s);
+    if (nseq > 0 && (d_rows || d_mask || d_type || d_row_seq || d_row_first)) {
+        launch_pairs_map(p, s);
+        if (rows_cap > 0 && (d_rows || d_mask || d_type)) launch_pairs_fill(p, s);
+    }
+    return hip_ok(hipGetLastError(), "IdsToPairRows kernels") ? 0 : BF_E_DEVICE;
+}
+
+// the ids one side's offsets can name in the host form: from the first offset to the largest; -1 = refused (a negative first offset)
+static int64_t host_side_len(const int64_t *off, int64_t nseq)
+{
+    if (off[0] < 0) return -1;
+    int64_t len = 0;
+    for (int64_t i = 0; i <= nseq; ++i) len = std::max(len, off[i] - off[0]);
+    return len;
+}
+
+// host buffers: both sides through stage_ragged, then the two passes of run_rows_host (size pass, offsets to the caller, capacity check, fill
+// pass, outputs to the caller); returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written
+int64_t run_pairs_host(Handle *h, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, const PairsSpec &spec,
+                       int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
+{
+    if (nseq < 0 || rows_cap < 0 || !off_a || !off_b || !row_off_out) return BF_E_ARG;
+    const int64_t len_a = host_side_len(off_a, nseq), len_b = host_side_len(off_b, nseq);
+    if (len_a < 0 || len_b < 0 || (len_a > 0 && !ids_a) || (len_b > 0 && !ids_b)) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (w_ids, w_starts and w_ends may hold a sharded range's ids that wait for their copy out)
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
+    Staged sa, sb;                                       // A in the id staging, B in the key staging of the dictionary lookup
+    int rc = stage_ragged(sa, ids_a, 4, off_a, nseq, h->w_ids, h->w_docoff, s, len_a);
+    if (rc == 0) rc = stage_ragged(sb, ids_b, 4, off_b, nseq, h->w_keys, h->w_keyoff, s, len_b);
+    auto pass = [&](int32_t *d_rows, uint8_t *d_mask, uint8_t *d_type, int32_t *d_seq, int32_t *d_first, int64_t cap) {
+        return run_pairs_device(h, h->w_ids.as<int32_t>(), len_a, h->w_docoff.as<int64_t>(), h->w_keys.as<int32_t>(), len_b, h->w_keyoff.as<int64_t>(), nseq, spec,
+                                d_rows, d_mask, d_type, d_seq, d_first, cap, h->w_idoff.as<int64_t>(), s);
+    };
+    if (rc == 0) rc = pass(nullptr, nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
+    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
+        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    const int64_t total = row_off_out[nseq];
+    if (total == 0 || (!rows_out && !mask_out && !type_out && !row_seq_out && !row_first_out)) return total;      // (a size query needs no capacity)
+    if (total > rows_cap) return BF_E_CAPACITY;
+    const size_t cells = (size_t)total * (size_t)spec.row_len;
+    if ((rows_out && !h->w_out.reserve(cells * 4 + 16)) || (mask_out && !h->w_text.reserve(cells + 16)) || (type_out && !h->w_vals.reserve(cells + 16)) ||
+        (row_seq_out && !h->w_starts.reserve((size_t)total * 4)) || (row_first_out && !h->w_ends.reserve((size_t)total * 4))) return BF_E_DEVICE;
+    rc = pass(rows_out ? h->w_out.as<int32_t>() : nullptr, mask_out ? h->w_text.as<uint8_t>() : nullptr, type_out ? h->w_vals.as<uint8_t>() : nullptr,
+              row_seq_out ? h->w_starts.as<int32_t>() : nullptr, row_first_out ? h->w_ends.as<int32_t>() : nullptr, total);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
+    bool ok = true;
+    if (rows_out) ok = ok && hip_ok(hipMemcpyAsync(rows_out, h->w_out.p, cells * 4, hipMemcpyDeviceToHost, s), "D2H rows");
+    if (mask_out) ok = ok && hip_ok(hipMemcpyAsync(mask_out, h->w_text.p, cells, hipMemcpyDeviceToHost, s), "D2H mask");
+    if (type_out) ok = ok && hip_ok(hipMemcpyAsync(type_out, h->w_vals.p, cells, hipMemcpyDeviceToHost, s), "D2H types");
+    if (row_seq_out) ok = ok && hip_ok(hipMemcpyAsync(row_seq_out, h->w_starts.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row pairs");
+    if (row_first_out) ok = ok && hip_ok(hipMemcpyAsync(row_first_out, h->w_ends.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row firsts");
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && ok ? total : BF_E_DEVICE;
+}
+
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
 bool ensure_dict_tables(Handle *h)
 {
@@ -2020,6 +2095,31 @@ int64_t IdsToRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, i
     RowsSpec spec;
     if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec)) return BF_E_ARG;
     return run_rows_host(h, ids, id_offsets, nseq, spec, rows_out, mask_out, row_seq_out, row_first_out, rows_cap, row_offsets_out);
+}
+
+/* ---- additive: the same for pairs (bf_pairs.h): [cls] A [sep] B [sep] rows with type ids, B windowed per pair or both sides cut longest first */
+int IdsToPairRowsBatchDevice(void *p, const int32_t *d_ids_a, int64_t ids_a_len, const int64_t *d_off_a, const int32_t *d_ids_b, int64_t ids_b_len,
+                             const int64_t *d_off_b, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride,
+                             int max_rows_per_pair, int flags, int32_t *d_rows_out, uint8_t *d_mask_out, uint8_t *d_type_out, int32_t *d_row_seq_out,
+                             int32_t *d_row_first_b_out, int64_t rows_cap, int64_t *d_row_offsets_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    PairsSpec spec;
+    if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_pairs_device(h, d_ids_a, ids_a_len, d_off_a, d_ids_b, ids_b_len, d_off_b, nseq, spec, d_rows_out, d_mask_out, d_type_out, d_row_seq_out,
+                            d_row_first_b_out, rows_cap, d_row_offsets_out, (hipStream_t)stream);
+}
+
+int64_t IdsToPairRowsBatch(void *p, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, int row_len, int cls_id,
+                           int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags, int32_t *rows_out, uint8_t *mask_out,
+                           uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out, int64_t rows_cap, int64_t *row_offsets_out)
+{
+    Handle *h = as_handle(p);
+    PairsSpec spec;
+    if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec)) return BF_E_ARG;
+    return run_pairs_host(h, ids_a, off_a, ids_b, off_b, nseq, spec, rows_out, mask_out, type_out, row_seq_out, row_first_b_out, rows_cap, row_offsets_out);
 }
 
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */

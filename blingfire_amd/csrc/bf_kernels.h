@@ -10,6 +10,7 @@
 #include "bf_flat.h"
 #include "bf_w2h.h"
 #include "bf_rows.h"
+#include "bf_pairs.h"
 
 namespace bfa {
 
@@ -267,6 +268,23 @@ struct RowsParams {
 void launch_rows_count(const RowsParams &p, hipStream_t s);
 void launch_rows_map(const RowsParams &p, hipStream_t s);
 void launch_rows_fill(const RowsParams &p, hipStream_t s);
+unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU
+
+// IdsToPairRowsBatch (additive; bf_pairs.h, bf_kernels_pairs.hip): pairs of ragged ids -> rows of row_len cells + mask + type.
+// Pair q = A: ids_a[off_a[q] .. off_a[q+1]), B: ids_b[off_b[q] .. off_b[q+1])
+struct PairsParams {
+    PairsSpec spec;
+    const int32_t *ids_a, *ids_b; int64_t len_a, len_b; const int64_t *off_a, *off_b; int64_t nseq; int *status;
+    int32_t *counts;             // [nseq] rows per pair
+    const int64_t *row_off;      // [nseq + 1] exclusive scan of counts; row_off[nseq] = the row total, read on the device
+    int64_t rows_cap;            // no row r >= rows_cap of any output is written
+    int32_t *rows; uint8_t *mask, *type;                             // [rows_cap * row_len] each, each may be NULL
+    // pair and first B id of every row, as RowsParams holds sequence and first id
+    int32_t *row_seq, *row_first; int64_t seq_rows, first_rows;
+};
+void launch_pairs_count(const PairsParams &p, hipStream_t s);
+void launch_pairs_map(const PairsParams &p, hipStream_t s);
+void launch_pairs_fill(const PairsParams &p, hipStream_t s);
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

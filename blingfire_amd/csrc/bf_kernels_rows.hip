@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_rows_fill(RowsParams p)
     }
 }
 
-static unsigned rows_blocks(int64_t items)
+unsigned rows_blocks(int64_t items)
 {
     int64_t blocks = (items + 255) / 256;
     if (blocks > (int64_t)device_cus() * 8) blocks = (int64_t)device_cus() * 8;

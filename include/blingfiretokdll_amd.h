@@ -176,6 +176,48 @@ BF_API int64_t IdsToRowsBatch(void *ModelPtr, const int32_t *ids, const int64_t 
                        int32_t *rows_out, uint8_t *mask_out, int32_t *row_seq_out, int32_t *row_first_out,
                        int64_t rows_cap, int64_t *row_offsets_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): fixed-shape model inputs from PAIRS of ragged id sequences,
+ * [cls] A [sep] B [sep] with token type ids -- cross-encoder / NLI inputs, and extractive-QA windows whose question is repeated in every row.
+ * Pair q of nseq is A = ids_a[off_a[q] .. off_a[q+1]) (na ids) and B = ids_b[off_b[q] .. off_b[q+1]) (nb ids), e.g. the d_ids_out /
+ * d_id_offsets_out of two TextToIdsBatchDevice calls as they are; ids_a and ids_b may be the same array.
+ * Specials: cls_id < 0 = no leading special; sep_id < 0 = no separators at all; with sep_id >= 0 one separator stands between A and B (two
+ * with flags bit 1, the RoBERTa form) and one behind B.  S = the number of specials, T = row_len - S = the room for ids.  A row is
+ *     [cls_id] A' [sep_id]([sep_id]) B' [sep_id] pad_id...                   (flags bit 0: the padding comes first)
+ * the mask is 1 over everything but the padding; the type byte is 0 over cls, A' and the middle separator(s), 1 over B' and the trailing
+ * separator, 0 over the padding.
+ * mode 0, window the second sequence: ka = min(na, max_a) and A' = the first ka ids of A, in every row of the pair.  The pair's own geometry
+ * is body_b = T - ka and step = body_b - stride: it yields 1 row when nb <= body_b (nb = 0 too), else 1 + ceil((nb - body_b) / step) rows, at
+ * most max_rows_per_pair of them when that is > 0 (1 = truncate B, 0 = all windows).  Row w of the pair holds B[w * step .. min(nb, w * step +
+ * body_b)).  BF_E_ARG unless 0 <= max_a <= T - 1, 0 <= stride < T - max_a and max_rows_per_pair >= 0 (every pair then has body_b >= 1 and
+ * step >= 1: no pair can fail on its own).
+ * mode 1, longest first, one row per pair: ids are dropped from the end of the longer sequence, one at a time, until ka + kb <= T; on a tie the
+ * id is dropped from B.  (In closed form ka = min(na, max(ceil(T / 2), T - nb)), kb = min(nb, T - ka); truncating both inputs to T ids first
+ * does not change the result.)  A' / B' = the first ka / kb ids.  BF_E_ARG unless max_a == 0, stride == 0 and max_rows_per_pair == 1.
+ * BF_E_ARG also for row_len outside 1 .. 1 << 20, T < 1, a mode other than 0 and 1, another flag bit, flags bit 1 with sep_id < 0 and a NULL
+ * ModelPtr (any live handle: it lends its device, workspaces and status word; the model is not consulted).  Rows come in pair order, windows
+ * in order.
+ * Device form: enqueues on `stream` (a hipStream_t), does not synchronise, returns 0 or BF_E_*.  ids_a_len / ids_b_len = the elements of
+ * d_ids_a / d_ids_b that may be read (capacities, exactly as ids_len of IdsToRowsBatchDevice); a range that is not inside [0, len] or whose
+ * offsets decrease makes that side of its pair empty and sets BfLastStatus bit 3.  d_row_offsets_out[nseq+1] is always complete: the rows of
+ * pair q are [off[q], off[q+1]).  d_rows_out (int32), d_mask_out and d_type_out (uint8; [rows_cap * row_len] each), d_row_seq_out (the pair of
+ * every row) and d_row_first_b_out (the index within B of the row's first B id, w * step, saturating at INT32_MAX; [rows_cap] each) may each
+ * be NULL; all five NULL = a size query.  No row r >= rows_cap of any output is written; rows dropped that way, and a saturated row count or
+ * first-id index, set BfLastStatus bit 0 (the call clears the status word first).  After BfReserve(h, max_docs >= nseq, ...) the call allocates
+ * nothing.  Every pointer needs only the natural alignment of its type; 16-byte aligned d_rows_out, 4-byte aligned d_mask_out and d_type_out
+ * and row_len % 4 == 0 take the wide stores.
+ * Host form: returns the row total, or BF_E_CAPACITY with complete offsets and nothing else written; with all five outputs NULL it is a size
+ * query that returns the total whatever rows_cap is.  It reads each side from its first offset to its largest one; off_a[0] < 0 or
+ * off_b[0] < 0 = BF_E_ARG. */
+BF_API int IdsToPairRowsBatchDevice(void *ModelPtr, const int32_t *d_ids_a, int64_t ids_a_len, const int64_t *d_off_a,
+                             const int32_t *d_ids_b, int64_t ids_b_len, const int64_t *d_off_b, int64_t nseq,
+                             int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags,
+                             int32_t *d_rows_out, uint8_t *d_mask_out, uint8_t *d_type_out, int32_t *d_row_seq_out, int32_t *d_row_first_b_out,
+                             int64_t rows_cap, int64_t *d_row_offsets_out, void *stream);
+BF_API int64_t IdsToPairRowsBatch(void *ModelPtr, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq,
+                           int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags,
+                           int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out,
+                           int64_t rows_cap, int64_t *row_offsets_out);
+
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
 
@@ -291,7 +333,8 @@ BF_API int BfModelKind(void *ModelPtr);
 /* Optional: size every workspace of the handle for batches of up to max_docs documents / max_bytes bytes of text now, so that
  * later ...BatchDevice calls of that size allocate nothing (workspaces only ever grow; growing means hipMalloc, which
  * synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
- * Every kind of handle has the workspaces of IdsToRowsBatchDevice sized for max_docs sequences (an [i2w]-only handle has no others).
+ * Every kind of handle has the workspaces of IdsToRowsBatchDevice and IdsToPairRowsBatchDevice (the same ones) sized for max_docs sequences
+ * or pairs (an [i2w]-only handle has no others).
  * Returns 0 or BF_E_*. */
 BF_API int BfReserve(void *ModelPtr, int64_t max_docs, int64_t max_bytes, int want_offsets);
 /* BPE models: the size of the pool from which documents with very many candidate arcs claim their working memory (about 16 bytes per
