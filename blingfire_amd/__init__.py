@@ -463,6 +463,46 @@ def _special(i):
     return -1 if i is None else int(i)
 
 
+def _rows_host(name, pre, nseq, L, planes):
+    """the host forms of the row stage: the size query, then every output (one `planes` dtype per [R, L] plane, row item, row first id)"""
+    fn = getattr(lib(), name)
+    r_off = np.zeros(nseq + 1, dtype=np.int64)
+    n = fn(*pre, *[None] * (len(planes) + 2), 0, r_off.ctypes.data)
+    if n < 0:
+        raise RuntimeError("%s failed: %d (%s)" % (name, n, lib().BfLastError().decode("utf-8", "replace")))
+    outs = [np.empty((n, L), dtype=t) for t in planes] + [np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)]
+    if n > 0:
+        r = fn(*pre, *[o.ctypes.data for o in outs], n, r_off.ctypes.data)
+        if r != n:
+            raise RuntimeError("%s failed: %d (%s)" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
+    return (*outs, r_off)
+
+
+def _rows_device(name, pre, nseq, L, planes, one_row, rows_cap, dev, stream):
+    """the device forms of the row stage.  rows_cap None: nseq rows where one row per item is certain (`one_row`), else a size query whose
+    total is read back"""
+    import torch
+    fn = getattr(lib(), name)
+    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
+
+    def call(outs, cap):
+        r = fn(*pre, *outs, cap, r_off.data_ptr(), s)
+        if r != 0:
+            raise RuntimeError("%s failed (%d): %s" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
+    if rows_cap is None:
+        if one_row:
+            rows_cap = nseq
+        else:
+            call([None] * (len(planes) + 2), 0)
+            if stream is not None:
+                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
+            rows_cap = int(r_off[-1].item())
+    outs = [torch.empty((rows_cap, L), dtype=t, device=dev) for t in planes] + [torch.empty(rows_cap, dtype=torch.int32, device=dev) for _ in range(2)]
+    call([o.data_ptr() for o in outs], rows_cap)
+    return (*outs, r_off)
+
+
 def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False):
     """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> fixed-shape model inputs (IdsToRowsBatch).  A sequence longer than
     the row is cut into windows that share `stride` ids (max_rows_per_seq: 1 = truncate, 0 = every window); cls_id / sep_id None = no
@@ -471,22 +511,9 @@ def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, str
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     id_off = np.ascontiguousarray(id_off, dtype=np.int64)
     nseq = len(id_off) - 1
-    r_off = np.zeros(nseq + 1, dtype=np.int64)
     pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride),
            int(max_rows_per_seq), int(bool(pad_left)))
-    fn = lib().IdsToRowsBatch
-    n = fn(*pre, None, None, None, None, 0, r_off.ctypes.data)          # the size query
-    if n < 0:
-        raise RuntimeError("IdsToRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
-    rows = np.empty((n, L), dtype=np.int32)
-    mask = np.empty((n, L), dtype=np.uint8)
-    seq = np.empty(n, dtype=np.int32)
-    first = np.empty(n, dtype=np.int32)
-    if n > 0:
-        r = fn(*pre, rows.ctypes.data, mask.ctypes.data, seq.ctypes.data, first.ctypes.data, n, r_off.ctypes.data)
-        if r != n:
-            raise RuntimeError("IdsToRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return rows, mask, seq, first, r_off
+    return _rows_host("IdsToRowsBatch", pre, nseq, L, (np.int32, np.uint8))
 
 
 def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False,
@@ -497,30 +524,9 @@ def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pa
     rows_cap of the caller's the tensors have rows_cap rows, row_offsets[-1] of them valid; rows beyond it are dropped (BfLastStatus bit 0)."""
     import torch
     nseq = d_id_off.numel() - 1
-    dev = d_ids.device
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
     pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id),
            int(stride), int(max_rows_per_seq), int(bool(pad_left)))
-    fn = lib().IdsToRowsBatchDevice
-    if rows_cap is None:
-        if max_rows_per_seq == 1:
-            rows_cap = nseq
-        else:
-            r = fn(*pre, None, None, None, None, 0, r_off.data_ptr(), c_void_p(s))
-            if r != 0:
-                raise RuntimeError("IdsToRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
-            if stream is not None:
-                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
-            rows_cap = int(r_off[-1].item())
-    rows = torch.empty((rows_cap, L), dtype=torch.int32, device=dev)
-    mask = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
-    seq = torch.empty(rows_cap, dtype=torch.int32, device=dev)
-    first = torch.empty(rows_cap, dtype=torch.int32, device=dev)
-    r = fn(*pre, rows.data_ptr(), mask.data_ptr(), seq.data_ptr(), first.data_ptr(), rows_cap, r_off.data_ptr(), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("IdsToRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return rows, mask, seq, first, r_off
+    return _rows_device("IdsToRowsBatchDevice", pre, nseq, L, (torch.int32, torch.uint8), max_rows_per_seq == 1, rows_cap, d_ids.device, stream)
 
 
 def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False):
@@ -565,23 +571,9 @@ def ids_to_pair_rows_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id
     nseq = len(off_a) - 1
     if len(off_b) != nseq + 1:
         raise ValueError("ids_to_pair_rows_batch: off_a and off_b name different numbers of sequences")
-    r_off = np.zeros(nseq + 1, dtype=np.int64)
     pre = (c_void_p(h), ids_a.ctypes.data, off_a.ctypes.data, ids_b.ctypes.data, off_b.ctypes.data, nseq) + _pair_args(
         L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    fn = lib().IdsToPairRowsBatch
-    n = fn(*pre, None, None, None, None, None, 0, r_off.ctypes.data)          # the size query
-    if n < 0:
-        raise RuntimeError("IdsToPairRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
-    rows = np.empty((n, L), dtype=np.int32)
-    mask = np.empty((n, L), dtype=np.uint8)
-    typ = np.empty((n, L), dtype=np.uint8)
-    seq = np.empty(n, dtype=np.int32)
-    first = np.empty(n, dtype=np.int32)
-    if n > 0:
-        r = fn(*pre, rows.ctypes.data, mask.ctypes.data, typ.ctypes.data, seq.ctypes.data, first.ctypes.data, n, r_off.ctypes.data)
-        if r != n:
-            raise RuntimeError("IdsToPairRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return rows, mask, typ, seq, first, r_off
+    return _rows_host("IdsToPairRowsBatch", pre, nseq, L, (np.int32, np.uint8, np.uint8))
 
 
 def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0,
@@ -595,31 +587,10 @@ def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_
     nseq = d_off_a.numel() - 1
     if d_off_b.numel() != nseq + 1:
         raise ValueError("ids_to_pair_rows_batch_device: d_off_a and d_off_b name different numbers of sequences")
-    dev = d_ids_a.device
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
     pre = (c_void_p(h), d_ids_a.data_ptr(), d_ids_a.numel(), d_off_a.data_ptr(), d_ids_b.data_ptr(), d_ids_b.numel(), d_off_b.data_ptr(), nseq) + _pair_args(
         L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    fn = lib().IdsToPairRowsBatchDevice
-    if rows_cap is None:
-        if mode == 1 or max_rows_per_pair == 1:
-            rows_cap = nseq
-        else:
-            r = fn(*pre, None, None, None, None, None, 0, r_off.data_ptr(), c_void_p(s))
-            if r != 0:
-                raise RuntimeError("IdsToPairRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
-            if stream is not None:
-                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
-            rows_cap = int(r_off[-1].item())
-    rows = torch.empty((rows_cap, L), dtype=torch.int32, device=dev)
-    mask = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
-    typ = torch.empty((rows_cap, L), dtype=torch.uint8, device=dev)
-    seq = torch.empty(rows_cap, dtype=torch.int32, device=dev)
-    first = torch.empty(rows_cap, dtype=torch.int32, device=dev)
-    r = fn(*pre, rows.data_ptr(), mask.data_ptr(), typ.data_ptr(), seq.data_ptr(), first.data_ptr(), rows_cap, r_off.data_ptr(), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("IdsToPairRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return rows, mask, typ, seq, first, r_off
+    return _rows_device("IdsToPairRowsBatchDevice", pre, nseq, L, (torch.int32, torch.uint8, torch.uint8), mode == 1 or max_rows_per_pair == 1, rows_cap,
+                        d_ids_a.device, stream)
 
 
 def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,

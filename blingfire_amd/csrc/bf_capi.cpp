@@ -105,7 +105,7 @@ struct PinBuf {
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device, in run_rows_device and in run_pairs_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            size pass of run_w2h_device, and in run_row_stage_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
 //                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
@@ -1316,101 +1316,41 @@ int run_w2h_device(Handle *h, const char *d_text, const int64_t *d_word_off, int
     return hip_ok(hipGetLastError(), "WordHyphenation kernels") ? 0 : BF_E_DEVICE;
 }
 
-// IdsToRowsBatch on device buffers (bf_rows.h, bf_kernels_rows.hip): count, scan, then -- when the caller takes any of the four outputs -- map and fill
+// The row stage on device buffers (bf_rowstage_body.h; S = RowsSource: IdsToRowsBatch, PairsSource: IdsToPairRowsBatch): count, scan, then -- when the
+// caller takes any of the outputs -- map and fill.  out[]: rows, mask, type (NULL where S has none), a row's item, its first id.
 bool reserve_rows_workspaces(Handle *h, int64_t nseq)
 {
     return h->w_counts.reserve((size_t)(nseq + 1) * 4) && h->w_bsums.reserve((size_t)(scan_nblocks(nseq) + 1) * 8) &&
            h->w_rowseq.reserve((size_t)(nseq + 1) * 4) && h->w_rowfirst.reserve((size_t)(nseq + 1) * 4);
 }
 
-int run_rows_device(Handle *h, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, const RowsSpec &spec, int32_t *d_rows,
-                    uint8_t *d_mask, int32_t *d_row_seq, int32_t *d_row_first, int64_t rows_cap, int64_t *d_row_off, hipStream_t s)
+constexpr int ROW_OUTS = 5;
+
+template <class S>
+int run_row_stage_device(Handle *h, const S &src, int64_t nseq, void *const out[ROW_OUTS], int64_t rows_cap, int64_t *d_row_off, hipStream_t s, const char *what)
 {
-    if (nseq < 0 || ids_len < 0 || rows_cap < 0 || !d_id_off || !d_row_off || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    if (nseq < 0 || rows_cap < 0 || !d_row_off || !src.valid()) return BF_E_ARG;
     if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
     if (!begin_launch(h, s)) return BF_E_DEVICE;
-    RowsParams p;
-    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
-    p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap; p.rows = d_rows; p.mask = d_mask;
-    // a row's sequence and first id go to the caller's arrays or, for the fill, to as much workspace as the handle has (the rows of a batch
-    // that is truncated to one row per sequence always fit; growing it here would be a hipMalloc the reserved call must not make)
-    p.row_seq = d_row_seq ? d_row_seq : h->w_rowseq.as<int32_t>(); p.seq_rows = d_row_seq ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
-    p.row_first = d_row_first ? d_row_first : h->w_rowfirst.as<int32_t>(); p.first_rows = d_row_first ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
-    if (nseq > 0) launch_rows_count(p, s);
+    RowStageParams<S> p;
+    p.src = src; p.nseq = nseq; p.status = &h->misc()->status; p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap;
+    p.rows = (int32_t *)out[0]; p.mask = (uint8_t *)out[1]; p.type = S::HAS_TYPE ? (uint8_t *)out[2] : nullptr;
+    // a row's item and first id go to the caller's arrays or, for the fill, to as much workspace as the handle has (the rows of a batch
+    // that is truncated to one row per item always fit; growing it here would be a hipMalloc the reserved call must not make)
+    p.row_seq = out[3] ? (int32_t *)out[3] : h->w_rowseq.as<int32_t>(); p.seq_rows = out[3] ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
+    p.row_first = out[4] ? (int32_t *)out[4] : h->w_rowfirst.as<int32_t>(); p.first_rows = out[4] ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
+    const bool planes = p.rows || p.mask || p.type;
+    if (nseq > 0) launch_rowstage_count(p, s);
     scan_counts(h, nseq, d_row_off, s);
-    if (nseq > 0 && (d_rows || d_mask || d_row_seq || d_row_first)) {
-        launch_rows_map(p, s);
-        if (rows_cap > 0 && (d_rows || d_mask)) launch_rows_fill(p, s);
+    if (nseq > 0 && (planes || out[3] || out[4])) {
+        launch_rowstage_map(p, s);
+        if (rows_cap > 0 && planes) launch_rowstage_fill(p, s);
     }
-    return hip_ok(hipGetLastError(), "IdsToRows kernels") ? 0 : BF_E_DEVICE;
+    return hip_ok(hipGetLastError(), what) ? 0 : BF_E_DEVICE;
 }
 
-// host buffers: upload, run, download; returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written
-int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const RowsSpec &spec, int32_t *rows_out, uint8_t *mask_out,
-                      int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
-{
-    if (nseq < 0 || rows_cap < 0 || !id_off || !row_off_out) return BF_E_ARG;
-    // the ids the sequences can name: from the first offset to the largest (an offset below the first one makes its sequences empty, as on the device)
-    const int64_t base = id_off[0];
-    if (base < 0) return BF_E_ARG;
-    int64_t ids_len = 0;
-    for (int64_t i = 0; i <= nseq; ++i) ids_len = std::max(ids_len, id_off[i] - base);
-    if (ids_len > 0 && !ids) return BF_E_ARG;
-    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (the id buffers this call uses may hold a sharded range's ids that wait for their copy out)
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    hipStream_t s = h->stream;
-    if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
-    Staged st;
-    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
-    if (rc != 0) return rc;
-    rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, nullptr, nullptr, nullptr, nullptr, 0, h->w_idoff.as<int64_t>(), s);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
-        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t total = row_off_out[nseq];
-    if (total == 0 || (!rows_out && !mask_out && !row_seq_out && !row_first_out)) return total;      // (a size query needs no capacity)
-    if (total > rows_cap) return BF_E_CAPACITY;
-    const size_t cells = (size_t)total * (size_t)spec.row_len;
-    if ((rows_out && !h->w_out.reserve(cells * 4 + 16)) || (mask_out && !h->w_text.reserve(cells + 16)) ||
-        (row_seq_out && !h->w_starts.reserve((size_t)total * 4)) || (row_first_out && !h->w_ends.reserve((size_t)total * 4))) return BF_E_DEVICE;
-    rc = run_rows_device(h, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, spec, rows_out ? h->w_out.as<int32_t>() : nullptr,
-                         mask_out ? h->w_text.as<uint8_t>() : nullptr, row_seq_out ? h->w_starts.as<int32_t>() : nullptr,
-                         row_first_out ? h->w_ends.as<int32_t>() : nullptr, total, h->w_idoff.as<int64_t>(), s);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    bool ok = true;
-    if (rows_out) ok = ok && hip_ok(hipMemcpyAsync(rows_out, h->w_out.p, cells * 4, hipMemcpyDeviceToHost, s), "D2H rows");
-    if (mask_out) ok = ok && hip_ok(hipMemcpyAsync(mask_out, h->w_text.p, cells, hipMemcpyDeviceToHost, s), "D2H mask");
-    if (row_seq_out) ok = ok && hip_ok(hipMemcpyAsync(row_seq_out, h->w_starts.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row sequences");
-    if (row_first_out) ok = ok && hip_ok(hipMemcpyAsync(row_first_out, h->w_ends.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row firsts");
-    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && ok ? total : BF_E_DEVICE;
-}
-
-// IdsToPairRowsBatch on device buffers (bf_pairs.h, bf_kernels_pairs.hip): the steps and the workspaces of run_rows_device, over two sources
-int run_pairs_device(Handle *h, const int32_t *d_ids_a, int64_t len_a, const int64_t *d_off_a, const int32_t *d_ids_b, int64_t len_b, const int64_t *d_off_b,
-                     int64_t nseq, const PairsSpec &spec, int32_t *d_rows, uint8_t *d_mask, uint8_t *d_type, int32_t *d_row_seq, int32_t *d_row_first,
-                     int64_t rows_cap, int64_t *d_row_off, hipStream_t s)
-{
-    if (nseq < 0 || len_a < 0 || len_b < 0 || rows_cap < 0 || !d_off_a || !d_off_b || !d_row_off || (len_a > 0 && !d_ids_a) || (len_b > 0 && !d_ids_b)) return BF_E_ARG;
-    if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
-    if (!begin_launch(h, s)) return BF_E_DEVICE;
-    PairsParams p;
-    p.spec = spec; p.ids_a = d_ids_a; p.len_a = len_a; p.off_a = d_off_a; p.ids_b = d_ids_b; p.len_b = len_b; p.off_b = d_off_b; p.nseq = nseq;
-    p.status = &h->misc()->status; p.counts = h->w_counts.as<int32_t>(); p.row_off = d_row_off; p.rows_cap = rows_cap;
-    p.rows = d_rows; p.mask = d_mask; p.type = d_type;
-    // (the caller's arrays or as much workspace as the handle has: run_rows_device)
-    p.row_seq = d_row_seq ? d_row_seq : h->w_rowseq.as<int32_t>(); p.seq_rows = d_row_seq ? rows_cap : (int64_t)(h->w_rowseq.cap / 4);
-    p.row_first = d_row_first ? d_row_first : h->w_rowfirst.as<int32_t>(); p.first_rows = d_row_first ? rows_cap : (int64_t)(h->w_rowfirst.cap / 4);
-    if (nseq > 0) launch_pairs_count(p, s);
-    scan_counts(h, nseq, d_row_off, s);
-    if (nseq > 0 && (d_rows || d_mask || d_type || d_row_seq || d_row_first)) {
-        launch_pairs_map(p, s);
-        if (rows_cap > 0 && (d_rows || d_mask || d_type)) launch_pairs_fill(p, s);
-    }
-    return hip_ok(hipGetLastError(), "IdsToPairRows kernels") ? 0 : BF_E_DEVICE;
-}
-
-// the ids one side's offsets can name in the host form: from the first offset to the largest; -1 = refused (a negative first offset)
+// the ids one side's offsets can name in the host form: from the first offset to the largest (an offset below the first one makes its
+// sequences empty, as on the device); -1 = refused (a negative first offset)
 static int64_t host_side_len(const int64_t *off, int64_t nseq)
 {
     if (off[0] < 0) return -1;
@@ -1419,46 +1359,85 @@ static int64_t host_side_len(const int64_t *off, int64_t nseq)
     return len;
 }
 
-// host buffers: both sides through stage_ragged, then the two passes of run_rows_host (size pass, offsets to the caller, capacity check, fill
-// pass, outputs to the caller); returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written
+// one optional output of the host form: the caller's array, the staging buffer it is filled in, its bytes per row (slots as run_row_stage_device's)
+struct RowOut { void *host; DevBuf *dev; size_t row_bytes; const char *what; };
+
+// Behind the staging of the host forms (the caller holds h->defer_mu, then h->mu -- w_ids, w_starts and w_ends may hold a sharded range's ids
+// that wait for their copy out -- and has reserved w_idoff): size pass, offsets to the caller, capacity check, fill pass, outputs to the caller.
+//   pass(d_out, cap)  run_row_stage_device over the staged source, with the row offsets in w_idoff
+// Returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written.  As in two_pass_host, whatever ends the call
+// early after work was queued synchronises the stream first.
+int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&outs)[ROW_OUTS], int64_t rows_cap, int64_t *row_off_out,
+                       const std::function<int(void *const d_out[ROW_OUTS], int64_t cap)> &pass)
+{
+    auto fail = [s](int64_t rc) { (void)hipStreamSynchronize(s); return rc; };
+    void *d_out[ROW_OUTS] = {};
+    int rc = pass(d_out, 0);
+    if (rc != 0) return fail(rc);
+    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets")) return fail(BF_E_DEVICE);
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    const int64_t total = row_off_out[nseq];
+    bool any = false;
+    for (const RowOut &o : outs) any = any || o.host;
+    if (total == 0 || !any) return total;                                     // (a size query needs no capacity)
+    if (total > rows_cap) return BF_E_CAPACITY;
+    for (int i = 0; i < ROW_OUTS; ++i) {
+        if (!outs[i].host) continue;
+        if (!outs[i].dev->reserve((size_t)total * outs[i].row_bytes + 16)) return BF_E_DEVICE;
+        d_out[i] = outs[i].dev->p;
+    }
+    rc = pass(d_out, total);
+    if (rc != 0) return fail(rc);
+    for (const RowOut &o : outs)
+        if (o.host && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, (size_t)total * o.row_bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? total : BF_E_DEVICE;
+}
+
+// IdsToRowsBatch on host buffers: the ids through stage_ragged, then row_stage_host
+int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const RowsSpec &spec, int32_t *rows_out, uint8_t *mask_out,
+                      int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
+{
+    if (nseq < 0 || rows_cap < 0 || !id_off || !row_off_out) return BF_E_ARG;
+    const int64_t ids_len = host_side_len(id_off, nseq);
+    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
+    Staged st;
+    const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    const RowsSource src{spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>()};
+    const size_t L = (size_t)spec.row_len;
+    const RowOut outs[ROW_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {nullptr, nullptr, 0, ""},
+                                   {row_seq_out, &h->w_starts, 4, "D2H row sequences"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
+    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_OUTS], int64_t cap) {
+        return run_row_stage_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), s, "IdsToRows kernels"); });
+}
+
+// IdsToPairRowsBatch on host buffers: A in the id staging, B in the key staging of the dictionary lookup, then row_stage_host
 int64_t run_pairs_host(Handle *h, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, const PairsSpec &spec,
                        int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
 {
     if (nseq < 0 || rows_cap < 0 || !off_a || !off_b || !row_off_out) return BF_E_ARG;
     const int64_t len_a = host_side_len(off_a, nseq), len_b = host_side_len(off_b, nseq);
     if (len_a < 0 || len_b < 0 || (len_a > 0 && !ids_a) || (len_b > 0 && !ids_b)) return BF_E_ARG;
-    std::lock_guard<std::mutex> dlock(h->defer_mu);      // (w_ids, w_starts and w_ends may hold a sharded range's ids that wait for their copy out)
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
     if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
-    Staged sa, sb;                                       // A in the id staging, B in the key staging of the dictionary lookup
+    Staged sa, sb;
     int rc = stage_ragged(sa, ids_a, 4, off_a, nseq, h->w_ids, h->w_docoff, s, len_a);
     if (rc == 0) rc = stage_ragged(sb, ids_b, 4, off_b, nseq, h->w_keys, h->w_keyoff, s, len_b);
-    auto pass = [&](int32_t *d_rows, uint8_t *d_mask, uint8_t *d_type, int32_t *d_seq, int32_t *d_first, int64_t cap) {
-        return run_pairs_device(h, h->w_ids.as<int32_t>(), len_a, h->w_docoff.as<int64_t>(), h->w_keys.as<int32_t>(), len_b, h->w_keyoff.as<int64_t>(), nseq, spec,
-                                d_rows, d_mask, d_type, d_seq, d_first, cap, h->w_idoff.as<int64_t>(), s);
-    };
-    if (rc == 0) rc = pass(nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets") ||
-        !hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t total = row_off_out[nseq];
-    if (total == 0 || (!rows_out && !mask_out && !type_out && !row_seq_out && !row_first_out)) return total;      // (a size query needs no capacity)
-    if (total > rows_cap) return BF_E_CAPACITY;
-    const size_t cells = (size_t)total * (size_t)spec.row_len;
-    if ((rows_out && !h->w_out.reserve(cells * 4 + 16)) || (mask_out && !h->w_text.reserve(cells + 16)) || (type_out && !h->w_vals.reserve(cells + 16)) ||
-        (row_seq_out && !h->w_starts.reserve((size_t)total * 4)) || (row_first_out && !h->w_ends.reserve((size_t)total * 4))) return BF_E_DEVICE;
-    rc = pass(rows_out ? h->w_out.as<int32_t>() : nullptr, mask_out ? h->w_text.as<uint8_t>() : nullptr, type_out ? h->w_vals.as<uint8_t>() : nullptr,
-              row_seq_out ? h->w_starts.as<int32_t>() : nullptr, row_first_out ? h->w_ends.as<int32_t>() : nullptr, total);
-    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }
-    bool ok = true;
-    if (rows_out) ok = ok && hip_ok(hipMemcpyAsync(rows_out, h->w_out.p, cells * 4, hipMemcpyDeviceToHost, s), "D2H rows");
-    if (mask_out) ok = ok && hip_ok(hipMemcpyAsync(mask_out, h->w_text.p, cells, hipMemcpyDeviceToHost, s), "D2H mask");
-    if (type_out) ok = ok && hip_ok(hipMemcpyAsync(type_out, h->w_vals.p, cells, hipMemcpyDeviceToHost, s), "D2H types");
-    if (row_seq_out) ok = ok && hip_ok(hipMemcpyAsync(row_seq_out, h->w_starts.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row pairs");
-    if (row_first_out) ok = ok && hip_ok(hipMemcpyAsync(row_first_out, h->w_ends.p, (size_t)total * 4, hipMemcpyDeviceToHost, s), "D2H row firsts");
-    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") && ok ? total : BF_E_DEVICE;
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }                  // (A's copies may be queued)
+    const PairsSource src{spec, h->w_ids.as<int32_t>(), h->w_keys.as<int32_t>(), len_a, len_b, h->w_docoff.as<int64_t>(), h->w_keyoff.as<int64_t>()};
+    const size_t L = (size_t)spec.row_len;
+    const RowOut outs[ROW_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {type_out, &h->w_vals, L, "D2H types"},
+                                   {row_seq_out, &h->w_starts, 4, "D2H row pairs"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
+    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_OUTS], int64_t cap) {
+        return run_row_stage_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), s, "IdsToPairRows kernels"); });
 }
 
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
@@ -2083,8 +2062,8 @@ int IdsToRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const i
     if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec)) return BF_E_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    return run_rows_device(h, d_ids, ids_len, d_id_offsets, nseq, spec, d_rows_out, d_mask_out, d_row_seq_out, d_row_first_out, rows_cap, d_row_offsets_out,
-                           (hipStream_t)stream);
+    void *const out[ROW_OUTS] = {d_rows_out, d_mask_out, nullptr, d_row_seq_out, d_row_first_out};
+    return run_row_stage_device(h, RowsSource{spec, d_ids, ids_len, d_id_offsets}, nseq, out, rows_cap, d_row_offsets_out, (hipStream_t)stream, "IdsToRows kernels");
 }
 
 int64_t IdsToRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int stride,
@@ -2108,8 +2087,9 @@ int IdsToPairRowsBatchDevice(void *p, const int32_t *d_ids_a, int64_t ids_a_len,
     if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec)) return BF_E_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    return run_pairs_device(h, d_ids_a, ids_a_len, d_off_a, d_ids_b, ids_b_len, d_off_b, nseq, spec, d_rows_out, d_mask_out, d_type_out, d_row_seq_out,
-                            d_row_first_b_out, rows_cap, d_row_offsets_out, (hipStream_t)stream);
+    void *const out[ROW_OUTS] = {d_rows_out, d_mask_out, d_type_out, d_row_seq_out, d_row_first_b_out};
+    return run_row_stage_device(h, PairsSource{spec, d_ids_a, d_ids_b, ids_a_len, ids_b_len, d_off_a, d_off_b}, nseq, out, rows_cap, d_row_offsets_out,
+                                (hipStream_t)stream, "IdsToPairRows kernels");
 }
 
 int64_t IdsToPairRowsBatch(void *p, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, int row_len, int cls_id,

@@ -253,38 +253,28 @@ void launch_w2h_prep(const W2hParams &p, hipStream_t s);
 void launch_w2h_walk(const W2hParams &p, hipStream_t s);
 void launch_w2h_copy(const W2hParams &p, hipStream_t s);
 
-// IdsToRowsBatch (additive; bf_rows.h, bf_kernels_rows.hip): ragged ids -> rows of row_len cells + mask.  Sequence q = ids[id_off[q] .. id_off[q+1])
-struct RowsParams {
-    RowsSpec spec;
-    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
-    int32_t *counts;             // [nseq] rows per sequence
+// IdsToRowsBatch / IdsToPairRowsBatch (additive): items of a source S (bf_rows.h RowsSource: ragged ids; bf_pairs.h PairsSource: pairs of them) ->
+// rows of row_len cells + mask (+ type where S has one).  The kernels are bf_rowstage_body.h, instantiated for RowsSource in bf_kernels_rows.hip and
+// for PairsSource in bf_kernels_pairs.hip.
+template <class S>
+struct RowStageParams {
+    S src;
+    int64_t nseq; int *status;
+    int32_t *counts;             // [nseq] rows per item
     const int64_t *row_off;      // [nseq + 1] exclusive scan of counts; row_off[nseq] = the row total, read on the device
     int64_t rows_cap;            // no row r >= rows_cap of any output is written
     int32_t *rows; uint8_t *mask;                                    // [rows_cap * row_len] each, either may be NULL
-    // sequence and first id of every row: the caller's arrays (seq_rows / first_rows = rows_cap) or, for one the caller left out, the
+    // item and first id of every row: the caller's arrays (seq_rows / first_rows = rows_cap) or, for one the caller left out, the
     // handle's workspace and the rows it holds; the fill finds a row at or past them by its own search
     int32_t *row_seq, *row_first; int64_t seq_rows, first_rows;
+    // [rows_cap * row_len] like mask, may be NULL (always, where S has none).  Last, so that a source without one leaves the kernel arguments it
+    // reads where they were: the RowsSource kernels then have the instruction counts of the hand-written ones, with it behind `mask` two more
+    uint8_t *type;
 };
-void launch_rows_count(const RowsParams &p, hipStream_t s);
-void launch_rows_map(const RowsParams &p, hipStream_t s);
-void launch_rows_fill(const RowsParams &p, hipStream_t s);
-unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU
-
-// IdsToPairRowsBatch (additive; bf_pairs.h, bf_kernels_pairs.hip): pairs of ragged ids -> rows of row_len cells + mask + type.
-// Pair q = A: ids_a[off_a[q] .. off_a[q+1]), B: ids_b[off_b[q] .. off_b[q+1])
-struct PairsParams {
-    PairsSpec spec;
-    const int32_t *ids_a, *ids_b; int64_t len_a, len_b; const int64_t *off_a, *off_b; int64_t nseq; int *status;
-    int32_t *counts;             // [nseq] rows per pair
-    const int64_t *row_off;      // [nseq + 1] exclusive scan of counts; row_off[nseq] = the row total, read on the device
-    int64_t rows_cap;            // no row r >= rows_cap of any output is written
-    int32_t *rows; uint8_t *mask, *type;                             // [rows_cap * row_len] each, each may be NULL
-    // pair and first B id of every row, as RowsParams holds sequence and first id
-    int32_t *row_seq, *row_first; int64_t seq_rows, first_rows;
-};
-void launch_pairs_count(const PairsParams &p, hipStream_t s);
-void launch_pairs_map(const PairsParams &p, hipStream_t s);
-void launch_pairs_fill(const PairsParams &p, hipStream_t s);
+template <class S> void launch_rowstage_count(const RowStageParams<S> &p, hipStream_t s);
+template <class S> void launch_rowstage_map(const RowStageParams<S> &p, hipStream_t s);
+template <class S> void launch_rowstage_fill(const RowStageParams<S> &p, hipStream_t s);
+unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU (bf_kernels_rows.hip)
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -126,4 +126,37 @@ BF_HD int32_t pairs_cell_value(const PairsSpec &s, const PairCell &c, const int3
     return v;
 }
 
+// The pair stage's source (what a source supplies: bf_rows.h RowsSource): items that are one range of each of two id arrays.  An item carries
+// its own geometry; a row's first id is a B id.
+struct PairsSource {
+    static constexpr bool HAS_TYPE = true;
+    PairsSpec spec;
+    const int32_t *ids_a, *ids_b; int64_t len_a, len_b; const int64_t *off_a, *off_b;      // pair q = A: ids_a[off_a[q] .. off_a[q+1]), B likewise
+
+    struct Item { const int32_t *seq_a, *seq_b; int64_t nb; PairGeom g; bool bad; };
+    typedef PairRow Row;
+
+    BF_HD bool valid() const { return len_a >= 0 && len_b >= 0 && off_a && off_b && (len_a == 0 || ids_a) && (len_b == 0 || ids_b); }
+    BF_HD Item load(int64_t q) const
+    {
+        Item it;
+        bool bad_a, bad_b;
+        const int64_t a0 = off_a[q], b0 = off_b[q];
+        const int64_t na = rows_seq_len(a0, off_a[q + 1], len_a, &bad_a);
+        it.nb = rows_seq_len(b0, off_b[q + 1], len_b, &bad_b);
+        it.seq_a = ids_a + (bad_a ? 0 : a0); it.seq_b = ids_b + (bad_b ? 0 : b0);
+        it.g = pairs_geom(spec, na, it.nb);
+        it.bad = bad_a || bad_b;
+        return it;
+    }
+    BF_HD int32_t count(const Item &it, bool *saturated) const { return pairs_count(spec, it.g, it.nb, saturated); }
+    BF_HD bool one_row() const { return pairs_one_row(spec); }
+    BF_HD int64_t first(const Item &it, int64_t k) const { return spec.mode == 0 ? k * it.g.step : 0; }
+    BF_HD Row row(const Item &it, int64_t first) const { return pairs_row(spec, it.g, first, it.nb); }
+    BF_HD int32_t cell(const Item &it, const Row &w, int j, uint8_t *mask, uint8_t *type) const
+    {
+        return pairs_cell_value(spec, pairs_cell(w, j), it.seq_a, it.seq_b, mask, type);
+    }
+};
+
 } // namespace bfa

@@ -104,4 +104,41 @@ BF_HD int64_t rows_find_seq(const int64_t *row_off, int64_t nseq, int64_t r)
     return lo;
 }
 
+// The rows stage's source, as bf_rowstage_body.h asks for one: items that are single ranges of one id array.  What a source supplies:
+//   HAS_TYPE       whether a type plane exists
+//   valid()        false = the arguments are refused (BF_E_ARG)
+//   load(q)        item q: what the other calls need of it, `bad` = a range outside its array or decreasing offsets (read as empty)
+//   count(it)      its rows, saturating at INT32_MAX
+//   one_row()      one row per item is certain whatever the lengths: row r is item r and starts at the item's first id
+//   first(it, k)   the first id of the item's row k
+//   row(it, first) that row laid out once for all of its cells
+//   cell(it, w, j) the id, the mask byte and the type byte of its cell j
+struct RowsSource {
+    static constexpr bool HAS_TYPE = false;
+    RowsSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off;      // sequence q = ids[id_off[q] .. id_off[q+1])
+
+    struct Item { const int32_t *seq; int64_t n; bool bad; };
+    struct Row { int64_t first; };
+
+    BF_HD bool valid() const { return ids_len >= 0 && id_off && (ids_len == 0 || ids); }
+    BF_HD Item load(int64_t q) const
+    {
+        Item it;
+        const int64_t b = id_off[q];
+        it.n = rows_seq_len(b, id_off[q + 1], ids_len, &it.bad);
+        it.seq = ids + (it.bad ? 0 : b);
+        return it;
+    }
+    BF_HD int32_t count(const Item &it, bool *saturated) const { return rows_count(spec, it.n, saturated); }
+    BF_HD constexpr bool one_row() const { return false; }
+    BF_HD int64_t first(const Item &, int64_t k) const { return k * spec.step; }
+    BF_HD Row row(const Item &, int64_t first) const { return Row{first}; }
+    BF_HD int32_t cell(const Item &it, const Row &w, int j, uint8_t *mask, uint8_t *type) const
+    {
+        *type = 0;
+        return rows_cell_value(spec, rows_cell(spec, w.first, it.n, j), it.seq, mask);
+    }
+};
+
 } // namespace bfa

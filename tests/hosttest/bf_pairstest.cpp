@@ -1,24 +1,12 @@
 // bf_pairstest.cpp -- TEST-ONLY: the pair-row logic of IdsToPairRowsBatch (blingfire_amd/csrc/bf_pairs.h) compiled for the host and driven
-// sequentially, the way bf_kernels_pairs.hip drives it on the device: a count per pair from its own geometry, a scan, the pair and first B id
-// of every row below the capacity, then every cell of those rows on its own, with the geometry taken from the offsets again.  With
-// BF_PAIRSTEST_MAIN the file is a program of its own that runs the parameter table over exactly sized heap arrays (tests build it with
-// -fsanitize=address,undefined).
+// sequentially, the way the kernels drive it on the device (bf_rowstagetest.h).  With BF_PAIRSTEST_MAIN the file is a program of its own that
+// runs the parameter table over exactly sized heap arrays (tests build it with -fsanitize=address,undefined).
 #include <stdint.h>
 #include <vector>
+#include "bf_rowstagetest.h"
 #include "../../blingfire_amd/csrc/bf_pairs.h"
 
 using namespace bfa;
-
-namespace {
-struct Side { const int32_t *seq; int64_t n; bool bad; };
-Side side(const int32_t *ids, int64_t len, const int64_t *off, int64_t q)
-{
-    Side d;
-    d.n = rows_seq_len(off[q], off[q + 1], len, &d.bad);
-    d.seq = ids + (d.bad ? 0 : off[q]);
-    return d;
-}
-}
 
 extern "C" {
 
@@ -31,38 +19,7 @@ int64_t bft_pair_rows_batch(const int32_t *ids_a, int64_t len_a, const int64_t *
     PairsSpec sp;
     *status = 0;
     if (!pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows, flags, &sp) || nseq < 0 || len_a < 0 || len_b < 0 || rows_cap < 0) return -1;
-    row_off[0] = 0;
-    for (int64_t q = 0; q < nseq; ++q) {
-        const Side a = side(ids_a, len_a, off_a, q), b = side(ids_b, len_b, off_b, q);
-        bool sat;
-        row_off[q + 1] = row_off[q] + pairs_count(sp, pairs_geom(sp, a.n, b.n), b.n, &sat);
-        if (a.bad || b.bad) *status |= 8;
-        if (sat) *status |= 1;
-    }
-    const int64_t total = row_off[nseq];
-    if (!rows && !mask && !type && !row_seq && !row_first) return total;
-    if (total > rows_cap) *status |= 1;
-    const int64_t nrows = total < rows_cap ? total : rows_cap;
-    for (int64_t r = 0; r < nrows; ++r) {
-        const int64_t q = pairs_one_row(sp) ? r : rows_find_seq(row_off, nseq, r);
-        const Side a = side(ids_a, len_a, off_a, q), b = side(ids_b, len_b, off_b, q);
-        const PairGeom g = pairs_geom(sp, a.n, b.n);
-        const int64_t first = sp.mode == 0 ? (r - row_off[q]) * g.step : 0;
-        if (row_seq) row_seq[r] = (int32_t)q;
-        bool fsat;
-        const int32_t first32 = rows_first_i32(first, &fsat);
-        if (row_first) row_first[r] = first32;
-        if (fsat) *status |= 1;
-        const PairRow w = pairs_row(sp, g, first, b.n);
-        for (int j = 0; j < row_len && (rows || mask || type); ++j) {
-            uint8_t m, t;
-            const int32_t v = pairs_cell_value(sp, pairs_cell(w, j), a.seq, b.seq, &m, &t);
-            if (rows) rows[r * row_len + j] = v;
-            if (mask) mask[r * row_len + j] = m;
-            if (type) type[r * row_len + j] = t;
-        }
-    }
-    return total;
+    return bft_rowstage(PairsSource{sp, ids_a, ids_b, len_a, len_b, off_a, off_b}, nseq, rows, mask, type, row_seq, row_first, rows_cap, row_off, status);
 }
 
 } // extern "C"

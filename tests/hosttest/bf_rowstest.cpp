@@ -1,10 +1,9 @@
 // bf_rowstest.cpp -- TEST-ONLY: the row logic of IdsToRowsBatch (blingfire_amd/csrc/bf_rows.h) compiled for the host and driven sequentially,
-// the way bf_kernels_rows.hip drives it on the device: a count per sequence, a scan, the sequence and first id of every row below the
-// capacity, then every cell of those rows on its own.  With BF_ROWSTEST_MAIN the file is a program of its own that runs the parameter
+// the way the kernels drive it on the device (bf_rowstagetest.h).  With BF_ROWSTEST_MAIN the file is a program of its own that runs the parameter
 // table over exactly sized heap arrays (tests build it with -fsanitize=address,undefined).
 #include <stdint.h>
 #include <vector>
-#include "../../blingfire_amd/csrc/bf_rows.h"
+#include "bf_rowstagetest.h"
 
 using namespace bfa;
 
@@ -19,36 +18,7 @@ int64_t bft_rows_batch(const int32_t *ids, int64_t ids_len, const int64_t *id_of
     RowsSpec sp;
     *status = 0;
     if (!rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows, flags, &sp) || nseq < 0 || ids_len < 0 || rows_cap < 0) return -1;
-    row_off[0] = 0;
-    for (int64_t q = 0; q < nseq; ++q) {
-        bool bad, sat;
-        const int64_t n = rows_seq_len(id_off[q], id_off[q + 1], ids_len, &bad);
-        row_off[q + 1] = row_off[q] + rows_count(sp, n, &sat);
-        if (bad) *status |= 8;
-        if (sat) *status |= 1;
-    }
-    const int64_t total = row_off[nseq];
-    if (!rows && !mask && !row_seq && !row_first) return total;
-    if (total > rows_cap) *status |= 1;
-    const int64_t nrows = total < rows_cap ? total : rows_cap;
-    for (int64_t r = 0; r < nrows; ++r) {
-        const int64_t q = rows_find_seq(row_off, nseq, r), first = (r - row_off[q]) * sp.step;
-        if (row_seq) row_seq[r] = (int32_t)q;
-        bool fsat;
-        const int32_t first32 = rows_first_i32(first, &fsat);
-        if (row_first) row_first[r] = first32;
-        if (fsat) *status |= 1;
-        bool bad;
-        const int64_t n = rows_seq_len(id_off[q], id_off[q + 1], ids_len, &bad);
-        const int32_t *seq = ids + (bad ? 0 : id_off[q]);
-        for (int j = 0; j < row_len && (rows || mask); ++j) {
-            uint8_t m;
-            const int32_t v = rows_cell_value(sp, rows_cell(sp, first, n, j), seq, &m);
-            if (rows) rows[r * row_len + j] = v;
-            if (mask) mask[r * row_len + j] = m;
-        }
-    }
-    return total;
+    return bft_rowstage(RowsSource{sp, ids, ids_len, id_off}, nseq, rows, mask, nullptr, row_seq, row_first, rows_cap, row_off, status);
 }
 
 } // extern "C"

@@ -2,7 +2,7 @@
 the element type and nothing else, says that d_text needs no padding and may be d_text + first_byte of a larger buffer, and that no output is written
 at or past its capacity.  Every other GPU test passes the base of a fresh torch tensor for every pointer, so the code the kernels keep for these
 callers never ran there: k_prep_wp in place of k_prep_wp_flat + k_prep_wp_docs for a text that is not 16-byte aligned (launch_prep_wp), the head /
-oq / rows_ok logic of k_wp_merge and its element-wise path for starts_out / ends_out that are not aligned like ids_out, the wide stores k_rows_fill
+oq / rows_ok logic of k_wp_merge and its element-wise path for starts_out / ends_out that are not aligned like ids_out, the wide stores k_rowstage_fill
 chooses from the alignment of rows / mask, and the end-of-text special cases (wf_units' b16, k_prep_wp_flat's last chunk, the nb < 8 tails of
 load_chunk and k_prep_sp8) that keep a kernel from looking at what lies behind total_bytes.
 

@@ -128,6 +128,16 @@ def test_2_capacity(h, par):
     r = bf.lib().IdsToRowsBatch(vp(h), ids.ctypes.data, off.ctypes.data, len(off) - 1, L, cls_id, sep_id, rc.PAD, stride, max_rows, 1 if pad_left else 0,
                                 None, None, None, None, 0, r_off.ctypes.data)
     assert r == total and np.array_equal(r_off, want[4])                  # the size query needs no capacity
+    # each output alone, then each left out in turn: what was asked for equals the restatement, nothing else is touched
+    cans = (CANARY32, CANARY8, CANARY32, CANARY32)
+    for asked in [tuple(i == k for i in range(4)) for k in range(4)] + [tuple(i != k for i in range(4)) for k in range(4)]:
+        outs = [np.full((total, L), CANARY32, dtype=np.int32), np.full((total, L), CANARY8, dtype=np.uint8),
+                np.full(total, CANARY32, dtype=np.int32), np.full(total, CANARY32, dtype=np.int32)]
+        r_off = np.full(len(off), -1, dtype=np.int64)
+        r = bf.lib().IdsToRowsBatch(vp(h), ids.ctypes.data, off.ctypes.data, len(off) - 1, L, cls_id, sep_id, rc.PAD, stride, max_rows, 1 if pad_left else 0,
+                                    *[o.ctypes.data if a else None for o, a in zip(outs, asked)], total, r_off.ctypes.data)
+        assert r == total and np.array_equal(r_off, want[4]), (par, asked)
+        assert all(np.array_equal(o, want[i]) if asked[i] else (o == cans[i]).all() for i, o in enumerate(outs)), (par, asked)
 
 
 # ---- 3. alignment
