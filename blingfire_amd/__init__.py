@@ -97,6 +97,10 @@ def lib():
         L.IdsToPairRowsBatchDevice.restype = c_int
         L.IdsToPairRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [
             c_int64, c_void_p, c_void_p]
+        L.IdsToPackedRowsBatch.restype = c_int64
+        L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
+        L.IdsToPackedRowsBatchDevice.restype = c_int
+        L.IdsToPackedRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64] + [c_void_p] * 4
         L.BfLastKernelMs.restype = c_int
         L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
         L.BfLastStatus.restype = c_int
@@ -625,6 +629,81 @@ def encode_pairs_batch(h, docs_a, docs_b, L, cls_id, sep_id, pad_id, unk=0, mode
         d.append(torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda())
         d.append(torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda())
     return encode_pairs_batch_device(h, d[0], d[1], d[2], d[3], L, cls_id, sep_id, pad_id, unk, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+
+
+def ids_to_packed_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0):
+    """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> PACKED model inputs (IdsToPackedRowsBatch): several sequences share a
+    row, filled greedily and in order; a sequence longer than a row is truncated, none is split.  cls_id / sep_id None = no such special.
+    Returns (rows int32[R, L], seg int32[R, L], pos int32[R, L], row_first_seq int32[R + 1], seq_row int32[nseq], seq_col int32[nseq]):
+    seg numbers the sequences of a row from 1 (0 = padding), pos restarts at every sequence, row r holds the sequences
+    [row_first_seq[r], row_first_seq[r + 1]), and sequence q begins at cell seq_col[q] of row seq_row[q]."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
+    nseq = len(id_off) - 1
+    fn = lib().IdsToPackedRowsBatch
+    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
+    seq_row = np.empty(nseq, dtype=np.int32)
+    seq_col = np.empty(nseq, dtype=np.int32)
+    n = fn(*pre, None, None, None, None, 0, seq_row.ctypes.data, seq_col.ctypes.data)
+    if n < 0:
+        raise RuntimeError("IdsToPackedRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    planes = [np.empty((n, L), dtype=np.int32) for _ in range(3)]
+    first = np.empty(n + 1, dtype=np.int32)
+    r = fn(*pre, *[p.ctypes.data for p in planes], first.ctypes.data, n, seq_row.ctypes.data, seq_col.ctypes.data)
+    if r != n:
+        raise RuntimeError("IdsToPackedRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return (*planes, first, seq_row, seq_col)
+
+
+def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, rows_cap=None, stream=None):
+    """Device-resident ids_to_packed_rows_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are)
+    -> (rows, seg, pos, row_first_seq, seq_row, seq_col, nrows) as tensors on that device, enqueued on torch's current stream (or `stream`);
+    nrows is int64[1], the row count R.  rows_cap None: a size query whose R is read back (one synchronisation), the tensors have R rows.
+    With a rows_cap of the caller's nothing is read back: the planes have rows_cap rows and row_first_seq rows_cap + 1 entries, of which
+    min(R, rows_cap) rows and one entry more are written; rows beyond it are dropped (BfLastStatus bit 0)."""
+    import torch
+    dev = d_ids.device
+    nseq = d_id_off.numel() - 1
+    fn = lib().IdsToPackedRowsBatchDevice
+    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
+    nrows = torch.empty(1, dtype=torch.int64, device=dev)
+
+    def call(outs, cap, seq):
+        r = fn(*pre, *outs, cap, *seq, nrows.data_ptr(), s)
+        if r != 0:
+            raise RuntimeError("IdsToPackedRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    if rows_cap is None:
+        call([None] * 4, 0, [None] * 2)
+        if stream is not None:
+            torch.cuda.synchronize(dev)                   # (a raw stream handle: nothing finer to wait on)
+        rows_cap = int(nrows.item())
+    planes = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(3)]
+    first = torch.empty(rows_cap + 1, dtype=torch.int32, device=dev)
+    seq = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(2)]
+    call([t.data_ptr() for t in planes] + [first.data_ptr()], rows_cap, [t.data_ptr() for t in seq])
+    return (*planes, first, *seq, nrows)
+
+
+def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None):
+    """Text in HBM -> packed tensors a model takes, nothing on the host: text_to_ids_batch_device (every document tokenised up to the ids
+    a row can hold) and ids_to_packed_rows_batch_device on one stream.  Returns what ids_to_packed_rows_batch_device returns; with a
+    rows_cap of the caller's nothing is read back."""
+    body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
+    if body < 1:
+        raise ValueError("encode_packed_batch_device: L leaves no room for ids")
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, body, unk)
+    return ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, rows_cap)
+
+
+def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None):
+    """encode_packed_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed into one buffer, uploaded with
+    torch to the current device, encoded there."""
+    import torch
+    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
+    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
+    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
+    return encode_packed_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
 
 
 def dict_get_info_batch(h, keys):

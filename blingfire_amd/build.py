@@ -41,8 +41,8 @@ def hipcc():
 
 
 def build_product(force=False):
-    """the product: seven translation units compiled side by side (the two large kernel files are most of the time), then linked"""
-    names = ("bf_kernels.hip", "bf_kernels_sp.hip", "bf_kernels_w2h.hip", "bf_kernels_rows.hip", "bf_kernels_pairs.hip", "bf_capi.cpp", "bf_model.cpp")
+    """the product: eight translation units compiled side by side (the two large kernel files are most of the time), then linked"""
+    names = ("bf_kernels.hip", "bf_kernels_sp.hip", "bf_kernels_w2h.hip", "bf_kernels_rows.hip", "bf_kernels_pairs.hip", "bf_kernels_packed.hip", "bf_capi.cpp", "bf_model.cpp")
     srcs = [os.path.join(CSRC, f) for f in names]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
         os.path.join(ROOT, "include", "blingfiretokdll_amd.h"), os.path.join(CSRC, "exports.map"), os.path.join(ROOT, "models", "wbd.bin"), os.path.join(ROOT, "models", "sbd.bin")]
@@ -104,7 +104,8 @@ def build_test_infra(force=False):
     ht = os.path.join(ROOT, "tests", "hosttest", "libbf_hosttest.so")
     ht_src = [os.path.join(ROOT, "tests", "hosttest", "bf_hosttest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_wavetest.cpp"),
               os.path.join(ROOT, "tests", "hosttest", "bf_w2htest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_rowstest.cpp"),
-              os.path.join(ROOT, "tests", "hosttest", "bf_pairstest.cpp"), os.path.join(CSRC, "bf_model.cpp")]
+              os.path.join(ROOT, "tests", "hosttest", "bf_pairstest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_packedtest.cpp"),
+              os.path.join(CSRC, "bf_model.cpp")]
     ht_dep = ht_src + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(odir, "bf_oracle.c"),
                                                                                               os.path.join(ROOT, "tests", "hosttest", "wave_emu.h"), os.path.join(ROOT, "tests", "hosttest", "hosttest.h")]
     if force or _newer(ht, ht_dep):

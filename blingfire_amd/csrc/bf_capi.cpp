@@ -105,7 +105,7 @@ struct PinBuf {
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device, and in run_row_stage_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            size pass of run_w2h_device, in run_row_stage_device and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
 //                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
@@ -201,6 +201,7 @@ struct Handle {
     DevBuf t_w2h, t_w2h_pats, t_w2h_l1, t_w2h_pages;             // [w2h]: pattern automaton, pattern pool, code point -> class (bf_w2h.h)
     DevBuf w_hcls, w_hnch, w_hsrc;                               // WordHyphenationBatch: position stream, characters and source bytes per word
     DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch / IdsToPairRowsBatch: sequence (pair) and first id of every row, where the caller takes neither
+    DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -1440,6 +1441,93 @@ int64_t run_pairs_host(Handle *h, const int32_t *ids_a, const int64_t *off_a, co
         return run_row_stage_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), s, "IdsToPairRows kernels"); });
 }
 
+// IdsToPackedRowsBatch on device buffers (bf_kernels_packed.hip): widths, scan, next, the doubling rounds, the scan of the marks, rows, then -- for
+// the outputs the caller takes -- cols and fill.  The launches depend on nseq and on which outputs are taken, never on the data.
+bool reserve_packed_workspaces(Handle *h, int64_t nseq)
+{
+    const size_t n = (size_t)nseq + 2;
+    return h->w_counts.reserve(n * 4) && h->w_bsums.reserve((size_t)(scan_nblocks(nseq) + 1) * 8) && h->w_pkW.reserve(n * 8) && h->w_pkjmp[0].reserve(n * 4) &&
+           h->w_pkjmp[1].reserve(n * 4) && h->w_pkmark.reserve(n * 4) && h->w_pkmoff.reserve(n * 8) && h->w_pkf.reserve(n * 4);
+}
+
+int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, int32_t *d_rows, int32_t *d_seg,
+                      int32_t *d_pos, int32_t *d_row_first, int64_t rows_cap, int32_t *d_seq_row, int32_t *d_seq_col, int64_t *d_nrows, hipStream_t s)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || ids_len < 0 || !d_id_off || !d_nrows || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    if (!reserve_packed_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    PackedParams p;
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
+    p.widths = h->w_counts.as<int32_t>(); p.W = h->w_pkW.as<int64_t>(); p.jmp[0] = h->w_pkjmp[0].as<int32_t>(); p.jmp[1] = h->w_pkjmp[1].as<int32_t>();
+    p.mark = h->w_pkmark.as<int32_t>(); p.mark_off = h->w_pkmoff.as<int64_t>(); p.f = h->w_pkf.as<int32_t>();
+    p.rows_cap = rows_cap; p.rows = d_rows; p.seg = d_seg; p.pos = d_pos; p.row_first = d_row_first; p.seq_row = d_seq_row; p.seq_col = d_seq_col; p.nrows = d_nrows;
+    // the events BfLastKernelMs reads: [0] widths + scan, [1] next + the doubling rounds, [5] the rounds alone, [2] the scan of the marks, rows and cols, [3] fill
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (nseq > 0) launch_packed_widths(p, s);
+    scan_counts(h, nseq, p.W, s);
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    if (nseq > 0) launch_packed_next(p, s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    if (nseq > 0) for (int k = 0, rounds = packed_rounds(nseq); k < rounds; ++k) launch_packed_double(p, k, s);
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    launch_scan(ScanParams{p.mark, nseq, p.mark_off, h->w_bsums.as<int64_t>(), scan_nblocks(nseq)}, s);
+    launch_packed_rows(p, s);
+    if (nseq > 0 && d_seq_col) launch_packed_cols(p, s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    if (nseq > 0 && rows_cap > 0 && (d_rows || d_seg || d_pos)) launch_packed_fill(p, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "IdsToPackedRows kernels") ? 0 : BF_E_DEVICE;
+}
+
+// IdsToPackedRowsBatch on host buffers: the ids through stage_ragged, a size pass that also answers the per-sequence outputs, the capacity check,
+// the fill pass.  As in two_pass_host, whatever ends the call early after work was queued synchronises the stream first.
+int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const PackedSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
+                        int32_t *row_first_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || !id_off) return BF_E_ARG;
+    const int64_t ids_len = host_side_len(id_off, nseq);
+    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    const size_t seq_bytes = (size_t)nseq * 4;
+    if (!h->w_idoff.reserve(16) || !h->w_starts.reserve(seq_bytes + 16) || !h->w_ends.reserve(seq_bytes + 16)) return BF_E_DEVICE;
+    Staged st;
+    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    auto fail = [s](int64_t e) { (void)hipStreamSynchronize(s); return e; };
+    auto pass = [&](int32_t *d_rows, int32_t *d_seg, int32_t *d_pos, int32_t *d_first, int64_t cap) {
+        return run_packed_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, d_rows, d_seg, d_pos, d_first, cap,
+                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s);
+    };
+    rc = pass(nullptr, nullptr, nullptr, nullptr, 0);
+    if (rc != 0) return fail(rc);
+    int64_t R = 0;
+    if (!hip_ok(hipMemcpyAsync(&R, h->w_idoff.p, 8, hipMemcpyDeviceToHost, s), "D2H row count") ||
+        (seq_row_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_row_out, h->w_starts.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence rows")) ||
+        (seq_col_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_col_out, h->w_ends.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence cells"))) return fail(BF_E_DEVICE);
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    if (!rows_out && !seg_out && !pos_out && !row_first_out) return R;         // (a size query needs no capacity)
+    if (R > rows_cap) return BF_E_CAPACITY;
+    const size_t plane_bytes = (size_t)R * (size_t)spec.row_len * 4, first_bytes = (size_t)(R + 1) * 4;
+    struct { int32_t *host; DevBuf *dev; size_t bytes; const char *what; } outs[4] = {{rows_out, &h->w_out, plane_bytes, "D2H rows"}, {seg_out, &h->w_vals, plane_bytes, "D2H segments"},
+                                                                                     {pos_out, &h->w_text, plane_bytes, "D2H positions"}, {row_first_out, &h->w_outoff, first_bytes, "D2H row starts"}};
+    int32_t *d_out[4] = {};
+    for (int i = 0; i < 4; ++i) {
+        if (!outs[i].host) continue;
+        if (!outs[i].dev->reserve(outs[i].bytes + 16)) return BF_E_DEVICE;
+        d_out[i] = outs[i].dev->as<int32_t>();
+    }
+    rc = pass(d_out[0], d_out[1], d_out[2], d_out[3], R);
+    if (rc != 0) return fail(rc);
+    for (const auto &o : outs)
+        if (o.host && o.bytes && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, o.bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
+}
+
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
 bool ensure_dict_tables(Handle *h)
 {
@@ -2102,6 +2190,29 @@ int64_t IdsToPairRowsBatch(void *p, const int32_t *ids_a, const int64_t *off_a, 
     return run_pairs_host(h, ids_a, off_a, ids_b, off_b, nseq, spec, rows_out, mask_out, type_out, row_seq_out, row_first_b_out, rows_cap, row_offsets_out);
 }
 
+/* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */
+int IdsToPackedRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
+                               int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
+                               int32_t *d_seq_row_out, int32_t *d_seq_col_out, int64_t *d_nrows_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    PackedSpec spec;
+    if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_packed_device(h, spec, d_ids, ids_len, d_id_offsets, nseq, d_rows_out, d_seg_out, d_pos_out, d_row_first_seq_out, rows_cap, d_seq_row_out, d_seq_col_out,
+                             d_nrows_out, (hipStream_t)stream);
+}
+
+int64_t IdsToPackedRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                             int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *row_first_seq_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
+{
+    Handle *h = as_handle(p);
+    PackedSpec spec;
+    if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec)) return BF_E_ARG;
+    return run_packed_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, row_first_seq_out, rows_cap, seq_row_out, seq_col_out);
+}
+
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */
 int DictGetInfoBatchDevice(void *p, const int32_t *d_keys, const int64_t *d_key_offsets, int64_t nkeys, int32_t *d_ret_out, int32_t *d_info_ids_out,
                            int32_t *d_values_out, int64_t values_cap, int64_t *d_value_offsets_out, void *stream)
@@ -2199,6 +2310,7 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     if (!reserve_rows_workspaces(h, max_docs)) return BF_E_DEVICE;                                   // IdsToRowsBatchDevice, any handle: documents = sequences
+    if (!reserve_packed_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToPackedRowsBatchDevice, any handle
     if (h->m.kind == KIND_I2W) return 0;                                                             // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words
     if (h->m.kind == KIND_W2H) return 0;

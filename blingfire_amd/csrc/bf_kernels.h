@@ -11,6 +11,7 @@
 #include "bf_w2h.h"
 #include "bf_rows.h"
 #include "bf_pairs.h"
+#include "bf_packed.h"
 
 namespace bfa {
 
@@ -275,6 +276,30 @@ template <class S> void launch_rowstage_count(const RowStageParams<S> &p, hipStr
 template <class S> void launch_rowstage_map(const RowStageParams<S> &p, hipStream_t s);
 template <class S> void launch_rowstage_fill(const RowStageParams<S> &p, hipStream_t s);
 unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU (bf_kernels_rows.hip)
+
+// IdsToPackedRowsBatch (additive; bf_packed.h has the lane code, bf_kernels_packed.hip the kernels): several sequences per row, with a segment
+// and a position plane.  Every workspace array has nseq + 1 entries (index nseq = the end of the chain) unless noted.
+struct PackedParams {
+    PackedSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    int32_t *widths;             // [nseq] unit widths, scanned into W
+    int64_t *W;                  // exclusive scan of the widths
+    int32_t *jmp[2];             // next(s), squared round by round from one buffer into the other
+    int32_t *mark;               // 1 = a row starts at this sequence
+    int64_t *mark_off;           // exclusive scan of mark[0 .. nseq): rows in front of a sequence's row start; mark_off[nseq] = R
+    int32_t *f;                  // the sequence every row starts at, f[R] = nseq
+    int64_t rows_cap;            // no row r >= rows_cap of a plane is written, no entry past min(R, rows_cap) of row_first
+    int32_t *rows, *seg, *pos;   // [rows_cap * row_len] each, any may be NULL
+    int32_t *row_first;          // [rows_cap + 1], may be NULL
+    int32_t *seq_row, *seq_col;  // [nseq] each, either may be NULL
+    int64_t *nrows;              // [1]
+};
+void launch_packed_widths(const PackedParams &p, hipStream_t s);                // lane per sequence: widths, status bit 3
+void launch_packed_next(const PackedParams &p, hipStream_t s);                  // lane per sequence: jmp[0] = next, mark = {0}
+void launch_packed_double(const PackedParams &p, int round, hipStream_t s);     // one doubling round: reads jmp[round & 1], writes the other
+void launch_packed_rows(const PackedParams &p, hipStream_t s);                  // behind the scan of the marks: f, row_first, seq_row, nrows, status bit 0
+void launch_packed_cols(const PackedParams &p, hipStream_t s);                  // seq_col
+void launch_packed_fill(const PackedParams &p, hipStream_t s);                  // the three planes
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

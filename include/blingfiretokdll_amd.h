@@ -218,6 +218,48 @@ BF_API int64_t IdsToPairRowsBatch(void *ModelPtr, const int32_t *ids_a, const in
                            int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out,
                            int64_t rows_cap, int64_t *row_offsets_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): PACKED rows -- several sequences share a row, a segment
+ * plane keeps a model's attention block-diagonal and a position plane restarts at every sequence.  Where IdsToRowsBatch pads every sequence
+ * to a row of its own, this fills rows greedily and in order.
+ * Units.  Sequence q of nseq = ids[off[q] .. off[q+1]), n_q ids; a range outside [0, ids_len] or with decreasing offsets is read as empty and
+ * sets BfLastStatus bit 3, exactly as in IdsToRowsBatchDevice.  lead = (cls_id >= 0), trail = (sep_id >= 0), body = row_len - lead - trail.
+ * Unit q is [cls_id] ids[0 .. k_q) [sep_id] with k_q = min(n_q, body): a sequence longer than a row is truncated silently, like
+ * max_rows_per_seq = 1 of IdsToRowsBatch (callers who need windows use that call).  Its width is w_q = lead + k_q + trail, 0 <= w_q <= row_len.
+ * A unit is never split across rows.  An empty sequence contributes only its specials; without specials its unit has width 0.
+ * Rows.  With W[q] = w_0 + ... + w_{q-1} (int64, W[0] = 0): row 0 starts at sequence f[0] = 0; a row that starts at sequence s holds the
+ * sequences [s, next(s)), next(s) = max{ e in (s, nseq] : W[e] - W[s] <= row_len }, and the next row starts at next(s); R is the number of rows
+ * until the chain reaches nseq.  So next(s) > s always; units of width 0 stay in the row in front of them; every row but row 0 begins with a unit
+ * of positive width; nseq > 0 gives R >= 1 even when every unit has width 0 (one row of padding); nseq = 0 gives R = 0; and a row that is
+ * neither the last nor followed only by units of width 0 cannot take the next unit (greedy maximality).
+ * Cells of row r.  Cell j < W[f[r+1]] - W[f[r]] belongs to unit q = the last q in [f[r], f[r+1]) with W[q] - W[f[r]] <= j, at place
+ * x = j - (W[q] - W[f[r]]) of the unit.  rows: cls_id at x = 0 when lead, sep_id at x = w_q - 1 when trail, else ids[off[q] + x - lead].
+ * seg: q - f[r] + 1 -- 1-based within the row, units of width 0 are counted, so f[r] + seg - 1 is the sequence.  pos: x.  Every cell behind the
+ * last unit is padding: rows = pad_id, seg = 0, pos = 0 (a mask is seg != 0).  Padding is always on the right.
+ * Per-row and per-sequence outputs.  d_row_first_seq_out[rows_cap + 1] holds f[r] for r = 0 .. min(R, rows_cap), with f[R] = nseq: the last
+ * entry written is nseq when every row fit (with nseq = 0 that is entry 0).  d_seq_row_out[nseq] is the row of sequence q, d_seq_col_out[nseq]
+ * is W[q] - W[f[row]], the cell where its unit begins; both are complete whatever rows_cap is.  d_nrows_out[1] is R.
+ * BF_E_ARG for row_len outside 1 .. 1 << 20, body < 1, flags != 0 (the flag word is reserved), nseq < 0 or nseq > INT32_MAX, rows_cap < 0,
+ * ids_len < 0, a NULL ModelPtr (any live handle of any kind serves, as for IdsToRowsBatch: it lends its device, workspaces and status word),
+ * a NULL d_id_offsets or d_nrows_out, and a NULL d_ids with ids_len > 0.
+ * Device form: every output but d_nrows_out may be NULL; with the three planes and d_row_first_seq_out all NULL it is a size query.  No row
+ * r >= rows_cap of any plane is written, no entry past min(R, rows_cap) of d_row_first_seq_out; rows dropped that way from an output the caller
+ * takes set BfLastStatus bit 0 (the call clears the status word first).  It enqueues on `stream` (a hipStream_t), does not synchronise and
+ * returns 0 or BF_E_*.  After BfReserve(h, max_docs >= nseq, ...) it allocates nothing.  The kernels it launches depend on nseq and on which
+ * outputs are taken, never on the data (the row starts are found by ceil(log2(nseq + 1)) rounds of pointer doubling over the whole batch, not
+ * by a walk), and nothing is read back.  Every pointer needs only the natural alignment of its type;
+ * planes that are all aligned to 16 bytes, with row_len % 4 == 0, take the wide stores.
+ * Host form: stages the ids like IdsToRowsBatch (it reads them from id_offsets[0] to the largest offset; id_offsets[0] < 0 = BF_E_ARG) and
+ * returns R.  With all four row outputs (rows, seg, pos, row_first_seq) NULL it is a size query, whatever rows_cap is; otherwise, when
+ * R > rows_cap, it returns BF_E_CAPACITY with seq_row_out / seq_col_out complete and nothing else written. */
+BF_API int IdsToPackedRowsBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                               int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                               int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
+                               int32_t *d_seq_row_out, int32_t *d_seq_col_out, int64_t *d_nrows_out, void *stream);
+BF_API int64_t IdsToPackedRowsBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                             int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                             int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *row_first_seq_out, int64_t rows_cap,
+                             int32_t *seq_row_out, int32_t *seq_col_out);
+
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
 
@@ -309,7 +351,8 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
 /* Per-kernel GPU time of the last batch call on this handle, measured with HIP events recorded on the
  * call's own stream.  Synchronises with those events.  Fills up to n floats (milliseconds):
  * [0] prep (decode+normalise+classify)  [1] tokenise (lexer / segmenter)  [2] scan  [3] compact  [4] total  [5] the dominant kernel of the
- * tokenise segment alone.
+ * tokenise segment alone.  After IdsToPackedRowsBatchDevice: [0] widths + scan, [1] next + the doubling rounds, [2] the scan of the marks and the
+ * per-row / per-sequence outputs, [3] the fill of the planes, [4] total, [5] the doubling rounds alone.
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
@@ -333,8 +376,8 @@ BF_API int BfModelKind(void *ModelPtr);
 /* Optional: size every workspace of the handle for batches of up to max_docs documents / max_bytes bytes of text now, so that
  * later ...BatchDevice calls of that size allocate nothing (workspaces only ever grow; growing means hipMalloc, which
  * synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
- * Every kind of handle has the workspaces of IdsToRowsBatchDevice and IdsToPairRowsBatchDevice (the same ones) sized for max_docs sequences
- * or pairs (an [i2w]-only handle has no others).
+ * Every kind of handle has the workspaces of IdsToRowsBatchDevice and IdsToPairRowsBatchDevice (the same ones) and those of
+ * IdsToPackedRowsBatchDevice (about 36 bytes per sequence) sized for max_docs sequences or pairs (an [i2w]-only handle has no others).
  * Returns 0 or BF_E_*. */
 BF_API int BfReserve(void *ModelPtr, int64_t max_docs, int64_t max_bytes, int want_offsets);
 /* BPE models: the size of the pool from which documents with very many candidate arcs claim their working memory (about 16 bytes per
