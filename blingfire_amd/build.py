@@ -102,12 +102,11 @@ def build_test_infra(force=False):
         if os.path.exists(src) and (force or _newer(out, [src])):
             _run([hipcc(), "--offload-arch=gfx950", "-O2", "-w", "-o", out, src])
     ht = os.path.join(ROOT, "tests", "hosttest", "libbf_hosttest.so")
-    ht_src = [os.path.join(ROOT, "tests", "hosttest", "bf_hosttest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_wavetest.cpp"),
-              os.path.join(ROOT, "tests", "hosttest", "bf_w2htest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_rowstest.cpp"),
-              os.path.join(ROOT, "tests", "hosttest", "bf_pairstest.cpp"), os.path.join(ROOT, "tests", "hosttest", "bf_packedtest.cpp"),
-              os.path.join(CSRC, "bf_model.cpp")]
-    ht_dep = ht_src + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(odir, "bf_oracle.c"),
-                                                                                              os.path.join(ROOT, "tests", "hosttest", "wave_emu.h"), os.path.join(ROOT, "tests", "hosttest", "hosttest.h")]
+    # the host test library is every unit tests/hosttest holds (bf_*test.cpp): a new one needs no line here, and the library is built from what the tests beside it are
+    htdir = os.path.join(ROOT, "tests", "hosttest")
+    ht_src = [os.path.join(htdir, f) for f in sorted(os.listdir(htdir)) if f.startswith("bf_") and f.endswith("test.cpp")] + [os.path.join(CSRC, "bf_model.cpp")]
+    ht_dep = ht_src + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(odir, "bf_oracle.c")] + [
+        os.path.join(htdir, f) for f in os.listdir(htdir) if f.endswith(".h")]
     if force or _newer(ht, ht_dep):
         obj = os.path.join(ROOT, "tests", "hosttest", "bf_oracle.o")
         _run(["gcc", "-O2", "-std=c99", "-fPIC", "-c", os.path.join(odir, "bf_oracle.c"), "-o", obj])

@@ -390,7 +390,7 @@ bool uni_lane_ok(const Model &m) { return m.trie_max_depth > 0 && m.trie_max_dep
 bool use_wave(const Handle *h, bool want_off, int words)
 {
     (void)want_off;                      // the offsets API has an instance of the wave program of its own (bf_wave_body.h OFFS)
-    return h->m.kind == KIND_WP && h->m.wave_ok && !words && (h->variant & 0xff) != 2;
+    return h->m.kind == KIND_WP && h->m.wave_ok && !words && !wp_choice(h->variant).lane_only;
 }
 
 // Batches of a flat-form model (bf_flat.h; every BERT model) that are large enough to fill the device take the flat program: ids, and ids
@@ -398,14 +398,13 @@ bool use_wave(const Handle *h, bool want_off, int words)
 bool use_flat(const Handle *h, bool want_off, int words, int64_t ndocs, int64_t total_bytes)
 {
     if (!use_wave(h, want_off, words) || !h->m.flat_ok || ndocs <= 0) return false;
-    const int v = h->variant & 0xff;
-    if (v == 4) return true;
-    return v == 3 && ndocs >= 1024 && total_bytes >= (1 << 20);
+    const WpChoice c = wp_choice(h->variant);
+    return c.flat_always || (c.flat_by_size && ndocs >= 1024 && total_bytes >= (1 << 20));
 }
 
 // the BPE wave program (bf_bpe_wave_body.h) in front of the lane-per-document kernels, for the models its load-time analysis admits
 // (Model::bpe_wave_ok); BfSetVariant bit 0x40 switches it off (A/B runs against the lane-per-document kernels alone)
-bool use_bpe_wave(const Handle *h, bool want_off) { return h->m.bpe_wave_ok && !want_off && (h->variant & 0x40) == 0; }
+bool use_bpe_wave(const Handle *h, bool want_off) { return h->m.bpe_wave_ok && !want_off && !bpe_wave_knobs(h->variant).off; }
 
 // Words modes (TextToWords / TextToSentences): documents of more than `thresh` characters go through the long-document path
 // (bf_lex.h lex_one_start), which spends about three times the transitions of the lane kernel on a document of short words but spreads
@@ -413,8 +412,8 @@ bool use_bpe_wave(const Handle *h, bool want_off) { return h->m.bpe_wave_ok && !
 // that is much longer than the rest: a lane walks 1.8 us per character when it is the last one running (config 1's 8,396-byte line:
 // 4.9 ms), the chip as a whole 75 ps per character (1 M lines: 3.25 ms), so a document of more than total_bytes / 24,000 characters
 // would hold the batch up (measured on MI355X, profiles/r06_words_*: 10,000 lines 4.6 -> 0.55 ms at 16, 1 M lines 3.25 ms at 128 and
-// 10.2 ms at 16).  BfSetVariant: bit 0x40000000 = off (every document on one lane), bits 12..15 = k > 0: thresh = 8 << k, bit 0x20000000 = a test
-// knob: the triple buffer of the words modes holds n / 8 triples instead of n (so that tests reach the position at which it fills), bit 0x10000000 =
+// 10.2 ms at 16).  BfSetVariant (bf_variant.h WordsKnobs): no_long = off (every document on one lane), thresh_k > 0: thresh = 8 << k, small_triples =
+// a test knob: the triple buffer of the words modes holds n / 8 triples instead of n (so that tests reach the position at which it fills), chunks_40 =
 // another: the workspace has room for 40 chunks only (so that tests reach the documents that do not fit and stay on lanes).
 // The capacities are bounds that hold for any batch of these sizes (a listed document has more than thresh bytes and owns
 // (n + 1 + 63) / 64 chunks) unless that is more than LONG_MAX_CHUNKS: then the documents that do not fit stay on lanes.
@@ -430,19 +429,20 @@ struct LongCaps { int thresh; int64_t docs, chunks; size_t list_off, spec_off, j
 LongCaps long_caps(const Handle *h, int64_t ndocs, int64_t total_bytes, int words)
 {
     LongCaps c{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!words || h->m.kind != KIND_WP || h->m.max_depth < 1 || h->m.lexer_void || (h->variant & 0x40000000) || ndocs <= 0) return c;
-    const int k = (h->variant >> 12) & 0xf;
+    const WordsKnobs wk = words_knobs(h->variant);
+    if (!words || h->m.kind != KIND_WP || h->m.max_depth < 1 || h->m.lexer_void || wk.no_long || ndocs <= 0) return c;
+    const int k = wk.thresh_k;
     c.thresh = k ? (8 << k) : (int)std::min<int64_t>(std::max<int64_t>(LONG_THRESH_MIN, total_bytes / LONG_BYTES_PER_THRESH), 1 << 30);
     c.docs = std::min<int64_t>(ndocs, total_bytes / ((int64_t)c.thresh + 1)) + 1;
-    c.chunks = std::min<int64_t>(total_bytes / 64 + 2 * c.docs + 1, (h->variant & 0x10000000) ? 40 : LONG_MAX_CHUNKS);      // (0x10000000: a test knob -- room for 40 chunks only)
+    c.chunks = std::min<int64_t>(total_bytes / 64 + 2 * c.docs + 1, wk.chunks_40 ? 40 : LONG_MAX_CHUNKS);
     c.list_off = 0;
     c.spec_off = ((size_t)c.docs * sizeof(LexLongDoc) + 255) & ~(size_t)255;
     c.jump_off = c.spec_off + (size_t)c.chunks * 64 * 16;
     c.tok2_off = c.jump_off + (size_t)c.chunks * 64 * 16;
     c.entry_off = c.tok2_off + (size_t)c.chunks * 64 * 8;
     // documents of more than LONG_BIG_CELLS cells take the chain in two levels (bf_kernels.hip k_lex_long_jump2 / _chain2 / _chain3): 16 more bytes
-    // per cell, reserved only for batches that can hold such a document.  BfSetVariant 0x08000000: a test knob -- from 256 cells on
-    c.big_cells = (h->variant & 0x08000000) ? 256 : LONG_BIG_CELLS;
+    // per cell, reserved only for batches that can hold such a document.  two_level_from_256: a test knob -- from 256 cells on
+    c.big_cells = wk.two_level_from_256 ? 256 : LONG_BIG_CELLS;
     const bool big = total_bytes + 1 > c.big_cells;
     c.jump2_off = c.entry_off + (size_t)c.chunks * 16;
     c.entry2_off = c.jump2_off + (big ? (size_t)c.chunks * 64 * 16 : 0);
@@ -573,11 +573,12 @@ int enqueue_flat(const Step &st)
     fp.dstat = h->w_dstat.as<int32_t>(); fp.cold = wave_cold(h, b.status); fp.espan = st.want_off ? h->w_espan.as<uint32_t>() : nullptr;
     fp.wrec = h->w_wrec.as<uint32_t>(); fp.wrec_cnt = (int32_t *)(h->w_wrec.as<char>() + (size_t)((total_bytes >> WF_REC_SHIFT) + 64) * 16);
     if (!hip_ok(hipMemsetAsync(fp.wrec_cnt, 0, (size_t)nranges * 8, s), "hipMemsetAsync")) return BF_E_DEVICE;      // (a range without documents writes nothing)
+    const WpFlatKnobs fk = wp_flat_knobs(h->variant);
 #ifdef BF_EXPERIMENTS
-    fp.dbg = (h->variant >> 20) & 0xf;
+    fp.dbg = fk.dbg;
 #endif
     st.record(EV_DOM0);
-    launch_wp_flat(fp, h->variant, s);
+    launch_wp_flat(fp, fk, s);
     st.record(EV_DOM1);
     // the words the table did not answer: walked by a kernel of their own
     WfUnitParams up;
@@ -585,13 +586,15 @@ int enqueue_flat(const Step &st)
     up.wrec = fp.wrec; up.wrec_cnt = fp.wrec_cnt; up.range_doc = fp.range_doc; up.doc_off = b.doc_off; up.nranges = nranges; up.ent = fp.ent; up.home = fp.home;
     up.extra = h->w_counts.as<int32_t>(); up.espan = fp.espan; up.hspan = st.want_off ? h->w_hspan.as<uint32_t>() : nullptr;
     up.cpmap = fp.cold.cpmap; up.kind = fp.cold.kind; up.nclasses = fp.cold.nclasses; up.stats = fp.cold.stats;
-    launch_wp_units(up, h->variant, s);
+    launch_wp_units(up, wp_units_knobs(h->variant), s);
     st.record(EV_TOK);
     // the documents it hands back: the wave program, one document at a time
     launch_wp_hardlist(fp.dstat, &misc->unsafe, ndocs, h->w_list.as<int32_t>(), &misc->list_n, s);
     WpWaveParams wp = wave_params(h, b, st.max_ids, st.unk, st.want_off);
     wp.doc_list = h->w_list.as<int32_t>(); wp.list_n = &misc->list_n; wp.cold.stats = nullptr;
-    launch_wp_wave(wp, h->variant & ~0x3f000000, s);
+    WpWaveKnobs lk = wp_wave_knobs(h->variant);
+    lk.per_cu = 0;                      // per_cu is meant for the flat program here: the list launch takes what the occupancy query answers
+    launch_wp_wave(wp, lk, s);
     WfMergeParams mp;
     mp.doc_off = b.doc_off; mp.ndocs = ndocs; mp.ent = fp.ent; mp.home = fp.home; mp.ent_off = fp.ent_off; mp.ent_cnt = fp.ent_cnt; mp.dstat = fp.dstat; mp.unsafe = &misc->unsafe;
     mp.ids_tmp = wp.ids_tmp; mp.counts = wp.counts; mp.id_off = st.id_off; mp.ids_out = st.ids_out; mp.ids_cap = st.ids_cap; mp.status = b.status; mp.max_ids = st.max_ids; mp.unk = st.unk;
@@ -615,7 +618,7 @@ StepTail enqueue_wave(const Step &st)
     st.record(EV_PREP);
     const WpWaveParams wp = wave_params(h, st.b, st.max_ids, st.unk, st.want_off);
     st.record(EV_DOM0);
-    if (st.b.ndocs > 0) launch_wp_wave(wp, h->variant, st.s);
+    if (st.b.ndocs > 0) launch_wp_wave(wp, wp_wave_knobs(h->variant), st.s);
     st.record(EV_DOM1);
     st.record(EV_TOK);
     return StepTail{};
@@ -650,13 +653,13 @@ StepTail enqueue_lane_lexer(const Step &st)
     lp.stats = h->lex_stats ? misc->stats : nullptr;
     const LongCaps lc = long_caps(h, ndocs, total_bytes, words);
     char *lg = h->w_long.as<char>();
-    lp.lg = LexLongParams{lc.thresh, (words && (h->variant & 0x20000000)) ? 3 : 0, lc.docs, lc.chunks, &misc->long_hdr,
+    lp.lg = LexLongParams{lc.thresh, (words && words_knobs(h->variant).small_triples) ? 3 : 0, lc.docs, lc.chunks, &misc->long_hdr,
                           (LexLongDoc *)(lg + lc.list_off), (int32_t *)(lg + lc.spec_off), (int32_t *)(lg + lc.jump_off), (int32_t *)(lg + lc.tok2_off), lc.big_cells,
                           (int32_t *)(lg + lc.jump2_off), (int32_t *)(lg + lc.entry2_off), (int32_t *)(lg + lc.entry_off)};
     st.record(EV_DOM0);
     if (ndocs > 0) {
         launch_lex_long_list(lp, s);
-        launch_lex_wp(lp, words ? (h->variant & ~0x7800F000) : h->variant, s);
+        launch_lex_wp(lp, lane_lex_knobs(h->variant, words != 0), s);
         launch_lex_long(lp, s);
     }
     st.record(EV_DOM1);
@@ -669,19 +672,19 @@ StepTail enqueue_lane_lexer(const Step &st)
 StepTail enqueue_bpe_wave(const Step &st, const SpSegParams &sg)
 {
     Handle *h = st.h; const Model &m = h->m; hipStream_t s = st.s;
-    const int tune = (h->variant >> 8) & 0xf;
+    const BpeWaveKnobs bk = bpe_wave_knobs(h->variant);
     BpeWaveParams bw;
     bw.T = sg.S.T; bw.info = sg.S.info; bw.initial = sg.S.initial; bw.cls_delim = sg.S.cls_delim; bw.id_offset = sg.S.id_offset;
     bw.prio = sg.bpe_prio; bw.place_id = sg.bpe_place_id;
-    if (!m.bpe_tab.empty() && (h->variant & 0x100000) == 0) { bw.W = h->t_bpetab.as<uint64_t>(); bw.wbits = m.bpe_tab_bits; bw.m0 = m.bpe_tab_m0; bw.m1 = m.bpe_tab_m1; bw.m2 = m.bpe_tab_m2; }      // (BfSetVariant bit 20: A/B runs without the word table)
+    if (!m.bpe_tab.empty() && !bk.no_word_table) { bw.W = h->t_bpetab.as<uint64_t>(); bw.wbits = m.bpe_tab_bits; bw.m0 = m.bpe_tab_m0; bw.m1 = m.bpe_tab_m1; bw.m2 = m.bpe_tab_m2; }      // (no_word_table: A/B runs without it)
     bw.stream = sg.stream; bw.lens = sg.lens; bw.doc_off = st.b.doc_off; bw.slot_mul = sg.slot_mul; bw.ndocs = st.b.ndocs;
     bw.ids_tmp = sg.ids_tmp; bw.counts = sg.counts; bw.flags = h->w_bwflags.as<int32_t>(); bw.max_ids = st.max_ids; bw.next_doc = sg.next_doc; bw.status = st.b.status;
     bw.scratch = (uint32_t *)sg.arcs; bw.stats = h->lex_stats ? h->misc()->stats : nullptr;
     st.record(EV_DOM0);
-    launch_bpe_wave(bw, tune, s);
+    launch_bpe_wave(bw, bk.tune, s);
     st.record(EV_DOM1);
     launch_bpe_seg_flags(sg, bw.flags, h->w_perm.as<int32_t>(), h->w_hist.as<unsigned int>(), s);
-    return StepTail{bpe_wave_home(tune) ? StepTail::BPE_HOME : StepTail::COMPACT, sg.slot_mul, nullptr};
+    return StepTail{bpe_wave_home(bk.tune, EXPERIMENTS_BUILD) ? StepTail::BPE_HOME : StepTail::COMPACT, sg.slot_mul, nullptr};
 }
 
 // The _sp family: Unigram (cut form, lane form) and BPE (the wave program above, the lane kernels).
@@ -697,8 +700,9 @@ StepTail enqueue_sp(const Step &st)
     pp.delim_code = m.sp_delim_code;
     pp.prefix_n = m.no_dummy_prefix ? 0 : (int)m.sp_prefix.size();
     for (int k = 0; k < 10; ++k) pp.prefix[k] = k < pp.prefix_n ? m.sp_prefix[(size_t)k] : 0;
-    pp.old_form = (h->variant & 0x80) ? 1 : 0;
-    pp.waves = (h->variant >> 24) & 0xf;
+    const SpPrepKnobs pk = sp_prep_knobs(h->variant);
+    pp.old_form = pk.old_form ? 1 : 0;
+    pp.waves = pk.waves;
     pp.slot_mul = mul; pp.stream = h->w_cls.as<uint16_t>(); pp.lens = h->w_nchars.as<int32_t>(); pp.src_off = want_off ? h->w_srcoff.as<int32_t>() : nullptr;
     if (ndocs > 0) launch_prep_sp(pp, s);
     st.record(EV_PREP);
@@ -718,11 +722,13 @@ StepTail enqueue_sp(const Step &st)
         if (m.kind == KIND_BPE_MERGES) { sg.bpe_prio = h->t_bpe_prio.as<uint32_t>(); sg.bpe_place_id = h->t_bpe_place.as<int32_t>(); }
         sg.bpe_unk_prio = bpe_unk_prio(m, st.unk);
     }
-    sg.narcs = h->w_narcs.as<int32_t>(); sg.next_doc = &misc->next_doc; sg.trie_depth = m.trie_max_depth; sg.variant = h->variant & 0xff; sg.tune = (h->variant >> 8) & 0xff; sg.tune2 = (h->variant >> 16) & 0xff;
+    sg.narcs = h->w_narcs.as<int32_t>(); sg.next_doc = &misc->next_doc; sg.trie_depth = m.trie_max_depth;
+    const SegKnobs sk = seg_knobs(h->variant);
+    sg.tune = sk.tune;
     sg.lane_ok = uni_lane_ok(m) ? 1 : 0;
-    // ids only: the cut form (bf_seg.h UniCut; BfSetVariant 6: the forward / backward kernels of round 4, which the offsets API still takes)
+    // ids only: the cut form (bf_seg.h UniCut; cut_off: the forward / backward kernels of round 4, which the offsets API still takes)
     const bool uni_lane = m.kind == KIND_UNIGRAM && sg.lane_ok;
-    sg.uni_cut = (uni_lane && !want_off && (h->variant & 0xff) != 6) ? 1 : 0;
+    sg.uni_cut = (uni_lane && !want_off && !sk.cut_off) ? 1 : 0;
     h->last_uni_cut = sg.uni_cut != 0;
     sg.perm = h->w_perm.as<int32_t>(); sg.hist = h->w_hist.as<unsigned int>();
     // the cut form leaves tokens, not ids (k_uni_ids is its compaction); the lane form writes its ids right-aligned (their first index: w_narcs)
@@ -732,7 +738,7 @@ StepTail enqueue_sp(const Step &st)
         // (the Unigram lane program records the two events around its forward kernel itself: the sort of the documents comes before it)
         sg.ev_dom0 = h->ev[EV_DOM0]; sg.ev_dom1 = h->ev[EV_DOM1];
         if (!uni_lane || ndocs <= 0) st.record(EV_DOM0);
-        if (ndocs > 0) launch_seg_sp(sg, s);
+        if (ndocs > 0) launch_seg_sp(sg, sk, s);
         if (!uni_lane || ndocs <= 0) st.record(EV_DOM1);
     }
     st.record(EV_TOK);
@@ -990,7 +996,7 @@ int64_t run_host_mapped(Handle *h, const char *text, const int64_t *doc_off, int
     wp.ids_tmp = (int32_t *)(dp + SmallLayout::ids); wp.counts = (int32_t *)(dp + SmallLayout::counts);
     wp.next_doc = nullptr;              // no work counter: an atomic on host memory costs every wave a trip over the bus
     wp.cold.stats = nullptr;
-    launch_wp_wave(wp, h->variant, h->stream);
+    launch_wp_wave(wp, wp_wave_knobs(h->variant), h->stream);
     h->ev_valid = false;
     if (!hip_ok(hipGetLastError(), "kernel launch") || !hip_ok(hipStreamSynchronize(h->stream), "hipStreamSynchronize")) return BF_E_DEVICE;
     h->small_status = *(const int *)(hp + SmallLayout::ctrl + 16);
@@ -2511,9 +2517,7 @@ int BfSetVariant(void *p, int variant)
     if (!h) return BF_E_ARG;
     std::lock_guard<std::mutex> lock(h->mu);
 #ifndef BF_EXPERIMENTS
-    // the bits that select a measurement instance (compiled with BF_EXPERIMENTS only): WordPiece -- units configuration (8..11), waves per SIMD of
-    // the flat program (16..19), transitions per vote of the lane kernel (20..23); _sp -- waves per SIMD of the prologue (24..27)
-    if (variant & (h->m.kind == KIND_WP ? 0x00FF0F00 : 0x0F000000)) return BF_E_UNSUPPORTED;
+    if (variant_needs_experiments(h->m.kind == KIND_WP, variant)) return BF_E_UNSUPPORTED;      // a measurement instance this build does not carry
 #endif
     int old = h->variant; h->variant = variant;
     for (Handle *c : h->shards) if (c && c != h) { std::lock_guard<std::mutex> lc(c->mu); c->variant = variant; }
@@ -2563,7 +2567,7 @@ const char *BfStepKernels(void *p)
         return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_seg_unigram_lane, k_uni_back | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
     case KIND_I2W: case KIND_W2H: return "";
     default:
-        if (use_bpe_wave(h, false)) return bpe_wave_home((h->variant >> 8) & 0xf) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather"
+        if (use_bpe_wave(h, false)) return bpe_wave_home(bpe_wave_knobs(h->variant).tune, EXPERIMENTS_BUILD) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather"
                                                                               : "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
         return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_bpe_fused, k_bpe_collect_list, k_bpe_sort, k_bpe_apply_flat, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
     }

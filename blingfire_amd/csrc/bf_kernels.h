@@ -12,6 +12,7 @@
 #include "bf_rows.h"
 #include "bf_pairs.h"
 #include "bf_packed.h"
+#include "bf_variant.h"
 
 namespace bfa {
 
@@ -121,9 +122,7 @@ struct SpSegParams {
     uint8_t *big_pool; unsigned long long big_cap; unsigned long long *big_used, *big_need;   // BPE: pool of the documents whose arcs exceed the per-document reserve (k_bpe_seg); *big_need: bytes that did not fit
     const uint32_t *bpe_prio; const int32_t *bpe_place_id; uint32_t bpe_unk_prio; int bpe_prio_bits;   // bf_bpe_seg_body.h: the arc order as integers (bf_model.h)
     unsigned long long *seg_stats;   // optional (experiments): counters of k_bpe_seg
-    int variant;
-    int tune;                   // experiments: vote threshold of the lane-local BPE solve / Unigram transitions per trip (0 = default)
-    int tune2;                  // experiments: resident waves per CU of the persistent segmenter kernels (0 = what fits)
+    int tune;                   // SegKnobs::tune, here because k_bpe_fused reads it on the device: the vote threshold of its lane-local solve (p.tune ? p.tune : 16)
     unsigned long long *next_doc;
     void *ev_dom0 = nullptr, *ev_dom1 = nullptr;   // optional (hipEvent_t): recorded around the dominant kernel of the step (the Unigram forward pass)
 };
@@ -155,7 +154,6 @@ struct BpeHomeParams {
     Batch b; const int32_t *ids_tmp; const int32_t *lens; const int32_t *flags; int slot_mul;
     int32_t *counts; const int64_t *id_off; int32_t *ids_out; int64_t ids_cap; int max_ids; int *status;
 };
-bool bpe_wave_home(int tune);
 void launch_bpe_home_gather(const BpeHomeParams &p, hipStream_t s);
 
 struct ScanParams { const int32_t *counts; int64_t ndocs; int64_t *id_off; int64_t *block_sums; int nblocks; };
@@ -172,22 +170,22 @@ struct CompactParams {
 
 // flags: one bit per 16-byte chunk of the text (u64 per KiB, + 1), or nullptr for the one-pass wave-per-document form
 void launch_prep_wp(const WpPrepParams &p, int64_t total_bytes, unsigned long long *flags, hipStream_t s);
-void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s);
+void launch_lex_wp(const WpLexParams &p, const LaneLexKnobs &k, hipStream_t s);
 void launch_lex_long_list(const WpLexParams &p, hipStream_t s);      // before launch_lex_wp: lists the long documents (counts[doc] = -1)
 void launch_lex_long(const WpLexParams &p, hipStream_t s);           // after it: the three kernels of the long-document path
-void launch_wp_wave(const WpWaveParams &p, int variant, hipStream_t s);     // unit-form lexers (bf_wave.h): replaces prep + lexer
+void launch_wp_wave(const WpWaveParams &p, const WpWaveKnobs &k, hipStream_t s);     // unit-form lexers (bf_wave.h): replaces prep + lexer
 // the flat program (bf_flat.h): ranges + fitness of the batch, the program, the documents it hands back, counts, merge
 int wp_flat_ranges(int64_t ndocs, int64_t total_bytes);
 void launch_wp_pre(const int64_t *doc_off, int64_t ndocs, int64_t total_bytes, int nranges, int64_t *range_doc, int *unsafe, hipStream_t s);
-void launch_wp_flat(const WfParams &p, int variant, hipStream_t s);
-void launch_wp_units(const WfUnitParams &p, int variant, hipStream_t s);
+void launch_wp_flat(const WfParams &p, const WpFlatKnobs &k, hipStream_t s);
+void launch_wp_units(const WfUnitParams &p, const WpUnitsKnobs &k, hipStream_t s);
 void launch_wp_hardlist(const int32_t *dstat, const int *unsafe, int64_t ndocs, int32_t *list, unsigned int *list_n, hipStream_t s);
 void launch_wp_count(const WfMergeParams &p, hipStream_t s);
 void launch_wp_merge(const WfMergeParams &p, hipStream_t s);
-void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s);                  // bpe-opt models (bf_bpe_wave_body.h)
+void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s);                  // bpe-opt models (bf_bpe_wave_body.h); tune: bf_variant.h BPE_WAVE_TUNES
 void launch_bpe_seg_flags(const SpSegParams &p, const int32_t *flags, int32_t *list, unsigned int *count, hipStream_t s);   // the documents it hands back: bf_bpe_seg_body.h
 void launch_prep_sp(const SpPrepParams &p, hipStream_t s);
-void launch_seg_sp(const SpSegParams &p, hipStream_t s);
+void launch_seg_sp(const SpSegParams &p, const SegKnobs &k, hipStream_t s);
 void launch_scan(const ScanParams &p, hipStream_t s);
 
 // IdsToText (reference tokdll:1689-1745) as a batch: ids of sequence d are ids[id_off[d] .. id_off[d+1])

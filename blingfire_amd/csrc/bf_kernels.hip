@@ -548,15 +548,14 @@ static size_t lex_lds_bytes(const WpLexParams &p, int threads, bool tlds = false
 constexpr int LEX_TLDS_THREADS = 512;            // workgroup of the LDS-table variant: 8 waves share one copy of the table
 constexpr size_t LEX_TLDS_MAX_BYTES = 64 * 1024; // LDS budget of one workgroup (two of them fit a CU's 160 KB)
 
-// variant (experiments): bits 8..15 = event threshold, bits 16..19 = fetch threshold, bits 20..23 = transitions per vote (two-level
-// ids-only instance: 3 or 5), bits 24..29 = resident waves per CU
-void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s)
+// k (bf_variant.h LaneLexKnobs): votes = transitions per vote of the two-level ids-only instance (3 or 5), per_cu = resident waves per CU
+void launch_lex_wp(const WpLexParams &p, const LaneLexKnobs &k, hipStream_t s)
 {
     WpLexParams q = p;
-    q.ev_thresh = (variant >> 8) & 0xff; if (q.ev_thresh == 0) q.ev_thresh = 32;
-    q.fetch_thresh = (variant >> 16) & 0xf; if (q.fetch_thresh == 0) q.fetch_thresh = 8;
+    q.ev_thresh = k.ev_thresh ? k.ev_thresh : 32;
+    q.fetch_thresh = k.fetch_thresh ? k.fetch_thresh : 8;
     q.acts_n = p.acts_n;                                          // <= 4096 ints, checked at LoadModel
-    int waves_per_cu = (variant >> 24) & 0x3f;
+    int waves_per_cu = k.per_cu;
     if (waves_per_cu == 0) waves_per_cu = resident_per_cu(k_lex_wp_flat<64, ClsWin, false, 3, false>, 64, lex_lds_bytes(q, 64), 16);      // persistent: exactly the resident waves
     const int64_t need = (p.b.ndocs + 63) / 64;
     const int64_t blocks = resident_blocks(waves_per_cu, need);
@@ -579,13 +578,13 @@ void launch_lex_wp(const WpLexParams &p, int variant, hipStream_t s)
     if (p.L.two_level && !p.stats) {
         // two-level lexers: no saved frames in LDS, cheap events -> a lower event threshold pays (swept on MI355X)
         WpLexParams q2 = q; q2.L.max_frames = 0;
-        if (((variant >> 8) & 0xff) == 0) q2.ev_thresh = 16;
+        if (k.ev_thresh == 0) q2.ev_thresh = 16;
         const size_t lds2 = lex_lds_bytes(q2, 64);
         // transitions per vote: swept on MI355X with the two-level event code (2: 8.50 ms, 3: 7.67, 4: 6.86 on the 1.25 M-doc shard)
-        const int un = (variant >> 20) & 0xf; (void)un;
+        const int un = k.votes; (void)un;
         const bool plain = !has_any && !q2.words && !q2.span_tmp;
         int per_cu = plain ? resident_per_cu(k_lex_wp_plain<4>, 64, lds2, 16) : resident_per_cu(k_lex_wp_flat<64, ClsWin, false, 4, false, false, true>, 64, lds2, 16);
-        if (((variant >> 24) & 0x3f) != 0) per_cu = (variant >> 24) & 0x3f;
+        if (k.per_cu != 0) per_cu = k.per_cu;
         const dim3 g2((unsigned)resident_blocks(per_cu, need)), t2(64);
         if (has_any) hipLaunchKernelGGL((k_lex_wp_flat<64, ClsWin, true, 1, false, false, true>), g2, t2, lds2, s, q2);
 #ifdef BF_EXPERIMENTS
@@ -982,18 +981,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // The instances the library carries: ids (ring of 1,024 elements -- the longest word + one chunk fit: bf_model.cpp "unit form" --, a queue
 // of 256 tokens, a table of 8 open documents, eight workgroups per CU: 64 VGPRs, 20 KB of LDS per workgroup; every parameter swept on
 // MI355X, profiles/r03_ab_runs.txt, r04_p_wp_trim.txt), its twin with counters (BfSetLexStats), the offsets instance (a span with every id:
-// six workgroups per CU) and the LIST instance (the documents the flat program hands back).  variant bits 12..15 = documents per grab
-// (0 = by batch size), bits 24..29 = workgroups per CU (measurements: fewer resident waves).
-void launch_wp_wave(const WpWaveParams &p, int variant, hipStream_t s)
+// six workgroups per CU) and the LIST instance (the documents the flat program hands back).  k (bf_variant.h WpWaveKnobs): grab = documents per
+// grab (0 = by batch size), per_cu = workgroups per CU (measurements: fewer resident waves).
+void launch_wp_wave(const WpWaveParams &p, const WpWaveKnobs &k, hipStream_t s)
 {
-    int grab = (variant >> 12) & 0xf;
+    int grab = k.grab;
     if (grab == 0 || grab > WV_GRAB_MAX) {
         // documents a wave takes from the work counter at once: eight in a large batch (one atomic per 4 KB of text); a batch with fewer
         // documents than that would give every wave is spread over the waves one by one (a batch of 64 single sentences: 64 waves)
         const int64_t per_wave = p.ndocs / ((int64_t)device_cus() * 32);
         grab = per_wave >= WV_GRAB_MAX ? WV_GRAB_MAX : per_wave < 1 ? 1 : (int)per_wave;
     }
-    const int per_cu_override = (variant >> 24) & 0x3f;
     typedef WvLds<1024, 256, 8> L;
     typedef WvLds<1024, 256, 8, true> LO;
     static int pc_ids = 0, pc_off = 0, pc_list = 0, pc_list_off = 0;
@@ -1002,7 +1000,7 @@ void launch_wp_wave(const WpWaveParams &p, int variant, hipStream_t s)
     else if (p.doc_list) { per_cu = wave_program_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15, true>, pc_list); grab = 1; }
     else if (p.span_tmp) per_cu = wave_program_per_cu(k_wp_wave<LO, 1, 3, 6, false, 4, true, 15>, pc_off);
     else per_cu = wave_program_per_cu(k_wp_wave<L, 1, 3, 8, false, 4, false, 15>, pc_ids);
-    if (per_cu_override > 0) per_cu = per_cu_override;
+    if (k.per_cu > 0) per_cu = k.per_cu;
     int64_t blocks = (int64_t)device_cus() * per_cu;
     if (!p.doc_list) {                      // (the number of listed documents is known to the device only)
         const int64_t need = (p.ndocs + (int64_t)grab * 4 - 1) / ((int64_t)grab * 4);
@@ -1149,10 +1147,10 @@ static void launch_wp_flat_wpe(const WfParams &p, int per_cu_override, hipStream
     else hipLaunchKernelGGL((k_wp_flat<WPE, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
-// variant bits 16..19 (measurements): waves per SIMD the kernel is compiled for (0 = shipped), bits 24..29: workgroups per CU
-void launch_wp_flat(const WfParams &p, int variant, hipStream_t s)
+// k (bf_variant.h WpFlatKnobs; measurements): waves_per_simd the kernel is compiled for (0 = shipped), per_cu = workgroups per CU
+void launch_wp_flat(const WfParams &p, const WpFlatKnobs &k, hipStream_t s)
 {
-    const int per_cu_override = (variant >> 24) & 0x3f, wpe = (variant >> 16) & 0xf;
+    const int per_cu_override = k.per_cu, wpe = k.waves_per_simd;
 #ifdef BF_EXPERIMENTS
     if (wpe == 8) { launch_wp_flat_wpe<8>(p, per_cu_override, s); return; }
     if (wpe == 6) { launch_wp_flat_wpe<6>(p, per_cu_override, s); return; }
@@ -1174,10 +1172,10 @@ static void launch_wp_units_cfg(const WfUnitParams &p, int per_cu_override, hipS
     else hipLaunchKernelGGL((k_wp_units<WPE, NU, false>), dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
-// variant bits 8..11 (measurements, BF_EXPERIMENTS builds): 1 = eight waves per SIMD, 2 = one word per lane
-void launch_wp_units(const WfUnitParams &p, int variant, hipStream_t s)
+// k (bf_variant.h WpUnitsKnobs; measurements): cfg (BF_EXPERIMENTS builds) 1 = eight waves per SIMD, 2 = one word per lane
+void launch_wp_units(const WfUnitParams &p, const WpUnitsKnobs &k, hipStream_t s)
 {
-    const int per_cu_override = (variant >> 24) & 0x3f, cfg = (variant >> 8) & 0xf;
+    const int per_cu_override = k.per_cu, cfg = k.cfg;
 #ifdef BF_EXPERIMENTS
     if (cfg == 1) { launch_wp_units_cfg<8, 2>(p, per_cu_override, s); return; }
     if (cfg == 2) { launch_wp_units_cfg<8, 1>(p, per_cu_override, s); return; }

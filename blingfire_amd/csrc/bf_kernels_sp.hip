@@ -12,6 +12,7 @@
 //              NormalizeSpaces, TextToHashes: variable-length byte gathers and streaming kernels.
 #include "bf_kernels_common.h"
 #include "bf_bpe_wave_body.h"
+#include <utility>
 namespace bfa {
 
 // k_bpe_wave: the BPE wave program (bf_bpe_wave_body.h) on the class streams k_prep_sp8 wrote.  The same source runs in the test simulator
@@ -47,24 +48,20 @@ static void launch_bpe_wave_cfg(const BpeWaveParams &p, hipStream_t s)
     hipLaunchKernelGGL((k_bpe_wave<L, 4, STEPS, UMIN, HOME>), dim3((unsigned)blocks), dim3(256), 0, s, p, grab);
 }
 
-// tune (BfSetVariant bits 8..11): 0 = shipped (the HOME form, four transitions per round, the units phase ends with fewer than 32 busy units, a queue
-// of 256 words); 8: the in-order form of rounds 4..5 (ids retired through the queue; A/B runs and tests); experiments builds: 1 .. 3: the phase ends
-// with fewer than 16 / 4 / 48; 6: six transitions per round (in-order form).  Queues of 512 / 1024 words cost a block per CU each: 22.9 / 31.5 ms against 18.8.
-bool bpe_wave_home(int tune) { return tune != 8 && tune != 1 && tune != 2 && tune != 3 && tune != 6 && tune != 4 && tune != 5 && tune != 7; }
-void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s)
+// The instance bf_variant.h BPE_WAVE_TUNES names for `tune`, all with a queue of 256 words (queues of 512 / 1024 words cost a block per CU each:
+// 22.9 / 31.5 ms against 18.8).  An entry this build does not carry is the shipped one, like bpe_wave_home says of it.
+template <int I>
+static void launch_bpe_wave_entry(const BpeWaveParams &p, hipStream_t s)
 {
-#ifdef BF_EXPERIMENTS
-    if (tune == 1) { launch_bpe_wave_cfg<4, 16, 256, false>(p, s); return; }
-    if (tune == 2) { launch_bpe_wave_cfg<4, 4, 256, false>(p, s); return; }
-    if (tune == 3) { launch_bpe_wave_cfg<4, 48, 256, false>(p, s); return; }
-    if (tune == 6) { launch_bpe_wave_cfg<6, 32, 256, false>(p, s); return; }
-#endif
-    if (tune == 8) { launch_bpe_wave_cfg<4, 32, 256, false>(p, s); return; }
-    if (tune == 9) { launch_bpe_wave_cfg<4, 48, 256, true>(p, s); return; }
-    if (tune == 10) { launch_bpe_wave_cfg<3, 32, 256, true>(p, s); return; }
-    if (tune == 11) { launch_bpe_wave_cfg<4, 60, 256, true>(p, s); return; }
-    launch_bpe_wave_cfg<4, 32, 256, true>(p, s);
+    constexpr BpeWaveTune t = bpe_wave_tune(I, EXPERIMENTS_BUILD);
+    launch_bpe_wave_cfg<t.steps, t.umin, 256, t.home>(p, s);
 }
+template <int... I>
+static void launch_bpe_wave_by(int tune, const BpeWaveParams &p, hipStream_t s, std::integer_sequence<int, I...>)
+{
+    ((tune == I ? launch_bpe_wave_entry<I>(p, s) : (void)0), ...);
+}
+void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s) { launch_bpe_wave_by(tune & 15, p, s, std::make_integer_sequence<int, 16>{}); }
 
 // The HOME form of the BPE wave program leaves every id at its word's home -- a cell of the document's staging slot under the word's own elements,
 // BW_HOME_NONE in the cells between -- with the document's count (the program adds it up as the words report); this puts them where the API wants
@@ -1652,7 +1649,7 @@ void launch_bpe_seg_flags(const SpSegParams &p_in, const int32_t *flags, int32_t
     hipLaunchKernelGGL(k_bpe_seg, dim3((unsigned)device_cus() * 2u), dim3(64), 0, s, q);
 }
 
-void launch_seg_sp(const SpSegParams &p_in, hipStream_t s)
+void launch_seg_sp(const SpSegParams &p_in, const SegKnobs &k, hipStream_t s)
 {
     const SpSegParams &p = p_in;
     const unsigned bsort = (unsigned)((p.b.ndocs + 256 * SP_SORT_ITEMS - 1) / (256 * SP_SORT_ITEMS));
@@ -1667,15 +1664,6 @@ void launch_seg_sp(const SpSegParams &p_in, hipStream_t s)
         else {
             int ring = 1; while (ring < p.trie_depth) ring <<= 1;
             const size_t lds = (size_t)ring * 64 * (sizeof(double) + sizeof(uint32_t));
-            int per_cu = 0;
-#ifdef BF_EXPERIMENTS
-            const bool one_kernel = (p.variant & 0x20) != 0;     // A/B runs: forward and backward pass in one kernel (the form of rounds 2..3)
-            const int unroll = p.tune ? p.tune : 3;
-            auto kern = one_kernel ? (const void *)k_seg_unigram_lane<3> : unroll == 4 ? (const void *)k_seg_unigram_lane<4, true, 8> : (const void *)k_seg_unigram_lane<3, true, 8>;
-#else
-            const bool one_kernel = false; const int unroll = 3;
-            auto kern = (const void *)k_seg_unigram_lane<3, true, 8>;
-#endif
             if (p.uni_cut) {
                 // the cut form (ids only): records in LDS, tokens out at the cuts, no backward kernel
                 int W = 32; while (W < p.trie_depth + UC_SPILL + 4) W <<= 1;
@@ -1683,58 +1671,51 @@ void launch_seg_sp(const SpSegParams &p_in, hipStream_t s)
                 int pc = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void *)k_uni_cut<3>, 64, lds_c) != hipSuccess || pc <= 0) pc = 8;
                 (void)hipGetLastError();
-                if (p.tune2 > 0 && p.tune2 < pc) pc = p.tune2;
+                if (k.per_cu_cap > 0 && k.per_cu_cap < pc) pc = k.per_cu_cap;
                 unsigned blocks = (unsigned)device_cus() * (unsigned)pc;
                 if ((int64_t)blocks > (int64_t)b64) blocks = b64;
                 unsigned period_mask = 31u;
-                if (p.tune > 0) { period_mask = 1u; while (period_mask + 1u < (unsigned)p.tune) period_mask = period_mask * 2u + 1u; if (p.tune == 1) period_mask = 0u; }
+                if (k.tune > 0) { period_mask = 1u; while (period_mask + 1u < (unsigned)k.tune) period_mask = period_mask * 2u + 1u; if (k.tune == 1) period_mask = 0u; }
+                const int quick = k.quick_or_one_kernel ? 1 : 0;
                 if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
-                if (p.variant & 0x10) hipLaunchKernelGGL(k_uni_cut<2>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, (p.variant & 0x20) ? 1 : 0);
-                else hipLaunchKernelGGL(k_uni_cut<3>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, (p.variant & 0x20) ? 1 : 0);
+                if (k.cut_unroll2) hipLaunchKernelGGL(k_uni_cut<2>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, quick);
+                else hipLaunchKernelGGL(k_uni_cut<3>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, quick);
                 if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
                 return;
             }
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 8;
+            // forward pass (persistent lanes, records out), then the backward pass over every document
+            void (*kern)(SpSegParams, int) = k_seg_unigram_lane<3, true, 8>;
+            bool back = true;
+#ifdef BF_EXPERIMENTS
+            if (k.quick_or_one_kernel) { kern = k_seg_unigram_lane<3>; back = false; }      // A/B runs: forward and backward pass in one kernel (the form of rounds 2..3)
+            else if (k.tune == 4) kern = k_seg_unigram_lane<4, true, 8>;                     // four transitions per trip
+#endif
+            int per_cu = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 8;
             (void)hipGetLastError();
-            if (p.tune2 > 0 && p.tune2 < per_cu) per_cu = p.tune2;
+            if (k.per_cu_cap > 0 && k.per_cu_cap < per_cu) per_cu = k.per_cu_cap;
             unsigned blocks = (unsigned)device_cus() * (unsigned)per_cu;
             if ((int64_t)blocks > (int64_t)b64) blocks = b64;
-#ifdef BF_EXPERIMENTS
-            if (one_kernel) {
-                if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
-                hipLaunchKernelGGL(k_seg_unigram_lane<3>, dim3(blocks), dim3(64), lds, s, p, ring);
-                if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
-            } else if (unroll == 4) {
-                if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
-                hipLaunchKernelGGL((k_seg_unigram_lane<4, true, 8>), dim3(blocks), dim3(64), lds, s, p, ring);
-                if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
-                hipLaunchKernelGGL(k_uni_back, dim3((unsigned)((p.b.ndocs + 255) / 256)), dim3(256), 0, s, p);
-            } else
-#endif
-            {
-                // forward pass (persistent lanes, records out), then the backward pass over every document
-                (void)one_kernel; (void)unroll;
-                if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
-                hipLaunchKernelGGL((k_seg_unigram_lane<3, true, 8>), dim3(blocks), dim3(64), lds, s, p, ring);
-                if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
-                hipLaunchKernelGGL(k_uni_back, dim3((unsigned)((p.b.ndocs + 255) / 256)), dim3(256), 0, s, p);
-            }
+            if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
+            hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, s, p, ring);
+            if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
+            if (back) hipLaunchKernelGGL(k_uni_back, dim3((unsigned)((p.b.ndocs + 255) / 256)), dim3(256), 0, s, p);
         }
     } else {
         SpSegParams p = p_in;
-        if (p.variant == 2) { p.fb_list = nullptr; p.fb_count = nullptr; hipLaunchKernelGGL(k_bpe_collect, dim3(b64), dim3(64), 0, s, p); }
+        if (k.per_doc_kernels) { p.fb_list = nullptr; p.fb_count = nullptr; hipLaunchKernelGGL(k_bpe_collect, dim3(b64), dim3(64), 0, s, p); }
         else {
             p.fb_count = p.hist; p.fb_list = p.tos + 2 * p.bm_words;    // behind the two bitmaps of k_bpe_apply_flat
             (void)hipMemsetAsync(p.fb_count, 0, sizeof(unsigned int), s);
             const bool mg = p.S.kind == SG_KIND_BPE_MERGES;
-            const bool local = p.variant != 4 && p.unk >= 0 && p.unk < (1 << BPE_LOCAL_ID_BITS);
+            const bool local = !k.no_local && p.unk >= 0 && p.unk < (1 << BPE_LOCAL_ID_BITS);
             const size_t lds = local ? (size_t)8 * 1024 : 0;           // CAP * sizeof(Key) * 64 lanes, both flavours
             int per_cu = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bpe_fused<false, true>, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 12;
             (void)hipGetLastError();
             unsigned blocks = (unsigned)device_cus() * (unsigned)per_cu;
             if ((int64_t)blocks > (int64_t)b64) blocks = b64;
-            const bool arcs = p.variant == 5;                          // variant 5 (A/B runs): the instances that write every document's arc list
+            const bool arcs = k.write_arcs;                            // (A/B runs): the instances that write every document's arc list
             if (mg) {
                 if (local && !arcs) hipLaunchKernelGGL((k_bpe_fused<true, true, false>), dim3(blocks), dim3(64), lds, s, p);
                 else if (local) hipLaunchKernelGGL((k_bpe_fused<true, true>), dim3(blocks), dim3(64), lds, s, p);
@@ -1750,7 +1731,7 @@ void launch_seg_sp(const SpSegParams &p_in, hipStream_t s)
         unsigned sort_blocks = p.fb_list ? 64 : (unsigned)device_cus() * 2;                 // the fallback list is normally empty
         if ((int64_t)sort_blocks > p.b.ndocs) sort_blocks = (unsigned)p.b.ndocs;
         hipLaunchKernelGGL(k_bpe_sort, dim3(sort_blocks), dim3(256), 0, s, p);
-        if (p.variant == 2) hipLaunchKernelGGL(k_bpe_apply, dim3(b64), dim3(64), 0, s, p);
+        if (k.per_doc_kernels) hipLaunchKernelGGL(k_bpe_apply, dim3(b64), dim3(64), 0, s, p);
         else {
             (void)hipMemsetAsync(p.next_doc, 0, sizeof(unsigned long long), s);
             int per_cu = 0;

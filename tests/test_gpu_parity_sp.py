@@ -176,6 +176,24 @@ def test_bpe_wave_program_variant(model, checker):
         checker.free(hck)
 
 
+def test_bpe_wave_tune_without_instance(checker):
+    """BfSetVariant bits 8..11 (bf_variant.h BPE_WAVE_TUNES) with values that have no instance of the wave program in a product build: 1 (a
+    measurement instance of the in-order form, BF_EXPERIMENTS builds only), 4 and 7 (none in any build).  The kernel and the tail behind it come
+    from one table, so such a value runs the shipped HOME form with its gather (and 1, in a BF_EXPERIMENTS build, its own in-order instance with
+    the compaction): the checker's ids either way"""
+    h = bf.load_model(bfutil.model_path("gpt2.bin"))
+    hck = checker.load(bfutil.model_path("gpt2.bin"))
+    try:
+        docs = list(bfutil.ADVERSARIAL) + bfutil.fuzz_docs(300, seed=29)
+        for variant in (3 | (1 << 8), 3 | (4 << 8), 3 | (7 << 8)):
+            assert bf.lib().BfSetVariant(h, variant) >= 0
+            for max_ids, unk in ((2048, 0), (3, 0)):
+                _compare(h, checker, hck, docs, max_ids, unk)
+    finally:
+        bf.free_model(h)
+        checker.free(hck)
+
+
 @pytest.mark.parametrize("model", [m for m in ("xlm_roberta_base.bin", "gpt2.bin", "laser100k.bin") if bfutil.have_model(m)])
 def test_prologue_instances_agree(model, checker):
     """the _sp prologue as shipped (eight bytes per lane, compiled for eight waves per SIMD), compiled for six / seven waves (BfSetVariant

@@ -8,8 +8,8 @@ Each wave-program case therefore asserts, from the checker's answer alone, that 
 exceeds 256 x (an upper bound on the waves the launch code starts): by pigeonhole some wave then opened more than 256 documents.  The bounds:
 
   launch_wp_wave (bf_kernels.hip): blocks = min(cus * per_cu, ceil(ndocs / (4 * grab))), four waves a block; BfSetVariant bits 24..29 = per_cu (the
-      override), bits 12..15 = grab.  With bits 24..29 = 1 at most 4 * cus waves run.  The LIST instance (the documents the flat program hands back) masks the
-      override away (enqueue_flat: h->variant & ~0x3f000000) and takes what the occupancy query answers: at most the hardware's 32 waves per CU.
+      override), bits 12..15 = grab.  With bits 24..29 = 1 at most 4 * cus waves run.  The LIST instance (the documents the flat program hands back) gets no
+      override (enqueue_flat sets its WpWaveKnobs::per_cu to 0) and takes what the occupancy query answers: at most the hardware's 32 waves per CU.
   launch_bpe_wave_cfg (bf_kernels_sp.hip): blocks = min(cus * per_cu, ...) with per_cu from the occupancy query, no override: at most 32 waves per CU.
 
 The flat program (batches of >= 1,024 documents and >= 1 MiB on a fresh handle: bf_capi.cpp use_flat) sees chunks of 512 bytes that hold more than 512
