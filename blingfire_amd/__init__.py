@@ -97,6 +97,17 @@ def lib():
         L.IdsToPairRowsBatchDevice.restype = c_int
         L.IdsToPairRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [
             c_int64, c_void_p, c_void_p]
+        L.IdsToRowsPlanesBatch.restype = c_int64
+        L.IdsToRowsPlanesBatch.argtypes = L.IdsToRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p]
+        L.IdsToRowsPlanesBatchDevice.restype = c_int
+        L.IdsToRowsPlanesBatchDevice.argtypes = L.IdsToRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.IdsToPairRowsPlanesBatch.restype = c_int64
+        L.IdsToPairRowsPlanesBatch.argtypes = L.IdsToPairRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.IdsToPairRowsPlanesBatchDevice.restype = c_int
+        L.IdsToPairRowsPlanesBatchDevice.argtypes = L.IdsToPairRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.RowsSpanCellsBatchDevice.restype = c_int
+        L.RowsSpanCellsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                               c_void_p, c_void_p, c_void_p]
         L.IdsToPackedRowsBatch.restype = c_int64
         L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
         L.IdsToPackedRowsBatchDevice.restype = c_int
@@ -446,6 +457,24 @@ def text_to_ids_batch_device(h, d_text, d_doc_off, max_len, unk=0, out_ids=None,
     return out_ids, out_off
 
 
+def text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, max_len, unk=0, stream=None):
+    """Device-resident text_to_ids_with_offsets_batch, the mirror of text_to_ids_batch_device: (ids int32[cap], starts int32[cap],
+    ends int32[cap], id_offsets int64[ndocs+1]) tensors, enqueued without synchronising; starts / ends are byte offsets inside each
+    document (the end inclusive), the valid count is id_offsets[-1]."""
+    import torch
+    ndocs = d_doc_off.numel() - 1
+    total = d_text.numel()
+    cap = max(1, min(2 * (total + ndocs), ndocs * max(max_len, 0)))
+    ids, starts, ends = (torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(3))
+    out_off = torch.empty(ndocs + 1, dtype=torch.int64, device=d_text.device)
+    s = stream if stream is not None else torch.cuda.current_stream(d_text.device).cuda_stream
+    r = lib().TextToIdsWithOffsetsBatchDevice(c_void_p(h), d_text.data_ptr(), d_doc_off.data_ptr(), ndocs, total, ids.data_ptr(), starts.data_ptr(),
+                                              ends.data_ptr(), cap, out_off.data_ptr(), max_len, unk, c_void_p(s))
+    if r != 0:
+        raise RuntimeError("TextToIdsWithOffsetsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return ids, starts, ends, out_off
+
+
 def ids_to_text_batch_device(h, d_ids, d_id_off, out_text=None, out_off=None, skip_special_tokens=True, stream=None):
     """Device-resident IdsToText: torch int32 ids + int64 offsets on the model's GPU -> (text uint8[cap], text offsets int64[nseq+1]).
     Without `out_text` a buffer of 16 bytes per id is used (IdsToTextBatchDevice never writes past it)."""
@@ -467,31 +496,51 @@ def _special(i):
     return -1 if i is None else int(i)
 
 
-def _rows_host(name, pre, nseq, L, planes):
-    """the host forms of the row stage: the size query, then every output (one `planes` dtype per [R, L] plane, row item, row first id)"""
+def _plane_tail(srcs, fill, addr):
+    """the companion-plane arguments of the ...Planes calls: `srcs` = one list of arrays / tensors (None entries allowed) per side, `fill` = one int per
+    plane, addr(x) = the address of an array.  -> (nplanes, tail) with tail(outs) = the arguments for the plane outputs `outs` (None: every
+    plane NULL); the ctypes arrays live as long as `tail` does"""
+    n = len(fill)
+    if n > 4 or any(len(side) != n for side in srcs):
+        raise ValueError("companion planes: at most 4, and one source (or None) per fill value and side")
+    c_src = [(c_void_p * max(n, 1))(*[None if x is None else addr(x) for x in side]) for side in srcs]
+    c_fill = (c_int32 * max(n, 1))(*[int(f) for f in fill])
+
+    def tail(outs):
+        c_out = (c_void_p * max(n, 1))(*([None] * n if outs is None else [addr(o) for o in outs]))
+        return (n, *c_src, c_fill, c_out)
+    return n, tail
+
+
+def _rows_host(name, pre, nseq, L, planes, extra=None):
+    """the host forms of the row stage: the size query, then every output (one `planes` dtype per [R, L] plane, row item, row first id).
+    extra = (nplanes, tail) of _plane_tail: the ...Planes calls, whose int32 [R, L] planes are appended to the result as a list"""
     fn = getattr(lib(), name)
+    nextra, tail = extra if extra else (0, lambda outs: ())
     r_off = np.zeros(nseq + 1, dtype=np.int64)
-    n = fn(*pre, *[None] * (len(planes) + 2), 0, r_off.ctypes.data)
+    n = fn(*pre, *[None] * (len(planes) + 2), 0, r_off.ctypes.data, *tail(None))
     if n < 0:
         raise RuntimeError("%s failed: %d (%s)" % (name, n, lib().BfLastError().decode("utf-8", "replace")))
     outs = [np.empty((n, L), dtype=t) for t in planes] + [np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)]
+    more = [np.empty((n, L), dtype=np.int32) for _ in range(nextra)]
     if n > 0:
-        r = fn(*pre, *[o.ctypes.data for o in outs], n, r_off.ctypes.data)
+        r = fn(*pre, *[o.ctypes.data for o in outs], n, r_off.ctypes.data, *tail(more))
         if r != n:
             raise RuntimeError("%s failed: %d (%s)" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
-    return (*outs, r_off)
+    return (*outs, r_off, more) if extra else (*outs, r_off)
 
 
-def _rows_device(name, pre, nseq, L, planes, one_row, rows_cap, dev, stream):
+def _rows_device(name, pre, nseq, L, planes, one_row, rows_cap, dev, stream, extra=None):
     """the device forms of the row stage.  rows_cap None: nseq rows where one row per item is certain (`one_row`), else a size query whose
-    total is read back"""
+    total is read back.  extra: as in _rows_host"""
     import torch
     fn = getattr(lib(), name)
+    nextra, tail = extra if extra else (0, lambda outs: ())
     s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
     r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
 
-    def call(outs, cap):
-        r = fn(*pre, *outs, cap, r_off.data_ptr(), s)
+    def call(outs, cap, more=None):
+        r = fn(*pre, *outs, cap, r_off.data_ptr(), *tail(more), s)
         if r != 0:
             raise RuntimeError("%s failed (%d): %s" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
     if rows_cap is None:
@@ -503,8 +552,9 @@ def _rows_device(name, pre, nseq, L, planes, one_row, rows_cap, dev, stream):
                 torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
             rows_cap = int(r_off[-1].item())
     outs = [torch.empty((rows_cap, L), dtype=t, device=dev) for t in planes] + [torch.empty(rows_cap, dtype=torch.int32, device=dev) for _ in range(2)]
-    call([o.data_ptr() for o in outs], rows_cap)
-    return (*outs, r_off)
+    more = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(nextra)]
+    call([o.data_ptr() for o in outs], rows_cap, more)
+    return (*outs, r_off, more) if extra else (*outs, r_off)
 
 
 def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False):
@@ -533,15 +583,92 @@ def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pa
     return _rows_device("IdsToRowsBatchDevice", pre, nseq, L, (torch.int32, torch.uint8), max_rows_per_seq == 1, rows_cap, d_ids.device, stream)
 
 
-def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False):
+def _np_i32(x):
+    return None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+
+
+def _dev_i32(t, dev, what):
+    """a device array a kernel reads as int32 through its address: None, or a contiguous torch.int32 tensor on `dev` (anything else would be read
+    as garbage -- an int64 labels tensor as pairs of int32 -- so it is refused, not converted behind the caller's back)"""
+    import torch
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+        raise ValueError("%s must be a contiguous torch.int32 tensor on %s (got %s)" % (
+            what, dev, "%s, %s, %s" % (t.dtype, t.device, "contiguous" if t.is_contiguous() else "not contiguous") if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t
+
+
+def ids_to_rows_planes_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False, src=(), fill=()):
+    """ids_to_rows_batch with companion planes (IdsToRowsPlanesBatch): src = up to 4 int32 arrays parallel to ids (token offsets, labels, ...),
+    fill = one int per array.  Returns ids_to_rows_batch's five results and the list of planes, int32[R, L] each: a cell that holds an id holds
+    that id's element of the array, every other cell the array's fill."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
+    src = [_np_i32(x) for x in src]
+    nseq = len(id_off) - 1
+    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride),
+           int(max_rows_per_seq), int(bool(pad_left)))
+    return _rows_host("IdsToRowsPlanesBatch", pre, nseq, L, (np.int32, np.uint8), _plane_tail([src], fill, lambda a: a.ctypes.data))
+
+
+def ids_to_rows_planes_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False,
+                                    rows_cap=None, stream=None, src=(), fill=()):
+    """Device-resident ids_to_rows_planes_batch: src = int32 tensors on the device of d_ids, parallel to it (the starts / ends of
+    text_to_ids_with_offsets_batch_device as they are).  Returns ids_to_rows_batch_device's five results and the list of plane tensors."""
+    import torch
+    nseq = d_id_off.numel() - 1
+    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id),
+           int(stride), int(max_rows_per_seq), int(bool(pad_left)))
+    return _rows_device("IdsToRowsPlanesBatchDevice", pre, nseq, L, (torch.int32, torch.uint8), max_rows_per_seq == 1, rows_cap, d_ids.device, stream,
+                        _plane_tail([[_dev_i32(t, d_ids.device, "ids_to_rows_planes_batch_device: src[%d]" % k) for k, t in enumerate(src)]], fill, lambda t: t.data_ptr()))
+
+
+def rows_span_cells_device(h, starts, ends, row_seq, row_offsets, span_first, span_last, none_cell=0, stream=None):
+    """An item's byte span [span_first[q], span_last[q]] (the last byte inclusive) -> the cells of each of its rows whose tokens hold the span's
+    two ends (RowsSpanCellsBatchDevice).  starts / ends: int32[R, L] planes of token offsets with a negative fill (ids_to_*_planes_batch_device
+    over the tokenizer's offsets); row_seq: int32[R] the item of every row, or None (row r is item r); row_offsets: the int64[nseq+1] row
+    offsets of the call that made the planes (its last entry bounds the rows, on the device), or None (every row of the planes; the items are then as many as span_first has entries).
+    Returns (start_cell int32[R], end_cell int32[R]); none_cell in both where the span is not inside the row.  Like every batch call it clears
+    the handle's status word first: BfLastStatus afterwards is this call's (bit 3: a row whose item is out of range), not the row call's."""
+    import torch
+    dev = starts.device
+    for what, t in (("starts", starts), ("ends", ends), ("row_seq", row_seq)):
+        _dev_i32(t, dev, "rows_span_cells_device: " + what)
+    if starts.dim() != 2 or ends.shape != starts.shape or (row_seq is not None and row_seq.numel() != starts.shape[0]):
+        raise ValueError("rows_span_cells_device: starts and ends are [R, L] planes of one shape, row_seq has R entries")
+    if row_offsets is not None and (row_offsets.dtype != torch.int64 or not row_offsets.is_contiguous() or row_offsets.device != dev):
+        raise ValueError("rows_span_cells_device: row_offsets must be a contiguous torch.int64 tensor on %s" % dev)
+    R, L = starts.shape
+    span_first = span_first.to(device=dev, dtype=torch.int32).contiguous(); span_last = span_last.to(device=dev, dtype=torch.int32).contiguous()
+    nseq = row_offsets.numel() - 1 if row_offsets is not None else span_first.numel()          # (without row offsets the spans say how many items there are)
+    if span_first.numel() != span_last.numel() or span_first.numel() < nseq:
+        raise ValueError("rows_span_cells_device: span_first / span_last need one entry per item (%d)" % nseq)
+    out = [torch.full((R,), int(none_cell), dtype=torch.int32, device=starts.device) for _ in range(2)]
+    s = stream if stream is not None else torch.cuda.current_stream(starts.device).cuda_stream
+    r = lib().RowsSpanCellsBatchDevice(c_void_p(h), starts.data_ptr(), ends.data_ptr(), L, R,
+                                       None if row_offsets is None else row_offsets.data_ptr() + 8 * nseq, None if row_seq is None else row_seq.data_ptr(),
+                                       nseq, span_first.data_ptr(), span_last.data_ptr(), int(none_cell), out[0].data_ptr(), out[1].data_ptr(), c_void_p(s))
+    if r != 0:
+        raise RuntimeError("RowsSpanCellsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return out[0], out[1]
+
+
+def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False, return_offsets=False):
     """Text in HBM -> tensors a model takes, nothing on the host: text_to_ids_batch_device and ids_to_rows_batch_device on one stream.
     Every document is tokenised up to the ids its rows can hold (all of them when max_rows_per_doc is 0).
-    Returns (rows int32[R, L], mask uint8[R, L], row_doc int32[R], row_offsets int64[ndocs+1])."""
+    Returns (rows int32[R, L], mask uint8[R, L], row_doc int32[R], row_offsets int64[ndocs+1]); with return_offsets also
+    (starts int32[R, L], ends int32[R, L]): every token's first and last byte in its document, -1 in cells without a token."""
     body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
     step = body - int(stride)
     if body < 1 or stride < 0 or step < 1 or max_rows_per_doc < 0:
         raise ValueError("encode_batch_device: L leaves no room for ids, or stride / max_rows_per_doc are out of range")
     max_len = min(body + (max_rows_per_doc - 1) * step, 2 ** 31 - 1) if max_rows_per_doc > 0 else 2 ** 31 - 1
+    if return_offsets:
+        d_ids, d_st, d_en, d_id_off = text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, max_len, unk)
+        rows, mask, seq, _, r_off, (st, en) = ids_to_rows_planes_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, stride, max_rows_per_doc, pad_left,
+                                                                               src=[d_st, d_en], fill=[-1, -1])
+        return rows, mask, seq, r_off, st, en
     d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, max_len, unk)
     rows, mask, seq, _, r_off = ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, stride, max_rows_per_doc, pad_left)
     return rows, mask, seq, r_off
@@ -597,13 +724,51 @@ def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_
                         d_ids_a.device, stream)
 
 
+def _pair_sides(src_a, src_b, n):
+    return [list(src_a) if src_a is not None else [None] * n, list(src_b) if src_b is not None else [None] * n]
+
+
+def ids_to_pair_rows_planes_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
+                                  pad_left=False, double_sep=False, src_a=None, src_b=None, fill=()):
+    """ids_to_pair_rows_batch with companion planes (IdsToPairRowsPlanesBatch): src_a / src_b = lists of int32 arrays parallel to ids_a / ids_b,
+    one entry per fill value; a list that is None, or an entry that is, leaves that side's cells at the fill.  Returns ids_to_pair_rows_batch's
+    six results and the list of planes, int32[R, L] each."""
+    ids_a = np.ascontiguousarray(ids_a, dtype=np.int32); off_a = np.ascontiguousarray(off_a, dtype=np.int64)
+    ids_b = np.ascontiguousarray(ids_b, dtype=np.int32); off_b = np.ascontiguousarray(off_b, dtype=np.int64)
+    nseq = len(off_a) - 1
+    if len(off_b) != nseq + 1:
+        raise ValueError("ids_to_pair_rows_planes_batch: off_a and off_b name different numbers of sequences")
+    sides = [[_np_i32(x) for x in side] for side in _pair_sides(src_a, src_b, len(fill))]
+    pre = (c_void_p(h), ids_a.ctypes.data, off_a.ctypes.data, ids_b.ctypes.data, off_b.ctypes.data, nseq) + _pair_args(
+        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+    return _rows_host("IdsToPairRowsPlanesBatch", pre, nseq, L, (np.int32, np.uint8, np.uint8), _plane_tail(sides, fill, lambda a: a.ctypes.data))
+
+
+def ids_to_pair_rows_planes_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0,
+                                         max_rows_per_pair=1, pad_left=False, double_sep=False, rows_cap=None, stream=None, src_a=None, src_b=None, fill=()):
+    """Device-resident ids_to_pair_rows_planes_batch: src_a / src_b = lists of int32 tensors parallel to d_ids_a / d_ids_b (None entries and
+    None lists allowed).  Returns ids_to_pair_rows_batch_device's six results and the list of plane tensors."""
+    import torch
+    nseq = d_off_a.numel() - 1
+    if d_off_b.numel() != nseq + 1:
+        raise ValueError("ids_to_pair_rows_planes_batch_device: d_off_a and d_off_b name different numbers of sequences")
+    pre = (c_void_p(h), d_ids_a.data_ptr(), d_ids_a.numel(), d_off_a.data_ptr(), d_ids_b.data_ptr(), d_ids_b.numel(), d_off_b.data_ptr(), nseq) + _pair_args(
+        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+    return _rows_device("IdsToPairRowsPlanesBatchDevice", pre, nseq, L, (torch.int32, torch.uint8, torch.uint8), mode == 1 or max_rows_per_pair == 1, rows_cap,
+                        d_ids_a.device, stream, _plane_tail([[_dev_i32(t, d_ids_a.device, "ids_to_pair_rows_planes_batch_device: src_%s[%d]" % (ab, k))
+                                                              for k, t in enumerate(side)] for ab, side in zip("ab", _pair_sides(src_a, src_b, len(fill)))],
+                                                            fill, lambda t: t.data_ptr()))
+
+
 def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
-                              pad_left=False, double_sep=False):
+                              pad_left=False, double_sep=False, return_offsets=False, offsets_a=False):
     """Two texts in HBM -> the tensors a pair model takes, nothing on the host: two text_to_ids_batch_device calls and
     ids_to_pair_rows_batch_device on one stream.  Each side is tokenised up to the ids its rows can hold: T = L - specials for both in mode 1
     (cutting both to T first does not change what longest-first keeps); in mode 0 max_a for A and T + (max_rows_per_pair - 1) * (T - stride)
     for B (all of B when max_rows_per_pair is 0).
-    Returns (rows int32[R, L], mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[npairs+1])."""
+    Returns (rows int32[R, L], mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[npairs+1]); with
+    return_offsets also (starts int32[R, L], ends int32[R, L]): first and last byte of every token of B in its text (with offsets_a, of A in
+    its own text too), -1 in every other cell."""
     nsep = 0 if _special(sep_id) < 0 else 3 if double_sep else 2
     T = int(L) - (1 if _special(cls_id) >= 0 else 0) - nsep
     if T < 1 or mode not in (0, 1) or (mode == 0 and not (0 <= max_a <= T - 1 and 0 <= stride < T - max_a and max_rows_per_pair >= 0)):
@@ -613,10 +778,39 @@ def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id
     else:
         len_a = int(max_a)
         len_b = min(T + (max_rows_per_pair - 1) * (T - int(stride)), 2 ** 31 - 1) if max_rows_per_pair > 0 else 2 ** 31 - 1
+    if return_offsets:
+        src_a = None
+        if offsets_a:
+            d_ids_a, d_st_a, d_en_a, d_idoff_a = text_to_ids_with_offsets_batch_device(h, d_text_a, d_off_a, len_a, unk)
+            src_a = [d_st_a, d_en_a]
+        else:
+            d_ids_a, d_idoff_a = text_to_ids_batch_device(h, d_text_a, d_off_a, len_a, unk)
+        d_ids_b, d_st_b, d_en_b, d_idoff_b = text_to_ids_with_offsets_batch_device(h, d_text_b, d_off_b, len_b, unk)
+        *base, (st, en) = ids_to_pair_rows_planes_batch_device(h, d_ids_a, d_idoff_a, d_ids_b, d_idoff_b, L, cls_id, sep_id, pad_id, mode, max_a, stride,
+                                                              max_rows_per_pair, pad_left, double_sep, src_a=src_a, src_b=[d_st_b, d_en_b], fill=[-1, -1])
+        return (*base, st, en)
     d_ids_a, d_idoff_a = text_to_ids_batch_device(h, d_text_a, d_off_a, len_a, unk)
     d_ids_b, d_idoff_b = text_to_ids_batch_device(h, d_text_b, d_off_b, len_b, unk)
     return ids_to_pair_rows_batch_device(h, d_ids_a, d_idoff_a, d_ids_b, d_idoff_b, L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair,
                                          pad_left, double_sep)
+
+
+def encode_qa_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, sep_id, pad_id, max_q, stride, unk=0, double_sep=False, d_ans_first=None,
+                           d_ans_last=None):
+    """Questions and contexts in HBM -> extractive-QA inputs, one stream end to end: [cls] question [sep] context window [sep] rows (mode 0,
+    the first max_q question ids in every row, every window of the context, `stride` ids shared by neighbours) with the context's byte
+    offsets as planes.  Returns (rows, mask, type, row_pair, row_first_b, row_offsets, starts, ends) -- starts / ends int32[R, L]: first and
+    last byte of every context token in its context, -1 elsewhere -- and, with d_ans_first / d_ans_last (int32[npairs]: first and last byte,
+    inclusive, of each answer in its context; negative = none), also (start_cell, end_cell) int32[R]: the token cells of the answer in every
+    row, the [cls] cell (0) in both where the answer is not inside the row's window.  The only read-back is the size query of
+    ids_to_pair_rows_batch_device.  BfLastStatus afterwards is that of the LAST call on the handle alone, as always: with answers that is the span
+    call, which cleared what the tokenizer and row calls reported (ids or rows dropped, bad ranges); a caller who needs those runs
+    encode_pairs_batch_device(..., return_offsets=True) and rows_span_cells_device itself and reads the status between them."""
+    out = encode_pairs_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, sep_id, pad_id, unk, 0, max_q, stride, 0, False, double_sep,
+                                    return_offsets=True)
+    if d_ans_first is None or d_ans_last is None:
+        return out
+    return (*out, *rows_span_cells_device(h, out[6], out[7], out[3], out[5], d_ans_first, d_ans_last, 0))
 
 
 def encode_pairs_batch(h, docs_a, docs_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1, pad_left=False, double_sep=False):

@@ -105,7 +105,7 @@ struct PinBuf {
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device, in run_row_stage_device and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            size pass of run_w2h_device, in run_row_stage_device, in RowsSpanCellsBatchDevice and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
 //                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
@@ -201,6 +201,7 @@ struct Handle {
     DevBuf t_w2h, t_w2h_pats, t_w2h_l1, t_w2h_pages;             // [w2h]: pattern automaton, pattern pool, code point -> class (bf_w2h.h)
     DevBuf w_hcls, w_hnch, w_hsrc;                               // WordHyphenationBatch: position stream, characters and source bytes per word
     DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch / IdsToPairRowsBatch: sequence (pair) and first id of every row, where the caller takes neither
+    DevBuf w_plsrc[2][ROWS_MAX_PLANES], w_plout[ROWS_MAX_PLANES]; // IdsToRowsPlanesBatch / IdsToPairRowsPlanesBatch, host forms: the staged companion arrays of each side, the planes
     DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
@@ -1166,17 +1167,20 @@ struct Staged { std::vector<int64_t> rel; int64_t total = 0; };
 
 // Validates (data, off, n), reserves d_data / d_off and queues the copies of the payload behind off[0] and of the rebased offsets: 0 or BF_E_*.
 // elem: bytes per element (1 text, 4 ids and keys).  The payload is off[n] - off[0] elements, or `len` of them where the caller counts them
-// itself (IdsToRowsBatch: up to the largest offset).  Synchronises only where it fails with a copy queued.
-int stage_ragged(Staged &st, const void *data, size_t elem, const int64_t *off, int64_t n, DevBuf &d_data, DevBuf &d_off, hipStream_t s, int64_t len = -1)
+// itself (IdsToRowsBatch: up to the largest offset).  Synchronises only where it fails with a copy queued.  payload_only: a second array over offsets
+// that are staged already (a companion array beside its ids) -- d_off is left alone and `st` carries only the total.
+int stage_ragged(Staged &st, const void *data, size_t elem, const int64_t *off, int64_t n, DevBuf &d_data, DevBuf &d_off, hipStream_t s, int64_t len = -1,
+                 bool payload_only = false)
 {
     if (n < 0 || !off) return BF_E_ARG;
     const int64_t base = off[0];
     st.total = len >= 0 ? len : (n > 0 ? off[n] - base : 0);
     if (st.total < 0 || (st.total > 0 && !data)) return BF_E_ARG;
-    if (!d_data.reserve(elem == 1 ? (size_t)st.total + 16 : (size_t)(st.total + 1) * elem) || !d_off.reserve((size_t)(n + 1) * 8)) return BF_E_DEVICE;
+    if (!d_data.reserve(elem == 1 ? (size_t)st.total + 16 : (size_t)(st.total + 1) * elem) || (!payload_only && !d_off.reserve((size_t)(n + 1) * 8))) return BF_E_DEVICE;
+    if (st.total > 0 && !hip_ok(hipMemcpyAsync(d_data.p, (const char *)data + base * (int64_t)elem, (size_t)st.total * elem, hipMemcpyHostToDevice, s), "H2D payload")) return BF_E_DEVICE;
+    if (payload_only) return 0;
     st.rel.resize((size_t)n + 1);
     for (int64_t i = 0; i <= n; ++i) st.rel[(size_t)i] = off[i] - base;
-    if (st.total > 0 && !hip_ok(hipMemcpyAsync(d_data.p, (const char *)data + base * (int64_t)elem, (size_t)st.total * elem, hipMemcpyHostToDevice, s), "H2D payload")) return BF_E_DEVICE;
     if (!hip_ok(hipMemcpyAsync(d_off.p, st.rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s), "H2D offsets")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
     return 0;
 }
@@ -1333,8 +1337,10 @@ bool reserve_rows_workspaces(Handle *h, int64_t nseq)
 
 constexpr int ROW_OUTS = 5;
 
+// p_out / with_planes: run_row_planes_device's (it launches k_rowstage_planes behind this with the same parameters, and needs the map for it)
 template <class S>
-int run_row_stage_device(Handle *h, const S &src, int64_t nseq, void *const out[ROW_OUTS], int64_t rows_cap, int64_t *d_row_off, hipStream_t s, const char *what)
+int run_row_stage_device(Handle *h, const S &src, int64_t nseq, void *const out[ROW_OUTS], int64_t rows_cap, int64_t *d_row_off, hipStream_t s, const char *what,
+                         RowStageParams<S> *p_out = nullptr, bool with_planes = false)
 {
     if (nseq < 0 || rows_cap < 0 || !d_row_off || !src.valid()) return BF_E_ARG;
     if (!reserve_rows_workspaces(h, nseq)) return BF_E_DEVICE;
@@ -1349,10 +1355,49 @@ int run_row_stage_device(Handle *h, const S &src, int64_t nseq, void *const out[
     const bool planes = p.rows || p.mask || p.type;
     if (nseq > 0) launch_rowstage_count(p, s);
     scan_counts(h, nseq, d_row_off, s);
-    if (nseq > 0 && (planes || out[3] || out[4])) {
+    if (nseq > 0 && (planes || out[3] || out[4] || with_planes)) {
         launch_rowstage_map(p, s);
         if (rows_cap > 0 && planes) launch_rowstage_fill(p, s);
     }
+    if (p_out) *p_out = p;
+    return hip_ok(hipGetLastError(), what) ? 0 : BF_E_DEVICE;
+}
+
+// The companion planes of a ...Planes call as its entry point got them: host arrays of nplanes entries (src_b: pairs alone), device pointers in them.
+static_assert(ROWS_MAX_PLANES == BF_ROWS_MAX_PLANES, "the header's plane limit is the kernels'");
+struct PlaneArgs { int nplanes; const int32_t *const *src_a, *const *src_b; const int32_t *fill; int32_t *const *out; };
+
+// false = BF_E_ARG.  need_a: the rows form, where a companion array must exist wherever there are ids
+static bool plane_args_ok(const PlaneArgs &a, bool need_a, int64_t ids_len)
+{
+    if (a.nplanes < 0 || a.nplanes > ROWS_MAX_PLANES) return false;
+    if (a.nplanes == 0) return true;
+    if (!a.fill || !a.out) return false;
+    if (need_a && ids_len > 0) {
+        if (!a.src_a) return false;
+        for (int k = 0; k < a.nplanes; ++k) if (!a.src_a[k]) return false;
+    }
+    return true;
+}
+
+// The row stage with companion planes: run_row_stage_device as the base call runs it (the map also where only planes are taken: it reports the
+// rows dropped and leaves a row's item and first id for the lanes), then k_rowstage_planes over the planes the caller takes.
+template <class S>
+int run_row_planes_device(Handle *h, const S &src, int64_t nseq, void *const out[ROW_OUTS], int64_t rows_cap, int64_t *d_row_off, const PlaneArgs &a, hipStream_t s,
+                          const char *what)
+{
+    RowPlanesParams<S> pp;
+    bool any = false;
+    pp.nplanes = a.nplanes;
+    for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
+        const bool in = k < a.nplanes;
+        pp.src[CELL_SIDE_A][k] = in && a.src_a ? a.src_a[k] : nullptr; pp.src[CELL_SIDE_B][k] = in && a.src_b ? a.src_b[k] : nullptr;
+        pp.fill[k] = in ? a.fill[k] : 0; pp.out[k] = in ? a.out[k] : nullptr;
+        any = any || pp.out[k];
+    }
+    const int rc = run_row_stage_device(h, src, nseq, out, rows_cap, d_row_off, s, what, &pp.st, any);
+    if (rc != 0 || !any || nseq == 0 || rows_cap == 0) return rc;
+    launch_rowstage_planes(pp, s);
     return hip_ok(hipGetLastError(), what) ? 0 : BF_E_DEVICE;
 }
 
@@ -1366,19 +1411,43 @@ static int64_t host_side_len(const int64_t *off, int64_t nseq)
     return len;
 }
 
-// one optional output of the host form: the caller's array, the staging buffer it is filled in, its bytes per row (slots as run_row_stage_device's)
+// one optional output of the host form: the caller's array, the staging buffer it is filled in, its bytes per row (slots as run_row_stage_device's,
+// then the companion planes of the ...Planes calls; the base calls leave those empty)
 struct RowOut { void *host; DevBuf *dev; size_t row_bytes; const char *what; };
+constexpr int ROW_HOST_OUTS = ROW_OUTS + ROWS_MAX_PLANES;
+
+// the planes of a host call in the output table, and the device arrays a pass gathers them into
+static void plane_outs(Handle *h, const PlaneArgs &a, size_t L, RowOut *outs)
+{
+    for (int k = 0; k < a.nplanes; ++k) outs[ROW_OUTS + k] = RowOut{a.out[k], &h->w_plout[k], L * 4, "D2H plane"};
+}
+
+// Stages the companion arrays of one side beside its ids: the payload alone, over the side's offsets that stage_ragged has already put into d_off
+// (element i of an array belongs to id i).  d_src[k] = the staged array, NULL where the caller gave none.  0 or BF_E_*.
+static int stage_planes(Handle *h, const int32_t *const *src, int nplanes, int side, const int64_t *off, int64_t nseq, int64_t len, DevBuf &d_off, hipStream_t s,
+                        const int32_t **d_src)
+{
+    for (int k = 0; k < nplanes; ++k) {
+        d_src[k] = nullptr;
+        if (!src || !src[k] || len == 0) continue;
+        Staged st;                                                               // (nothing of it is a copy's source: the payload is the caller's array)
+        const int rc = stage_ragged(st, src[k], 4, off, nseq, h->w_plsrc[side][k], d_off, s, len, true);
+        if (rc != 0) return rc;
+        d_src[k] = h->w_plsrc[side][k].as<int32_t>();
+    }
+    return 0;
+}
 
 // Behind the staging of the host forms (the caller holds h->defer_mu, then h->mu -- w_ids, w_starts and w_ends may hold a sharded range's ids
 // that wait for their copy out -- and has reserved w_idoff): size pass, offsets to the caller, capacity check, fill pass, outputs to the caller.
 //   pass(d_out, cap)  run_row_stage_device over the staged source, with the row offsets in w_idoff
 // Returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written.  As in two_pass_host, whatever ends the call
 // early after work was queued synchronises the stream first.
-int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&outs)[ROW_OUTS], int64_t rows_cap, int64_t *row_off_out,
-                       const std::function<int(void *const d_out[ROW_OUTS], int64_t cap)> &pass)
+int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&outs)[ROW_HOST_OUTS], int64_t rows_cap, int64_t *row_off_out,
+                       const std::function<int(void *const d_out[ROW_HOST_OUTS], int64_t cap)> &pass)
 {
     auto fail = [s](int64_t rc) { (void)hipStreamSynchronize(s); return rc; };
-    void *d_out[ROW_OUTS] = {};
+    void *d_out[ROW_HOST_OUTS] = {};
     int rc = pass(d_out, 0);
     if (rc != 0) return fail(rc);
     if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets")) return fail(BF_E_DEVICE);
@@ -1388,7 +1457,7 @@ int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&ou
     for (const RowOut &o : outs) any = any || o.host;
     if (total == 0 || !any) return total;                                     // (a size query needs no capacity)
     if (total > rows_cap) return BF_E_CAPACITY;
-    for (int i = 0; i < ROW_OUTS; ++i) {
+    for (int i = 0; i < ROW_HOST_OUTS; ++i) {
         if (!outs[i].host) continue;
         if (!outs[i].dev->reserve((size_t)total * outs[i].row_bytes + 16)) return BF_E_DEVICE;
         d_out[i] = outs[i].dev->p;
@@ -1401,35 +1470,43 @@ int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&ou
 }
 
 // IdsToRowsBatch on host buffers: the ids through stage_ragged, then row_stage_host
+// (planes: IdsToRowsPlanesBatch; none = the base call, with the kernels of the base call)
 int64_t run_rows_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const RowsSpec &spec, int32_t *rows_out, uint8_t *mask_out,
-                      int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
+                      int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out, const PlaneArgs &planes = PlaneArgs{})
 {
     if (nseq < 0 || rows_cap < 0 || !id_off || !row_off_out) return BF_E_ARG;
     const int64_t ids_len = host_side_len(id_off, nseq);
-    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    if (ids_len < 0 || (ids_len > 0 && !ids) || !plane_args_ok(planes, true, ids_len)) return BF_E_ARG;
     std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = h->stream;
     if (!h->w_idoff.reserve((size_t)(nseq + 1) * 8)) return BF_E_DEVICE;
     Staged st;
-    const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    const int32_t *d_src[ROWS_MAX_PLANES] = {};
+    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
     if (rc != 0) return rc;
+    rc = stage_planes(h, planes.src_a, planes.nplanes, 0, id_off, nseq, ids_len, h->w_docoff, s, d_src);
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }                  // (the ids' copies are queued)
     const RowsSource src{spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>()};
     const size_t L = (size_t)spec.row_len;
-    const RowOut outs[ROW_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {nullptr, nullptr, 0, ""},
-                                   {row_seq_out, &h->w_starts, 4, "D2H row sequences"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
-    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_OUTS], int64_t cap) {
-        return run_row_stage_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), s, "IdsToRows kernels"); });
+    RowOut outs[ROW_HOST_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {nullptr, nullptr, 0, ""},
+                                  {row_seq_out, &h->w_starts, 4, "D2H row sequences"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
+    plane_outs(h, planes, L, outs);
+    // (without planes run_row_planes_device launches what run_row_stage_device launches, and nothing else)
+    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_HOST_OUTS], int64_t cap) {
+        const PlaneArgs d{planes.nplanes, d_src, nullptr, planes.fill, (int32_t *const *)(d_out + ROW_OUTS)};
+        return run_row_planes_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), d, s, "IdsToRows kernels"); });
 }
 
 // IdsToPairRowsBatch on host buffers: A in the id staging, B in the key staging of the dictionary lookup, then row_stage_host
 int64_t run_pairs_host(Handle *h, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, const PairsSpec &spec,
-                       int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out)
+                       int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap, int64_t *row_off_out,
+                       const PlaneArgs &planes = PlaneArgs{})
 {
     if (nseq < 0 || rows_cap < 0 || !off_a || !off_b || !row_off_out) return BF_E_ARG;
     const int64_t len_a = host_side_len(off_a, nseq), len_b = host_side_len(off_b, nseq);
-    if (len_a < 0 || len_b < 0 || (len_a > 0 && !ids_a) || (len_b > 0 && !ids_b)) return BF_E_ARG;
+    if (len_a < 0 || len_b < 0 || (len_a > 0 && !ids_a) || (len_b > 0 && !ids_b) || !plane_args_ok(planes, false, 0)) return BF_E_ARG;
     std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
@@ -1438,13 +1515,18 @@ int64_t run_pairs_host(Handle *h, const int32_t *ids_a, const int64_t *off_a, co
     Staged sa, sb;
     int rc = stage_ragged(sa, ids_a, 4, off_a, nseq, h->w_ids, h->w_docoff, s, len_a);
     if (rc == 0) rc = stage_ragged(sb, ids_b, 4, off_b, nseq, h->w_keys, h->w_keyoff, s, len_b);
+    const int32_t *d_src_a[ROWS_MAX_PLANES] = {}, *d_src_b[ROWS_MAX_PLANES] = {};
+    if (rc == 0) rc = stage_planes(h, planes.src_a, planes.nplanes, 0, off_a, nseq, len_a, h->w_docoff, s, d_src_a);
+    if (rc == 0) rc = stage_planes(h, planes.src_b, planes.nplanes, 1, off_b, nseq, len_b, h->w_keyoff, s, d_src_b);
     if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }                  // (A's copies may be queued)
     const PairsSource src{spec, h->w_ids.as<int32_t>(), h->w_keys.as<int32_t>(), len_a, len_b, h->w_docoff.as<int64_t>(), h->w_keyoff.as<int64_t>()};
     const size_t L = (size_t)spec.row_len;
-    const RowOut outs[ROW_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {type_out, &h->w_vals, L, "D2H types"},
-                                   {row_seq_out, &h->w_starts, 4, "D2H row pairs"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
-    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_OUTS], int64_t cap) {
-        return run_row_stage_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), s, "IdsToPairRows kernels"); });
+    RowOut outs[ROW_HOST_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {mask_out, &h->w_text, L, "D2H mask"}, {type_out, &h->w_vals, L, "D2H types"},
+                                  {row_seq_out, &h->w_starts, 4, "D2H row pairs"}, {row_first_out, &h->w_ends, 4, "D2H row firsts"}};
+    plane_outs(h, planes, L, outs);
+    return row_stage_host(h, s, nseq, outs, rows_cap, row_off_out, [&](void *const d_out[ROW_HOST_OUTS], int64_t cap) {
+        const PlaneArgs d{planes.nplanes, d_src_a, d_src_b, planes.fill, (int32_t *const *)(d_out + ROW_OUTS)};
+        return run_row_planes_device(h, src, nseq, d_out, cap, h->w_idoff.as<int64_t>(), d, s, "IdsToPairRows kernels"); });
 }
 
 // IdsToPackedRowsBatch on device buffers (bf_kernels_packed.hip): widths, scan, next, the doubling rounds, the scan of the marks, rows, then -- for
@@ -2194,6 +2276,79 @@ int64_t IdsToPairRowsBatch(void *p, const int32_t *ids_a, const int64_t *off_a, 
     PairsSpec spec;
     if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec)) return BF_E_ARG;
     return run_pairs_host(h, ids_a, off_a, ids_b, off_b, nseq, spec, rows_out, mask_out, type_out, row_seq_out, row_first_b_out, rows_cap, row_offsets_out);
+}
+
+/* ---- additive: the row calls with companion planes (k_rowstage_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */
+int IdsToRowsPlanesBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
+                               int pad_id, int stride, int max_rows_per_seq, int flags, int32_t *d_rows_out, uint8_t *d_mask_out, int32_t *d_row_seq_out,
+                               int32_t *d_row_first_out, int64_t rows_cap, int64_t *d_row_offsets_out, int nplanes, const int32_t *const *d_src, const int32_t *fill,
+                               int32_t *const *d_planes_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    RowsSpec spec;
+    const PlaneArgs planes{nplanes, d_src, nullptr, fill, d_planes_out};
+    if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec) || !plane_args_ok(planes, true, ids_len)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    void *const out[ROW_OUTS] = {d_rows_out, d_mask_out, nullptr, d_row_seq_out, d_row_first_out};
+    return run_row_planes_device(h, RowsSource{spec, d_ids, ids_len, d_id_offsets}, nseq, out, rows_cap, d_row_offsets_out, planes, (hipStream_t)stream, "IdsToRowsPlanes kernels");
+}
+
+int64_t IdsToRowsPlanesBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int stride,
+                             int max_rows_per_seq, int flags, int32_t *rows_out, uint8_t *mask_out, int32_t *row_seq_out, int32_t *row_first_out, int64_t rows_cap,
+                             int64_t *row_offsets_out, int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out)
+{
+    Handle *h = as_handle(p);
+    RowsSpec spec;
+    if (!h || !rows_spec(row_len, cls_id, sep_id, pad_id, stride, max_rows_per_seq, flags, &spec)) return BF_E_ARG;
+    return run_rows_host(h, ids, id_offsets, nseq, spec, rows_out, mask_out, row_seq_out, row_first_out, rows_cap, row_offsets_out, PlaneArgs{nplanes, src, nullptr, fill, planes_out});
+}
+
+int IdsToPairRowsPlanesBatchDevice(void *p, const int32_t *d_ids_a, int64_t ids_a_len, const int64_t *d_off_a, const int32_t *d_ids_b, int64_t ids_b_len,
+                                   const int64_t *d_off_b, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride,
+                                   int max_rows_per_pair, int flags, int32_t *d_rows_out, uint8_t *d_mask_out, uint8_t *d_type_out, int32_t *d_row_seq_out,
+                                   int32_t *d_row_first_b_out, int64_t rows_cap, int64_t *d_row_offsets_out, int nplanes, const int32_t *const *d_src_a,
+                                   const int32_t *const *d_src_b, const int32_t *fill, int32_t *const *d_planes_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    PairsSpec spec;
+    const PlaneArgs planes{nplanes, d_src_a, d_src_b, fill, d_planes_out};
+    if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec) || !plane_args_ok(planes, false, 0)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    void *const out[ROW_OUTS] = {d_rows_out, d_mask_out, d_type_out, d_row_seq_out, d_row_first_b_out};
+    return run_row_planes_device(h, PairsSource{spec, d_ids_a, d_ids_b, ids_a_len, ids_b_len, d_off_a, d_off_b}, nseq, out, rows_cap, d_row_offsets_out, planes,
+                                 (hipStream_t)stream, "IdsToPairRowsPlanes kernels");
+}
+
+int64_t IdsToPairRowsPlanesBatch(void *p, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq, int row_len, int cls_id,
+                                 int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags, int32_t *rows_out, uint8_t *mask_out,
+                                 uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out, int64_t rows_cap, int64_t *row_offsets_out, int nplanes,
+                                 const int32_t *const *src_a, const int32_t *const *src_b, const int32_t *fill, int32_t *const *planes_out)
+{
+    Handle *h = as_handle(p);
+    PairsSpec spec;
+    if (!h || !pairs_spec(row_len, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, flags, &spec)) return BF_E_ARG;
+    return run_pairs_host(h, ids_a, off_a, ids_b, off_b, nseq, spec, rows_out, mask_out, type_out, row_seq_out, row_first_b_out, rows_cap, row_offsets_out,
+                          PlaneArgs{nplanes, src_a, src_b, fill, planes_out});
+}
+
+/* ---- additive: an item's byte span -> the cells of each of its rows that hold the span's ends (k_rows_span), over planes that are on the device */
+int RowsSpanCellsBatchDevice(void *p, const int32_t *d_start_plane, const int32_t *d_end_plane, int row_len, int64_t rows_cap, const int64_t *d_nrows,
+                             const int32_t *d_row_seq, int64_t nseq, const int32_t *d_span_first, const int32_t *d_span_last, int none_cell,
+                             int32_t *d_start_cell_out, int32_t *d_end_cell_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h || row_len < 1 || row_len > ROWS_MAX_LEN || rows_cap < 0 || nseq < 0) return BF_E_ARG;
+    if (rows_cap > 0 && (!d_start_plane || !d_end_plane || !d_span_first || !d_span_last || !d_start_cell_out || !d_end_cell_out)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    if (rows_cap > 0)
+        launch_rows_span(RowsSpanParams{d_start_plane, d_end_plane, row_len, rows_cap, d_nrows, d_row_seq, nseq, d_span_first, d_span_last, none_cell,
+                                        d_start_cell_out, d_end_cell_out, &h->misc()->status}, s);
+    return hip_ok(hipGetLastError(), "RowsSpanCells kernel") ? 0 : BF_E_DEVICE;
 }
 
 /* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */

@@ -273,6 +273,29 @@ struct RowStageParams {
 template <class S> void launch_rowstage_count(const RowStageParams<S> &p, hipStream_t s);
 template <class S> void launch_rowstage_map(const RowStageParams<S> &p, hipStream_t s);
 template <class S> void launch_rowstage_fill(const RowStageParams<S> &p, hipStream_t s);
+// IdsToRowsPlanesBatch / IdsToPairRowsPlanesBatch (additive): up to ROWS_MAX_PLANES int32 arrays parallel to the ids, gathered into planes with the
+// layout of `rows` by k_rowstage_planes (bf_rowstage_body.h), behind the map (and the fill) of the same call.  A struct of its own: the three
+// kernels above keep their arguments where they are.
+constexpr int ROWS_MAX_PLANES = 4;
+template <class S>
+struct RowPlanesParams {
+    RowStageParams<S> st;        // the call's row stage as its kernels saw it: source, row offsets, capacity, a row's item and first id
+    int nplanes;
+    const int32_t *src[2][ROWS_MAX_PLANES];      // [side][k] (bf_rows.h CELL_SIDE_A / CELL_SIDE_B): parallel to the ids of that side (RowsSource: side 0 alone); NULL = that side's cells take the fill
+    int32_t fill[ROWS_MAX_PLANES];               // what a cell without an id gets
+    int32_t *out[ROWS_MAX_PLANES];               // [rows_cap * row_len] each; NULL = not taken
+};
+template <class S> void launch_rowstage_planes(const RowPlanesParams<S> &p, hipStream_t s);
+
+// RowsSpanCellsBatchDevice (additive; bf_rows.h span_*, k_rows_span in bf_kernels_rows.hip): the cells of every row that hold the two ends of its item's byte span
+struct RowsSpanParams {
+    const int32_t *start_plane, *end_plane; int row_len;
+    int64_t rows_cap; const int64_t *nrows;      // rows below min(rows_cap, *nrows); nrows NULL = rows_cap
+    const int32_t *row_seq; int64_t nseq;        // a row's item (NULL: row r is item r); an item outside [0, nseq) has no span (status bit 3)
+    const int32_t *span_first, *span_last; int none_cell;
+    int32_t *start_cell, *end_cell; int *status;
+};
+void launch_rows_span(const RowsSpanParams &p, hipStream_t s);
 unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU (bf_kernels_rows.hip)
 
 // IdsToPackedRowsBatch (additive; bf_packed.h has the lane code, bf_kernels_packed.hip the kernels): several sequences per row, with a segment

@@ -7,5 +7,6 @@ namespace bfa {
 template void launch_rowstage_count<PairsSource>(const RowStageParams<PairsSource> &p, hipStream_t s);
 template void launch_rowstage_map<PairsSource>(const RowStageParams<PairsSource> &p, hipStream_t s);
 template void launch_rowstage_fill<PairsSource>(const RowStageParams<PairsSource> &p, hipStream_t s);
+template void launch_rowstage_planes<PairsSource>(const RowPlanesParams<PairsSource> &p, hipStream_t s);
 
 } // namespace bfa

@@ -116,6 +116,14 @@ BF_HD PairCell pairs_cell(const PairRow &w, int j)
     return c;
 }
 
+static_assert(PAIRS_CELL_A == CELL_SIDE_A && PAIRS_CELL_B == CELL_SIDE_B, "a pair cell's `what` is the side of its CellWhere");
+// pairs_cell as a CellWhere (bf_rows.h): side = PAIRS_CELL_A / PAIRS_CELL_B and the index within that sequence, or side < 0
+BF_HD CellWhere pairs_where(const PairRow &w, int j)
+{
+    const PairCell c = pairs_cell(w, j);
+    return CellWhere{c.at, c.what >= 0 ? c.what : -1};
+}
+
 // the id, the mask byte and the type byte of a cell; seq_a / seq_b = the ids of its pair
 BF_HD int32_t pairs_cell_value(const PairsSpec &s, const PairCell &c, const int32_t *seq_a, const int32_t *seq_b, uint8_t *mask, uint8_t *type)
 {
@@ -156,6 +164,12 @@ struct PairsSource {
     BF_HD int32_t cell(const Item &it, const Row &w, int j, uint8_t *mask, uint8_t *type) const
     {
         return pairs_cell_value(spec, pairs_cell(w, j), it.seq_a, it.seq_b, mask, type);
+    }
+    BF_HD CellWhere where(const Item &it, const Row &w, int j) const
+    {
+        CellWhere c = pairs_where(w, j);
+        c.at += c.side == CELL_SIDE_B ? it.seq_b - ids_b : it.seq_a - ids_a;
+        return c;
     }
 };
 

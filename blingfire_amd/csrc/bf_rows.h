@@ -79,6 +79,18 @@ BF_HD int64_t rows_cell(const RowsSpec &s, int64_t row_first, int64_t n, int j)
     return i < k ? row_first + i : ROWS_CELL_SEP;
 }
 
+// where a cell reads: `side` = the id array (0; bf_pairs.h: PAIRS_CELL_A / PAIRS_CELL_B) and `at` = the index of the element in it, or
+// side < 0 = the cell holds no id (a special or padding).  What the companion planes gather by (k_rowstage_planes).
+struct CellWhere { int64_t at; int side; };
+constexpr int CELL_SIDE_A = 0, CELL_SIDE_B = 1;          // the sides there are: the first index of RowPlanesParams::src (a source with one id array has side A alone)
+
+// rows_cell as a CellWhere: `at` = the index within the sequence
+BF_HD CellWhere rows_where(const RowsSpec &s, int64_t row_first, int64_t n, int j)
+{
+    const int64_t c = rows_cell(s, row_first, n, j);
+    return CellWhere{c, c >= 0 ? CELL_SIDE_A : -1};
+}
+
 // the id and the mask byte of a cell; `seq` = the ids of its sequence
 BF_HD int32_t rows_cell_value(const RowsSpec &s, int64_t cell, const int32_t *seq, uint8_t *mask)
 {
@@ -113,6 +125,7 @@ BF_HD int64_t rows_find_seq(const int64_t *row_off, int64_t nseq, int64_t r)
 //   first(it, k)   the first id of the item's row k
 //   row(it, first) that row laid out once for all of its cells
 //   cell(it, w, j) the id, the mask byte and the type byte of its cell j
+//   where(it, w, j) which element of which id array that cell reads (CellWhere, `at` counted from the start of the array), or "not an id"
 struct RowsSource {
     static constexpr bool HAS_TYPE = false;
     RowsSpec spec;
@@ -139,6 +152,46 @@ struct RowsSource {
         *type = 0;
         return rows_cell_value(spec, rows_cell(spec, w.first, it.n, j), it.seq, mask);
     }
+    BF_HD CellWhere where(const Item &it, const Row &w, int j) const
+    {
+        CellWhere c = rows_where(spec, w.first, it.n, j);
+        c.at += it.seq - ids;
+        return c;
+    }
 };
+
+// ---- span cells (RowsSpanCellsBatchDevice): a byte span [a, z] (z inclusive) -> the cells of a row whose tokens hold its two ends.  S / E = the
+// row's cells of a start plane and an end plane; only cells with S[j] >= 0 count.  start = max { j : S[j] <= a }, end = min { j : E[j] >= z };
+// no order of the planes is assumed: every cell is looked at, the candidates are combined with max / min (k_rows_span: across lanes).
+constexpr int ROWS_SPAN_NO_END = 0x7fffffff;
+
+struct SpanAcc { int32_t start, end; };          // the best candidates so far: -1 / ROWS_SPAN_NO_END = none
+
+BF_HD SpanAcc span_none() { return SpanAcc{-1, ROWS_SPAN_NO_END}; }
+
+// what cell j contributes
+BF_HD SpanAcc span_cell(int32_t s, int32_t e, int32_t a, int32_t z, int j)
+{
+    const bool in = s >= 0;
+    return SpanAcc{in && s <= a ? j : -1, in && e >= z ? j : ROWS_SPAN_NO_END};
+}
+
+BF_HD SpanAcc span_combine(const SpanAcc &x, const SpanAcc &y) { return SpanAcc{x.start > y.start ? x.start : y.start, x.end < y.end ? x.end : y.end}; }
+
+// the two cells of a row from what all of its cells contributed: none_cell twice unless the span is one (0 <= a <= z) and both ends were found
+BF_HD void span_result(const SpanAcc &acc, int32_t a, int32_t z, int none_cell, int32_t *start_cell, int32_t *end_cell)
+{
+    const bool ok = a >= 0 && z >= a && acc.start >= 0 && acc.end != ROWS_SPAN_NO_END;
+    *start_cell = ok ? acc.start : none_cell;
+    *end_cell = ok ? acc.end : none_cell;
+}
+
+// lanes that share a row in k_rows_span: a wave (64), or the smallest power of two >= row_len where that is at most 32
+BF_HD int span_group(int row_len)
+{
+    int g = 1;
+    while (g < row_len && g < 64) g <<= 1;
+    return g;
+}
 
 } // namespace bfa

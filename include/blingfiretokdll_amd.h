@@ -218,6 +218,76 @@ BF_API int64_t IdsToPairRowsBatch(void *ModelPtr, const int32_t *ids_a, const in
                            int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out,
                            int64_t rows_cap, int64_t *row_offsets_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): COMPANION PLANES for IdsToRowsBatch / IdsToPairRowsBatch -- up
+ * to BF_ROWS_MAX_PLANES int32 arrays that run parallel to the ids (the d_starts_out / d_ends_out of TextToIdsWithOffsetsBatchDevice as they
+ * are, per-token labels, word indices, ...) are gathered into int32 planes of [rows_cap * row_len] cells with the layout of d_rows_out, in the
+ * same call.  Element i of a source belongs to d_ids[i].  Plane k of nplanes: a cell that holds id number i of its sequence q gets
+ * src[k][off[q] + i]; a cell that holds cls_id, a separator or padding gets fill[k].
+ * IdsToRowsPlanesBatchDevice / IdsToRowsPlanesBatch take every argument of IdsToRowsBatchDevice / IdsToRowsBatch, with the same meaning, checks,
+ * status bits and capacity rules, and behind d_row_offsets_out: nplanes, d_src, fill, d_planes_out -- three HOST arrays of nplanes entries whose
+ * values travel to the kernel by value (d_src[k] and d_planes_out[k] are device pointers in the Device form, host pointers in the host form).
+ * d_src[k] is read for at most ids_len elements, and only at cells that hold an id.  d_planes_out[k] may be NULL: that plane is skipped.
+ * IdsToPairRowsPlanesBatchDevice / IdsToPairRowsPlanesBatch are the same over IdsToPairRowsBatchDevice / IdsToPairRowsBatch, with d_src_a (parallel
+ * to d_ids_a) and d_src_b (parallel to d_ids_b).  Either array pointer, or any entry of one, may be NULL: the cells of that side then take fill[k]
+ * -- the extractive-QA form is offsets over the context (B) alone and the fill over the question.
+ * BF_E_ARG for nplanes outside 0 .. BF_ROWS_MAX_PLANES, a NULL fill or d_planes_out with nplanes > 0 and, in the rows form, a NULL d_src or
+ * d_src[k] with ids_len > 0 (host form: with any id to read); and for whatever the base call refuses.
+ * The calls are supersets of the base calls: rows, mask, type, row_seq, row_first and the row offsets are byte for byte what the base call
+ * writes for the same arguments; with nplanes = 0 the call is the base call; a size query is every output and every plane NULL.  No row
+ * r >= rows_cap of a plane is written; a sequence read as empty (BfLastStatus bit 3) has no id cells; rows dropped from a plane the caller takes
+ * set BfLastStatus bit 0.  After BfReserve(h, max_docs >= nseq, ...) the Device forms allocate nothing.  Every pointer needs only the natural
+ * alignment of its type: with row_len % 4 == 0 and every taken plane aligned to 16 bytes a lane makes one 16-byte store per plane, otherwise
+ * it writes one cell; the sources are read element by element, because a sequence starts anywhere.
+ * Host forms: each source is staged beside the ids (read, like them, from the side's first offset to its largest one); BF_E_CAPACITY with
+ * complete offsets and nothing else written, exactly as the base calls.  Packed rows (IdsToPackedRowsBatch) have no companion planes. */
+#define BF_ROWS_MAX_PLANES 4
+BF_API int IdsToRowsPlanesBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                               int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags,
+                               int32_t *d_rows_out, uint8_t *d_mask_out, int32_t *d_row_seq_out, int32_t *d_row_first_out,
+                               int64_t rows_cap, int64_t *d_row_offsets_out,
+                               int nplanes, const int32_t *const *d_src, const int32_t *fill, int32_t *const *d_planes_out, void *stream);
+BF_API int64_t IdsToRowsPlanesBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                             int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags,
+                             int32_t *rows_out, uint8_t *mask_out, int32_t *row_seq_out, int32_t *row_first_out,
+                             int64_t rows_cap, int64_t *row_offsets_out,
+                             int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out);
+BF_API int IdsToPairRowsPlanesBatchDevice(void *ModelPtr, const int32_t *d_ids_a, int64_t ids_a_len, const int64_t *d_off_a,
+                                   const int32_t *d_ids_b, int64_t ids_b_len, const int64_t *d_off_b, int64_t nseq,
+                                   int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags,
+                                   int32_t *d_rows_out, uint8_t *d_mask_out, uint8_t *d_type_out, int32_t *d_row_seq_out, int32_t *d_row_first_b_out,
+                                   int64_t rows_cap, int64_t *d_row_offsets_out,
+                                   int nplanes, const int32_t *const *d_src_a, const int32_t *const *d_src_b, const int32_t *fill,
+                                   int32_t *const *d_planes_out, void *stream);
+BF_API int64_t IdsToPairRowsPlanesBatch(void *ModelPtr, const int32_t *ids_a, const int64_t *off_a, const int32_t *ids_b, const int64_t *off_b, int64_t nseq,
+                                 int row_len, int cls_id, int sep_id, int pad_id, int mode, int max_a, int stride, int max_rows_per_pair, int flags,
+                                 int32_t *rows_out, uint8_t *mask_out, uint8_t *type_out, int32_t *row_seq_out, int32_t *row_first_b_out,
+                                 int64_t rows_cap, int64_t *row_offsets_out,
+                                 int nplanes, const int32_t *const *src_a, const int32_t *const *src_b, const int32_t *fill, int32_t *const *planes_out);
+
+/* additive (no counterpart in the reference; this comment is the specification): SPAN CELLS -- an item's byte span, e.g. an answer inside a
+ * context, as token cells of each of its rows.  Device only: it reads a start plane and an end plane that are already on the device
+ * ([rows_cap * row_len] int32 each, e.g. two companion planes of the calls above over the tokenizer's starts and ends with fill -1), whatever
+ * call laid the rows out: rows and pair rows alike.
+ * Rows r < min(rows_cap, *d_nrows) are processed (d_nrows NULL = rows_cap rows; d_row_offsets_out + nseq of the row call before is the
+ * intended d_nrows: nothing is read back); no entry at or past that bound of either output is written.  Row r belongs to item
+ * q = d_row_seq ? d_row_seq[r] : r; a q outside [0, nseq) gives none_cell twice and sets BfLastStatus bit 3.
+ * With a = d_span_first[q] and z = d_span_last[q] -- byte offsets in the coordinates of the planes, the last byte INCLUSIVE like the
+ * tokenizer's ends -- S and E the row's cells of the two planes and C = { j : S[j] >= 0 }:
+ *     a < 0, or z < a, or no j in C with S[j] <= a, or no j in C with E[j] >= z:   start_cell = end_cell = none_cell
+ *     otherwise:   start_cell = max { j in C : S[j] <= a },   end_cell = min { j in C : E[j] >= z }
+ * The definition assumes no ordering of the planes and neither does the kernel.  For offsets that rise along the row it is what the usual QA
+ * preprocessing computes: the last token that starts at or before the answer and the first token that ends at or behind it.  With none_cell =
+ * the cell of cls_id, an answer that is not fully inside the window gets the [CLS] cell (a window that begins behind a, or ends in front of z,
+ * lacks one of the two candidates).  A token whose start is negative -- the dummy prefix of a SentencePiece model, the fill over a question --
+ * is never an answer cell.
+ * BF_E_ARG for row_len outside 1 .. 1 << 20, a negative rows_cap or nseq, a NULL plane, span array or output with rows_cap > 0, and a NULL
+ * ModelPtr (any live handle, as for the row calls).  The call clears the status word first, like every batch call, enqueues on `stream`, does
+ * not synchronise, allocates nothing and returns 0 or BF_E_*.  A wave shares a row (a power-of-two slice of a wave when row_len <= 32). */
+BF_API int RowsSpanCellsBatchDevice(void *ModelPtr, const int32_t *d_start_plane, const int32_t *d_end_plane, int row_len,
+                             int64_t rows_cap, const int64_t *d_nrows, const int32_t *d_row_seq, int64_t nseq,
+                             const int32_t *d_span_first, const int32_t *d_span_last, int none_cell,
+                             int32_t *d_start_cell_out, int32_t *d_end_cell_out, void *stream);
+
 /* additive (no counterpart in the reference; this comment is the specification): PACKED rows -- several sequences share a row, a segment
  * plane keeps a model's attention block-diagonal and a position plane restarts at every sequence.  Where IdsToRowsBatch pads every sequence
  * to a row of its own, this fills rows greedily and in order.
