@@ -135,6 +135,8 @@ def lib():
         L.BfSetLexStats.argtypes = [c_void_p, c_int]
         L.BfSetBpePoolBytes.restype = c_int64
         L.BfSetBpePoolBytes.argtypes = [c_void_p, c_int64]
+        L.BfWorkspaceGrows.restype = c_int
+        L.BfWorkspaceGrows.argtypes = [c_void_p]
         L.BfReserve.restype = c_int
         L.BfReserve.argtypes = [c_void_p, c_int64, c_int64, c_int]
         L.NormalizeSpaces.restype = c_int
@@ -934,6 +936,17 @@ def reserve(h, max_docs, max_bytes, want_offsets=False):
     r = lib().BfReserve(c_void_p(h), int(max_docs), int(max_bytes), int(bool(want_offsets)))
     if r != 0:
         raise RuntimeError("BfReserve failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+
+
+def workspace_grows():
+    """diagnostic (BfWorkspaceGrows): (device allocations the library's workspaces and tables have made in this process, those of them for the
+    long-document workspace of the words modes, which reserve() leaves out).  A device-resident call on a reserved handle moves neither,
+    or only the second."""
+    out = (ctypes.c_longlong * 2)()
+    r = lib().BfWorkspaceGrows(out)
+    if r != 0:
+        raise RuntimeError("BfWorkspaceGrows failed (%d)" % r)
+    return int(out[0]), int(out[1])
 
 
 def last_kernel_ms(h):

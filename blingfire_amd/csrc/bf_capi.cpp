@@ -48,6 +48,9 @@ bool hip_ok(hipError_t e, const char *what)
     return false;
 }
 
+// BfWorkspaceGrows (bf_internal.h): the hipMalloc calls of DevBuf::reserve in this process, retries included; [1]: those for Handle::w_long alone
+std::atomic<long long> g_workspace_grows[2];
+
 struct DevBuf {
     void *p = nullptr; size_t cap = 0;
     DevBuf() = default;
@@ -55,16 +58,19 @@ struct DevBuf {
     DevBuf &operator=(const DevBuf &) = delete;
     ~DevBuf() { release(); }
     // Grow-only.  Growing is a hipMalloc + hipFree (both synchronise the device): callers that must not synchronise size the
-    // workspaces once with BfReserve.
-    bool reserve(size_t bytes)
+    // workspaces once with BfReserve.  is_long: the buffer is Handle::w_long, which BfReserve leaves out (counted apart)
+    bool reserve(size_t bytes, bool is_long = false)
     {
         if (bytes <= cap) return true;
         size_t want = bytes + bytes / 8 + 256;
         void *q = nullptr;
+        const auto count = [is_long]() { g_workspace_grows[0].fetch_add(1, std::memory_order_relaxed); if (is_long) g_workspace_grows[1].fetch_add(1, std::memory_order_relaxed); };
         // the contents are never kept across a grow; the old buffer goes first when both do not fit
+        count();
         if (hipMalloc(&q, want) != hipSuccess) {
             (void)hipGetLastError();
             if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+            count();
             if (!hip_ok(hipMalloc(&q, want), "hipMalloc(workspace)")) return false;
         } else if (p) (void)hipFree(p);
         p = q; cap = want; return true;
@@ -461,10 +467,14 @@ bool reserve_flat_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool
     return !want_off || (h->w_espan.reserve((size_t)(total_bytes + 64) * 4) && h->w_hspan.reserve((size_t)(total_bytes + 64) * 8) && h->w_chard.reserve((size_t)(ndocs + 1) * 4));
 }
 
-// the lane-per-document lexer (bf_lex.h): class stream, dirty flags; the offsets API and the words modes: source offsets and spans
+// the documents k_prep_wp hands to k_prep_wp_long: those of more than 2048 bytes
+int64_t prep_long_cap(int64_t total_bytes) { return total_bytes / 2048 + 1; }
+
+// the lane-per-document lexer (bf_lex.h): class stream, dirty flags, the list of long documents; the offsets API and the words modes: source offsets and spans
 bool reserve_lane_lexer_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off)
 {
-    if (!h->w_cls.reserve((size_t)(total_bytes + 64) * 2) || !h->w_flags.reserve((size_t)((total_bytes >> 10) + 2) * 8)) return false;
+    if (!h->w_cls.reserve((size_t)(total_bytes + 64) * 2) || !h->w_flags.reserve((size_t)((total_bytes >> 10) + 2) * 8) ||
+        !h->w_preplong.reserve((size_t)prep_long_cap(total_bytes) * 8)) return false;
     return !want_off || (h->w_srcoff.reserve((size_t)(total_bytes + 64) * 4) && h->w_span.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 8));
 }
 
@@ -496,7 +506,7 @@ bool reserve_sp_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool w
 // "no allocation later": sizes and order are part of that contract.
 bool reserve_ids_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool want_off, int words = 0, bool with_long = true)
 {
-    if (const LongCaps lc = long_caps(h, ndocs, total_bytes, words); with_long && lc.thresh > 0 && !h->w_long.reserve(lc.bytes)) return false;
+    if (const LongCaps lc = long_caps(h, ndocs, total_bytes, words); with_long && lc.thresh > 0 && !h->w_long.reserve(lc.bytes, true)) return false;
     if (!h->w_nchars.reserve((size_t)(ndocs + 1) * 4) || !h->w_counts.reserve((size_t)(ndocs + 1) * 4) ||
         !h->w_bsums.reserve((size_t)(scan_nblocks(ndocs) + 1) * 8) || !h->w_tmp.reserve((size_t)(total_bytes + 8 * ndocs + 64) * 4)) return false;
     if (h->m.kind != KIND_WP) return reserve_sp_workspaces(h, ndocs, total_bytes, want_off);
@@ -634,8 +644,8 @@ StepTail enqueue_lane_lexer(const Step &st)
                     m.wbd_charmap_multi ? 1 : 0, h->w_cls.as<uint16_t>(), st.want_off ? h->w_srcoff.as<int32_t>() : nullptr, h->w_nchars.as<int32_t>()};
     if (words) { pp.cpmap = DevCpMap{h->t_wcp_l1.as<uint16_t>(), h->t_wcp_pages.as<uint32_t>()}; pp.has_multi = 0; }   // no charmap (tokdll:476-499)
     // long documents are decoded by sixteen waves each (k_prep_wp_long)
-    pp.long_cap = total_bytes / 2048 + 1;
-    pp.long_list = h->w_preplong.reserve((size_t)pp.long_cap * 8) ? h->w_preplong.as<int64_t>() : nullptr;
+    pp.long_cap = prep_long_cap(total_bytes);
+    pp.long_list = h->w_preplong.as<int64_t>();          // (reserve_lane_lexer_workspaces)
     pp.long_count = &misc->prep_long_n;
     if (ndocs > 0) launch_prep_wp(pp, total_bytes, h->w_flags.as<unsigned long long>(), s);
     st.record(EV_PREP);
@@ -1104,6 +1114,17 @@ int64_t run_host_locked(Handle *h, const char *text, const int64_t *doc_off, int
     return nids;
 }
 
+// What run_words_device needs beyond the lexer's workspaces (BfReserve sizes the same): the list of the documents of more than 1024 tokens
+// (k_w2t_len_long / k_w2t_copy_long) and, where the call tokenises itself (the Device forms), the tags, spans and their offsets -- a words-mode
+// document has at most one token per byte.
+int64_t w2t_long_cap(int64_t total_bytes) { return total_bytes / 1024 + 2; }
+bool reserve_words_workspaces(Handle *h, int64_t ndocs, int64_t total_bytes, bool tokenise)
+{
+    if (!h->w_w2tlong.reserve((size_t)w2t_long_cap(total_bytes) * 8)) return false;
+    return !tokenise || (h->w_ids.reserve((size_t)(total_bytes + 1) * 4) && h->w_starts.reserve((size_t)(total_bytes + 1) * 4) &&
+                         h->w_ends.reserve((size_t)(total_bytes + 1) * 4) && h->w_idoff.reserve((size_t)(ndocs + 1) * 8));
+}
+
 // TextToWords for a batch resident on the device: lexer in words mode -> spans -> lengths -> scan -> byte gather.
 // The word tags / spans stay in the handle's buffers; d_out may be NULL to size only (d_out_off is always filled).
 int run_words_device(Handle *h, const char *d_text, const int64_t *d_doc_off, int64_t ndocs, int64_t total_bytes,
@@ -1112,9 +1133,8 @@ int run_words_device(Handle *h, const char *d_text, const int64_t *d_doc_off, in
     if (h->m.kind != KIND_WP) return BF_E_UNSUPPORTED;
     if (h->m.lexer_void) { g_last_error = "TextToWords / TextToSentences: a moore-multi-dfa lexer answers -1 to every input (the single-document calls return that)"; return BF_E_UNSUPPORTED; }
     if (ndocs < 0 || total_bytes < 0 || !d_doc_off || !d_out_off) return BF_E_ARG;
+    if (!reserve_words_workspaces(h, ndocs, total_bytes, tokenise)) return BF_E_DEVICE;
     if (tokenise) {
-        if (!h->w_ids.reserve((size_t)(total_bytes + 1) * 4) || !h->w_starts.reserve((size_t)(total_bytes + 1) * 4) ||
-            !h->w_ends.reserve((size_t)(total_bytes + 1) * 4) || !h->w_idoff.reserve((size_t)(ndocs + 1) * 8)) return BF_E_DEVICE;
         int rc = run_device(h, d_text, d_doc_off, ndocs, total_bytes, h->w_ids.as<int32_t>(), total_bytes, h->w_idoff.as<int64_t>(), 0x7fffffff, 0, s,
                             h->w_starts.as<int32_t>(), h->w_ends.as<int32_t>(), mode);
         if (rc != 0) return rc;
@@ -1123,8 +1143,8 @@ int run_words_device(Handle *h, const char *d_text, const int64_t *d_doc_off, in
                 h->w_counts.as<int32_t>(), d_out_off, (uint8_t *)d_out, out_cap, mode == 2 ? h->w_nchars.as<int32_t>() : nullptr};
     // documents of many tokens are measured and assembled by sixteen waves each (k_w2t_len_long / k_w2t_copy_long); their numbers: w2t_len_long_n
     // (cleared by run_device's begin_launch above) and w2t_copy_long_n (cleared below)
-    p.long_cap = total_bytes / 1024 + 2;
-    p.long_list = h->w_w2tlong.reserve((size_t)p.long_cap * 8) ? h->w_w2tlong.as<int64_t>() : nullptr;
+    p.long_cap = w2t_long_cap(total_bytes);
+    p.long_list = h->w_w2tlong.as<int64_t>();
     p.long_count = &h->misc()->w2t_len_long_n;
     if (tokenise) {
         if (ndocs > 0) { if (mode == 2) launch_s2t_len(p, s); else launch_w2t_len(p, s); }
@@ -1630,19 +1650,27 @@ bool ensure_dict_tables(Handle *h)
     return ok;
 }
 
+// a handle whose [pos-dict] DictGetInfoBatch looks keys up in
+bool has_dict(const Model &m) { return m.has_seg && !m.k2i.empty(); }
+
+// the tables and the per-key workspaces of a lookup of nkeys keys (BfReserve: max_docs keys)
+bool reserve_dict_workspaces(Handle *h, int64_t nkeys)
+{
+    return ensure_dict_tables(h) && h->w_counts.reserve((size_t)(nkeys + 1) * 4) && h->w_bsums.reserve((size_t)(scan_nblocks(nkeys) + 1) * 8) &&
+           h->w_dids.reserve((size_t)(nkeys + 1) * 4) && h->w_dret.reserve((size_t)(nkeys + 1) * 4);
+}
+
 int run_dict_device(Handle *h, const int32_t *d_keys, const int64_t *d_key_off, int64_t nkeys, int32_t *d_ret, int32_t *d_info_ids,
                     int32_t *d_vals, int64_t vals_cap, int64_t *d_val_off, hipStream_t s, bool size)
 {
     const Model &m = h->m;
-    if (!m.has_seg || m.k2i.empty()) return BF_E_UNSUPPORTED;
+    if (!has_dict(m)) return BF_E_UNSUPPORTED;
     // the reference looks a key up as it is only for (no ignore-case, left-to-right) dictionaries, lower-cases for ignore-case ones and
     // reverses only right-to-left ones (FADictInterpreter_t.h:203-205, FAFsmConst.h DIR_L2R = 0, DIR_R2L = 1): the other combinations are
     // refused here instead of being looked up wrongly
     if (m.dict_direction != 0 && m.dict_direction != 1) { g_last_error = "dictionary lookup: direction other than l2r, r2l is not supported"; return BF_E_UNSUPPORTED; }
     if (nkeys < 0 || !d_key_off || !d_val_off) return BF_E_ARG;
-    const int nblocks = scan_nblocks(nkeys);
-    if (!ensure_dict_tables(h) || !h->w_counts.reserve((size_t)(nkeys + 1) * 4) || !h->w_bsums.reserve((size_t)(nblocks + 1) * 8) ||
-        !h->w_dids.reserve((size_t)(nkeys + 1) * 4) || !h->w_dret.reserve((size_t)(nkeys + 1) * 4)) return BF_E_DEVICE;
+    if (!reserve_dict_workspaces(h, nkeys)) return BF_E_DEVICE;
     DictParams p;
     p.D.T = h->t_dict.as<uint64_t>(); p.D.initial = m.dict.initial_base; p.D.initial_final = m.dict_raw.is_final[(size_t)m.dict_raw.initial] ? 1 : 0;
     p.D.cls_l1 = h->t_dk_l1.as<uint16_t>(); p.D.cls_pages = h->t_dk_pages.as<uint32_t>();
@@ -2478,9 +2506,12 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     // both forms of the WordPiece path: the wave program's workspaces and (words = 1 skips use_wave()'s early return) the class stream and flags of
     // the lane-per-document kernels, which TextToWords / TextToSentences, lexers outside the unit form and BfSetVariant(2) run -- no hipMalloc
     // (= device synchronisation) inside a later call of either kind
-    if (!reserve_ids_workspaces(h, max_docs, max_bytes, want_offsets != 0)) return BF_E_DEVICE;
+    // want_offsets sizes the offsets API as well, not instead: a BPE model's ids-only call takes the wave program, whose hand-back flags the offsets path lacks
+    if (!reserve_ids_workspaces(h, max_docs, max_bytes, false) || (want_offsets && !reserve_ids_workspaces(h, max_docs, max_bytes, true))) return BF_E_DEVICE;
     // (not the long-document workspace of the words modes, w_long: 40 .. 56 bytes per cell, allocated by the first words call that is that large)
-    if (h->m.kind == KIND_WP && !reserve_ids_workspaces(h, max_docs, max_bytes, true, 1, false)) return BF_E_DEVICE;
+    if (h->m.kind == KIND_WP && (!reserve_ids_workspaces(h, max_docs, max_bytes, true, 1, false) || !reserve_words_workspaces(h, max_docs, max_bytes, true))) return BF_E_DEVICE;
+    // DictGetInfoBatchDevice: documents = keys; the tables of the [pos-dict] go up here instead of inside the first lookup
+    if (has_dict(h->m) && !reserve_dict_workspaces(h, max_docs)) return BF_E_DEVICE;
     return 0;
 }
 
@@ -2639,6 +2670,14 @@ int BfLastStatus(void *p)
 }
 
 const char *BfLastError(void) { return g_last_error.c_str(); }
+
+/* diagnostics: the device allocations of the library's workspaces and tables in this process (bf_internal.h) */
+int BfWorkspaceGrows(long long out[2])
+{
+    if (!out) return BF_E_ARG;
+    out[0] = g_workspace_grows[0].load(std::memory_order_relaxed); out[1] = g_workspace_grows[1].load(std::memory_order_relaxed);
+    return 0;
+}
 
 /* experiments: instrumentation counters of the lexer kernel (BF_LEX_STATS=1), accumulated since LoadModel */
 int BfLexStats(void *p, unsigned long long *out, int n)

@@ -10,6 +10,11 @@ extern "C" {
  * Lane-per-document kernels: [0] walk trips [1] lane-steps [2] event rounds [3] event lanes [4] fetch rounds [5] idle lane-steps
  * [6..8] cycles in walk / event / fetch */
 BF_API int BfLexStats(void *ModelPtr, unsigned long long *out, int n);
+/* the device allocations of the library's workspaces and tables in this process: out[0] = hipMalloc calls made (every workspace and table goes
+ * through one grow-only buffer type), out[1] = those of them for the long-document workspace of the words modes, which BfReserve leaves out.
+ * A ...BatchDevice call that keeps the promise of BfReserve leaves out[0] - out[1] where it was.  Torch's allocator and other processes cannot
+ * move it.  Returns 0, or BF_E_ARG for a NULL out. */
+BF_API int BfWorkspaceGrows(long long out[2]);
 /* experiments / A-B runs.  Low byte: 3 = default (flat-form WordPiece models: the flat program, bf_flat.h, for batches of >= 1,024 documents and
  * >= 1 MiB, else the wave program, bf_wave.h); 4 = the flat program for every batch; 5 = never; 2 = the lane-per-document WordPiece kernels
  * (bf_lex.h) also for unit-form lexers; bit 0x40 = BPE without its wave program.  The higher bits carry tuning values and the test knobs of the

@@ -444,10 +444,24 @@ BF_API long long BfBpeFallbackDocs(void *ModelPtr);   /* diagnostics: documents 
 BF_API int BfModelKind(void *ModelPtr);
 
 /* Optional: size every workspace of the handle for batches of up to max_docs documents / max_bytes bytes of text now, so that
- * later ...BatchDevice calls of that size allocate nothing (workspaces only ever grow; growing means hipMalloc, which
- * synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
+ * later ...BatchDevice calls of that size allocate nothing, the first one included (workspaces only ever grow; growing means hipMalloc,
+ * which synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
  * Every kind of handle has the workspaces of IdsToRowsBatchDevice and IdsToPairRowsBatchDevice (the same ones) and those of
  * IdsToPackedRowsBatchDevice (about 36 bytes per sequence) sized for max_docs sequences or pairs (an [i2w]-only handle has no others).
+ * A WordPiece handle also gets the buffers of TextToWordsBatchDevice / TextToSentencesBatchDevice (12 bytes per byte of text and 8 per
+ * document); a handle with a [pos-dict] gets its lookup tables uploaded and the workspaces of DictGetInfoBatchDevice for max_docs keys; a
+ * handle with [w2h] those of WordHyphenationBatchDevice for max_docs words.
+ * The limits of the promise:
+ *  - one workspace is left out: the long-document workspace of the words modes (40 .. 56 bytes per cell, about one cell per byte of text).
+ *    It is sized for the worst case from the batch's size alone, before any kernel has looked for a long document: with the default
+ *    knobs EVERY first TextToWordsBatchDevice / TextToSentencesBatchDevice call of a given size (documents, bytes) allocates it, whatever
+ *    its documents look like -- a batch of uniform short lines too -- and every later call of a larger size allocates it again.  Such
+ *    calls are not safe inside a stream capture.  The only way to avoid the allocation today is the no_long knob of BfSetVariant
+ *    (bit 30, 0x40000000; bf_internal.h), which keeps every document on one lane;
+ *  - it holds for the BfSetVariant value and the BfSetBpePoolBytes size in force when BfReserve was called (the workspaces are those of the
+ *    program these select): after either call, call BfReserve again;
+ *  - the built-in models of the words calls (ModelPtr == NULL there) have no handle a caller could reserve: load wbd.bin / sbd.bin and pass
+ *    the handle.
  * Returns 0 or BF_E_*. */
 BF_API int BfReserve(void *ModelPtr, int64_t max_docs, int64_t max_bytes, int want_offsets);
 /* BPE models: the size of the pool from which documents with very many candidate arcs claim their working memory (about 16 bytes per

@@ -169,6 +169,16 @@ def test_reserve_then_no_growth():
         bf.reserve(h, 10, 100)                             # never shrinks
         b = bf.text_to_ids_batch(h, docs, 32, 100)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        # ... and the device-resident call within the bounds makes the library allocate nothing, the first time and the second (BfWorkspaceGrows)
+        import torch
+        text, off = bf.pack_docs(docs)
+        d_text, d_off = torch.from_numpy(text.copy()).cuda(), torch.from_numpy(off).cuda()
+        grows0 = bf.workspace_grows()
+        for _ in range(2):
+            ids, id_off = bf.text_to_ids_batch_device(h, d_text, d_off, 32, 100)
+            torch.cuda.synchronize()
+            assert bf.workspace_grows() == grows0
+            assert np.array_equal(id_off.cpu().numpy(), a[1]) and np.array_equal(ids[:int(a[1][-1])].cpu().numpy(), a[0])
     finally:
         bf.free_model(h)
 

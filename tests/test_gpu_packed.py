@@ -360,9 +360,11 @@ def test_10_repeated_call_after_reserve_allocates_nothing():
     hm = bf.load_model(bfutil.model_path("bert_base_tok.bin"))
     try:
         bf.reserve(hm, len(docs), len(text))
+        grows0 = bf.workspace_grows()
         d_text = torch.from_numpy(text.copy()).cuda(); d_off = torch.from_numpy(off).cuda()
         a = bf.encode_packed_batch_device(hm, d_text, d_off, 16, sp["cls_id"], sp["sep_id"], sp["pad_id"], sp["unk"], rows_cap=len(docs))
         torch.cuda.synchronize()
+        assert bf.workspace_grows() == grows0, "the FIRST call on the reserved handle made the library allocate device memory (BfWorkspaceGrows)"
         R = int(a[6].item())
         assert 0 < R < len(docs)
         a = [t.cpu().numpy() for t in a]
@@ -371,6 +373,7 @@ def test_10_repeated_call_after_reserve_allocates_nothing():
         torch.cuda.synchronize()
         free1 = torch.cuda.mem_get_info()[0]
         assert free1 == free0, "the device's free memory moved by %d bytes across a reserved call" % (free0 - free1)
+        assert bf.workspace_grows() == grows0, "the repeated call made the library allocate device memory (BfWorkspaceGrows)"
         for i, (x, y) in enumerate(zip(a, b)):
             n = R if i < 3 else R + 1 if i == 3 else len(x)
             assert np.array_equal(x[:n], y.cpu().numpy()[:n])

@@ -385,15 +385,18 @@ def test_7_repeated_call_after_reserve_allocates_nothing():
     hm = bf.load_model(bfutil.model_path("bert_base_tok.bin"))
     try:
         bf.reserve(hm, len(oa) - 1, max(len(ta), len(tb)))
+        grows0 = bf.workspace_grows()
         d = [torch.from_numpy(x.copy()).cuda() for x in (ta, oa, tb, ob)]
         a = bf.encode_pairs_batch_device(hm, *d, 32, sp["cls_id"], sp["sep_id"], sp["pad_id"], sp["unk"])
         torch.cuda.synchronize()
+        assert bf.workspace_grows() == grows0, "the FIRST call on the reserved handle made the library allocate device memory (BfWorkspaceGrows)"
         a = [t.cpu().numpy() for t in a]
         free0 = torch.cuda.mem_get_info()[0]
         b = bf.encode_pairs_batch_device(hm, *d, 32, sp["cls_id"], sp["sep_id"], sp["pad_id"], sp["unk"])
         torch.cuda.synchronize()
         free1 = torch.cuda.mem_get_info()[0]
         assert free1 == free0, "the device's free memory moved by %d bytes across a reserved call" % (free0 - free1)
+        assert bf.workspace_grows() == grows0, "the repeated call made the library allocate device memory (BfWorkspaceGrows)"
         for x, y in zip(a, b):
             assert np.array_equal(x, y.cpu().numpy())
         assert a[2].max() == 1 and (a[1].sum(axis=1) >= 3).all()

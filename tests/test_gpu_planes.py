@@ -687,16 +687,19 @@ def test_8_repeated_calls_after_reserve_allocate_nothing():
     hm = bf.load_model(bfutil.model_path("bert_base_tok.bin"))
     try:
         bf.reserve(hm, len(oc) - 1, max(len(tq), len(tc)), True)
+        grows0 = bf.workspace_grows()
         ans = dev(np.full(len(docs), 4)), dev(np.full(len(docs), 9))
         args = (d_tq, d_oq, d_tc, d_oc, 32, sp["cls_id"], sp["sep_id"], sp["pad_id"], 6, 5, sp["unk"])
         a = bf.encode_qa_batch_device(hm, *args, d_ans_first=ans[0], d_ans_last=ans[1])
         torch.cuda.synchronize()
+        assert bf.workspace_grows() == grows0, "the FIRST call on the reserved handle made the library allocate device memory (BfWorkspaceGrows)"
         a = [t.cpu().numpy() for t in a]
         free0 = torch.cuda.mem_get_info()[0]
         b = bf.encode_qa_batch_device(hm, *args, d_ans_first=ans[0], d_ans_last=ans[1])
         torch.cuda.synchronize()
         free1 = torch.cuda.mem_get_info()[0]
         assert free1 == free0, "the device's free memory moved by %d bytes across a reserved call" % (free0 - free1)
+        assert bf.workspace_grows() == grows0, "the repeated call made the library allocate device memory (BfWorkspaceGrows)"
         for x, y in zip(a, b):
             assert np.array_equal(x, y.cpu().numpy())
         assert (a[8] != 0).any() and (a[6] >= 0).any()

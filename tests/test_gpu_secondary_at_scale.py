@@ -81,13 +81,15 @@ class Case:
         return rc, out, off
 
     # ---- Device form
-    def run_dev(self, cap, null_out=False, side_stream=False):
+    def run_dev(self, cap, null_out=False, side_stream=False, stream=None):
+        """stream: the torch stream to run on (a caller's own); else a fresh side stream or the current one"""
         import torch
         dev = torch.device("cuda:0")
         if self._dev_pre is None:
             self._dev_pre = [torch.from_numpy(a).to(dev) if isinstance(a, np.ndarray) else a for a in self.pre]
             torch.cuda.synchronize()
-        stream = torch.cuda.Stream() if side_stream else torch.cuda.current_stream()
+        if stream is None:
+            stream = torch.cuda.Stream() if side_stream else torch.cuda.current_stream()
         tdt = torch.uint8 if self.want.dtype == np.uint8 else torch.int32
         with torch.cuda.stream(stream):
             out = torch.full((self.T + SLACK,), CANARY[self.want.dtype], dtype=tdt, device=dev)
