@@ -11,7 +11,7 @@ raise / return the reference's error value, loudly.
 """
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -108,6 +108,9 @@ def lib():
         L.RowsSpanCellsBatchDevice.restype = c_int
         L.RowsSpanCellsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                                c_void_p, c_void_p, c_void_p]
+        L.RowsMlmMaskBatchDevice.restype = c_int
+        L.RowsMlmMaskBatchDevice.argtypes = [c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int, c_void_p] + [c_double] * 3 + [c_int] * 4 + [
+            c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]
         L.IdsToPackedRowsBatch.restype = c_int64
         L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
         L.IdsToPackedRowsBatchDevice.restype = c_int
@@ -900,6 +903,72 @@ def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None
     d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
     d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
     return encode_packed_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
+
+
+def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None, nrows=None, special_ids=(), select_prob=0.15, mask_prob=0.8, random_prob=0.1,
+                         mask_id, rand_range, ignore_label=-100, seed, epoch=0, inplace=False, stream=None):
+    """Masked-language-model masking of rows that are on the device (RowsMlmMaskBatchDevice): -> (ids int32[R, L], labels int32[R, L]).
+    rows: int32[R, L] from any of the row calls; mask: uint8[R, L] or None; seg: int32[R, L] (the packed call's segment plane) or None; a cell
+    outside the mask, in segment 0 or holding one of special_ids (at most 8) is never masked.  starts / ends: int32[R, L] planes of token
+    offsets with a negative fill (both or neither): with them a run of byte-adjacent tokens is selected as a whole (whole-word masking for
+    WordPiece models), without them every token on its own.  nrows: an int64 tensor of one element on the device that bounds the rows (a view
+    such as row_offsets[-1:]), or None (every row).  A selected cell gets labels = its id and ids = mask_id with mask_prob, a random id
+    of rand_range = (lo, hi), hi exclusive, with random_prob, its own id otherwise; every other cell keeps its id and gets ignore_label.
+    The result is a function of (seed, epoch, row, cell) and the row alone: the same call gives the same result, another epoch another one.
+    inplace: ids is `rows` itself, overwritten.  Rows at or past nrows of a fresh ids tensor are copies of `rows`, of labels ignore_label.
+    Like every batch call it clears the handle's status word first."""
+    import torch
+    dev = rows.device
+    for what, t in (("rows", rows), ("seg", seg), ("starts", starts), ("ends", ends)):
+        _dev_i32(t, dev, "rows_mlm_mask_device: " + what)
+    if rows.dim() != 2 or any(t is not None and t.shape != rows.shape for t in (mask, seg, starts, ends)):
+        raise ValueError("rows_mlm_mask_device: rows is an [R, L] plane; mask, seg, starts and ends have its shape")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev):
+        raise ValueError("rows_mlm_mask_device: mask must be a contiguous torch.uint8 tensor on %s" % dev)
+    if (starts is None) != (ends is None):
+        raise ValueError("rows_mlm_mask_device: starts and ends come together")
+    if nrows is not None and (not isinstance(nrows, torch.Tensor) or nrows.dtype != torch.int64 or nrows.numel() != 1 or nrows.device != dev):
+        raise ValueError("rows_mlm_mask_device: nrows must be a torch.int64 tensor of one element on %s" % dev)
+    special_ids = [int(x) for x in special_ids]
+    if len(special_ids) > 8:
+        raise ValueError("rows_mlm_mask_device: at most 8 special ids")
+    R, L = rows.shape
+    ids = rows if inplace else rows.clone()
+    labels = torch.full((R, L), int(ignore_label), dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    c_special = (c_int32 * max(len(special_ids), 1))(*special_ids)
+
+    def addr(t):
+        return None if t is None else t.data_ptr()
+    r = lib().RowsMlmMaskBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), addr(starts), addr(ends), len(special_ids), c_special,
+                                     float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]), int(rand_range[1]), int(ignore_label),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, ids.data_ptr(), labels.data_ptr(), c_void_p(s))
+    if r != 0:
+        raise RuntimeError("RowsMlmMaskBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return ids, labels
+
+
+def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mask_id, rand_range, seed, epoch=0, whole_word=False, packed=False, unk=0,
+                            special_ids=None, select_prob=0.15, mask_prob=0.8, random_prob=0.1, ignore_label=-100, rows_cap=None):
+    """Text in HBM -> the tensors of a masked-language-model step, nothing on the host: encode_batch_device (with return_offsets=whole_word)
+    or, with packed=True, encode_packed_batch_device, and rows_mlm_mask_device on one stream.  Returns the base call's tuple with the masked
+    input ids in place of its rows and `labels` (int32[R, L], ignore_label where nothing is predicted) appended:
+    (ids, mask, row_doc, row_offsets[, starts, ends], labels), or packed (ids, seg, pos, row_first_seq, seq_row, seq_col, nrows, labels).
+    special_ids None: the cls_id, sep_id and pad_id there are.  Packed rows mask inside the segment plane; they have no offset planes, so
+    packed=True with whole_word=True raises ValueError.  rows_cap is the packed call's (None: its one read-back)."""
+    if packed and whole_word:
+        raise ValueError("encode_mlm_batch_device: packed rows have no offset planes, so no whole-word masking")
+    if special_ids is None:
+        special_ids = [i for i in (_special(cls_id), _special(sep_id), _special(pad_id)) if i >= 0]
+    kw = dict(special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id, rand_range=rand_range,
+              ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True)
+    if packed:
+        out = encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
+        ids, labels = rows_mlm_mask_device(h, out[0], seg=out[1], nrows=out[6], **kw)
+        return (ids, *out[1:], labels)
+    out = encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, return_offsets=whole_word)
+    ids, labels = rows_mlm_mask_device(h, out[0], mask=out[1], starts=out[4] if whole_word else None, ends=out[5] if whole_word else None, nrows=out[3][-1:], **kw)
+    return (ids, *out[1:], labels)
 
 
 def dict_get_info_batch(h, keys):

@@ -111,7 +111,7 @@ struct PinBuf {
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device, in run_row_stage_device, in RowsSpanCellsBatchDevice and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
+//                            size pass of run_w2h_device, in run_row_stage_device, in RowsSpanCellsBatchDevice, in RowsMlmMaskBatchDevice and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
 //                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
@@ -2377,6 +2377,26 @@ int RowsSpanCellsBatchDevice(void *p, const int32_t *d_start_plane, const int32_
         launch_rows_span(RowsSpanParams{d_start_plane, d_end_plane, row_len, rows_cap, d_nrows, d_row_seq, nseq, d_span_first, d_span_last, none_cell,
                                         d_start_cell_out, d_end_cell_out, &h->misc()->status}, s);
     return hip_ok(hipGetLastError(), "RowsSpanCells kernel") ? 0 : BF_E_DEVICE;
+}
+
+/* ---- additive: masked-language-model masking of rows that are on the device (bf_mlm.h, k_rows_mlm): masked ids and labels, token by token or whole words */
+int RowsMlmMaskBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows, const uint8_t *d_mask, const int32_t *d_seg,
+                           const int32_t *d_start_plane, const int32_t *d_end_plane, int nspecial, const int32_t *special_ids, double select_prob, double mask_prob,
+                           double random_prob, int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch, int32_t *d_ids_out,
+                           int32_t *d_labels_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    MlmSpec spec;
+    if (!h || row_len < 1 || row_len > MLM_MAX_LEN || rows_cap < 0 || (d_start_plane != nullptr) != (d_end_plane != nullptr)) return BF_E_ARG;
+    if (!mlm_spec(nspecial, special_ids, select_prob, mask_prob, random_prob, mask_id, rand_lo, rand_hi, ignore_label, seed, epoch, &spec)) return BF_E_ARG;
+    if (rows_cap > 0 && (!d_rows || (!d_ids_out && !d_labels_out))) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    if (rows_cap > 0)
+        launch_rows_mlm(RowsMlmParams{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, d_start_plane, d_end_plane, spec, d_ids_out, d_labels_out}, s);
+    return hip_ok(hipGetLastError(), "RowsMlmMask kernel") ? 0 : BF_E_DEVICE;
 }
 
 /* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */

@@ -12,6 +12,7 @@
 #include "bf_rows.h"
 #include "bf_pairs.h"
 #include "bf_packed.h"
+#include "bf_mlm.h"
 #include "bf_variant.h"
 
 namespace bfa {
@@ -297,6 +298,17 @@ struct RowsSpanParams {
 };
 void launch_rows_span(const RowsSpanParams &p, hipStream_t s);
 unsigned rows_blocks(int64_t items);      // blocks of 256 lanes for `items` lanes, a grid-stride loop beyond 8 blocks per CU (bf_kernels_rows.hip)
+
+// RowsMlmMaskBatchDevice (additive; bf_mlm.h has the lane code, k_rows_mlm in bf_kernels_mlm.hip): masked ids and labels of rows that are already there
+struct RowsMlmParams {
+    const int32_t *rows; int row_len;
+    int64_t rows_cap; const int64_t *nrows;      // rows below min(rows_cap, *nrows); nrows NULL = rows_cap
+    const uint8_t *mask; const int32_t *seg;     // either may be NULL: every cell counts
+    const int32_t *start_plane, *end_plane;      // both or neither: whole-word units / every cell its own unit
+    MlmSpec spec;                                // thresholds, generator key, ids; the specials by value
+    int32_t *ids_out, *labels_out;               // [rows_cap * row_len] each, either may be NULL; ids_out may be `rows`
+};
+void launch_rows_mlm(const RowsMlmParams &p, hipStream_t s);
 
 // IdsToPackedRowsBatch (additive; bf_packed.h has the lane code, bf_kernels_packed.hip the kernels): several sequences per row, with a segment
 // and a position plane.  Every workspace array has nseq + 1 entries (index nseq = the end of the chain) unless noted.

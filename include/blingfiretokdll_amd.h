@@ -288,6 +288,48 @@ BF_API int RowsSpanCellsBatchDevice(void *ModelPtr, const int32_t *d_start_plane
                              const int32_t *d_span_first, const int32_t *d_span_last, int none_cell,
                              int32_t *d_start_cell_out, int32_t *d_end_cell_out, void *stream);
 
+/* additive (no counterpart in the reference; this comment is the specification): MLM MASKING -- the masked input ids and the labels of
+ * masked-language-model pretraining, token by token or whole words.  Device only: it reads rows that are already on the device
+ * ([rows_cap * row_len] int32), whatever call laid them out: rows, pair rows and packed rows alike.
+ * Rows r < min(rows_cap, *d_nrows) are processed (d_nrows NULL = rows_cap rows; d_row_offsets_out + nseq of a row call or d_nrows_out of the
+ * packed call is the intended d_nrows: nothing is read back); nothing at or past that bound of either output is written.  c = r * row_len + j
+ * is cell j of row r.
+ * The draw.  W(r, j) = Philox4x32-10(counter = {lo32(r), hi32(r), j, epoch}, key = {lo32(seed), hi32(seed)}), four 32-bit words; r is the
+ * row's index in the planes as an int64.  (Multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85, ten rounds, a round
+ * maps c to {hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)}, the key is bumped after every round.)  What a cell gets depends
+ * on (seed, r, j, epoch) and the row's own contents alone: not on the grid, the number of rows or the order of calls.
+ * Eligible cell.  d_mask == NULL or d_mask[c] != 0; and d_seg == NULL or d_seg[c] != 0 (the segment plane of the packed call: 0 = padding);
+ * and d_rows[c] is none of special_ids[0 .. nspecial) -- a HOST array of at most BF_MLM_MAX_SPECIAL ids whose values travel to the kernel by
+ * value (cls_id, sep_id, pad_id, ...).
+ * Units.  Without offset planes (d_start_plane and d_end_plane both NULL) every cell is its own unit: h(j) = j.  With both planes
+ * ([rows_cap * row_len] int32 each, e.g. two companion planes over the tokenizer's starts and ends with fill -1; S and E the row's cells), cell
+ * j >= 1 CONTINUES cell j - 1 when both cells are eligible, S[j-1] >= 0 and S[j] >= 0, and S[j] - 1 == E[j-1]: ends are inclusive like the
+ * tokenizer's, so this is byte adjacency -- `play` `##ing` is one unit, two tokens with white space between them are two.  h(j) = the largest
+ * j' <= j that does not continue.  This is whole-word masking for WordPiece models; for models whose tokens carry their white space (the
+ * SentencePiece family, byte-level BPE) the definition holds as written but its units need not coincide with words.
+ * Thresholds, computed on the host in double: Ts = (uint64) floor(select_prob * 4294967296.0), Tm and Tr the same of mask_prob and
+ * random_prob.  All comparisons below are in 64 bits, so a probability of 1 means always.
+ * Decision for an eligible cell j: it is selected iff W(r, h(j))[0] < Ts -- the unit's head decides, a unit is selected whole.  If selected,
+ * with w = W(r, j), the cell's OWN draw (the pieces of a word take their own action, as the usual whole-word collator has it):
+ *     labels = d_rows[c];   w[1] < Tm: ids = mask_id;   else w[1] < Tm + Tr: ids = rand_lo + (int32)(((uint64)w[2] * (uint64)(rand_hi - rand_lo)) >> 32);
+ *     else ids = d_rows[c]
+ * A cell that is not selected, and every cell that is not eligible: ids = d_rows[c], labels = ignore_label.
+ * Outputs.  d_ids_out and d_labels_out are [rows_cap * row_len] int32; either may be NULL, not both.  d_ids_out == d_rows (in place) is
+ * allowed: a lane reads only its own cell of d_rows before it writes it, what it needs of the neighbour comes from the planes.
+ * BF_E_ARG for row_len outside 1 .. 1 << 20, a negative rows_cap, a NULL d_rows or both outputs NULL with rows_cap > 0, one offset plane
+ * without the other, nspecial outside 0 .. BF_MLM_MAX_SPECIAL, a NULL special_ids with nspecial > 0, a probability outside [0, 1] (a NaN
+ * is), mask_prob + random_prob > 1.0, Tr > 0 without 0 <= rand_lo < rand_hi, and a NULL ModelPtr (any live handle, as for the row calls).
+ * The call clears the status word first, like every batch call, and sets no bit of it; it enqueues on `stream`, does not synchronise and
+ * returns 0 or BF_E_*.  It has no workspace: it allocates nothing, with and without BfReserve.  Every pointer needs only the natural
+ * alignment of its type.  A wave shares a row (a power-of-two slice of a wave when row_len <= 32) and walks it in chunks of as many cells.
+ * Not here: a cap on the predictions of a row, span (n-gram) masking, a host-buffer form, offset planes of packed rows. */
+#define BF_MLM_MAX_SPECIAL 8
+BF_API int RowsMlmMaskBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
+                           const uint8_t *d_mask, const int32_t *d_seg, const int32_t *d_start_plane, const int32_t *d_end_plane,
+                           int nspecial, const int32_t *special_ids, double select_prob, double mask_prob, double random_prob,
+                           int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch,
+                           int32_t *d_ids_out, int32_t *d_labels_out, void *stream);
+
 /* additive (no counterpart in the reference; this comment is the specification): PACKED rows -- several sequences share a row, a segment
  * plane keeps a model's attention block-diagonal and a position plane restarts at every sequence.  Where IdsToRowsBatch pads every sequence
  * to a row of its own, this fills rows greedily and in order.
