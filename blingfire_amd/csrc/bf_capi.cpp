@@ -110,9 +110,13 @@ struct PinBuf {
 
 // The handle's device control block (Handle::w_misc, 256 bytes, zeroed at LoadModel): every word a kernel shares with the host or with the next
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
-//   per launch   [0, 64)     on the stream, by the calls whose kernels use one of these words: begin_launch() in run_device (TextToIds, words, sentences), in the
-//                            size pass of run_w2h_device, in run_row_stage_device, in RowsSpanCellsBatchDevice, in RowsMlmMaskBatchDevice and in run_packed_device; clear_launch_words() in run_i2t_host and IdsToTextBatchDevice.  The fill passes
-//                            of the two-pass calls keep the size pass's words; normalize-spaces, hashes and the dictionary lookup use none.
+//   per launch   [0, 64)     on the stream, by begin_launch() in EVERY batch call that takes a handle of the caller's, whether its kernels use one of these
+//                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
+//                            calls on one handle): run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
+//                            run_row_stage_device, RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, run_packed_device, run_i2t_host and
+//                            IdsToTextBatchDevice.  The fill passes of the two-pass calls keep the size pass's words.  NormalizeSpacesBatch and
+//                            TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for its status, and their
+//                            kernels use none of the words: they clear nothing.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
 //   flat program [192, 224)  enqueue_flat(), on the stream, behind begin_launch(): no other program reads or writes them
@@ -371,8 +375,8 @@ Handle *make_handle(const uint8_t *img, size_t size)
 // Clears the per-launch words of the control block (MiscWords) on stream s.
 bool clear_launch_words(Handle *h, hipStream_t s) { return hip_ok(hipMemsetAsync(h->misc(), 0, MISC_LAUNCH_BYTES, s), "hipMemsetAsync"); }
 
-// Begins a launch: the per-launch words cleared, and the device status word is the one BfLastStatus reports from here on.  (The two IdsToText
-// calls only clear the words: BfLastStatus keeps answering for the batch before them, as it always did.)
+// Begins a launch: the per-launch words cleared, and the device status word is the one BfLastStatus reports from here on (not the word a
+// batch on the mapped host path left in Handle::small_status).  A memset on the stream: it allocates nothing, so the BfReserve promise holds.
 bool begin_launch(Handle *h, hipStream_t s)
 {
     if (!clear_launch_words(h, s)) return false;
@@ -1250,7 +1254,7 @@ int64_t run_i2t_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64
     hipStream_t s = h->stream;
     Staged st;
     int status = 0;
-    if (!clear_launch_words(h, s)) return BF_E_DEVICE;      // the status word the size pass reports an unknown id in
+    if (!begin_launch(h, s)) return BF_E_DEVICE;            // the status word the size pass reports an unknown id in
     const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s);
     if (rc != 0) return rc;
     const int64_t total = two_pass_host(s, nseq, h->w_idoff, h->w_text, 1, text_out, text_cap, text_off_out,
@@ -1683,6 +1687,7 @@ int run_dict_device(Handle *h, const int32_t *d_keys, const int64_t *d_key_off, 
     p.info_ids = d_info_ids ? d_info_ids : h->w_dids.as<int32_t>(); p.ret = d_ret ? d_ret : h->w_dret.as<int32_t>(); p.counts = h->w_counts.as<int32_t>();
     p.val_off = d_val_off; p.vals = d_vals; p.vals_cap = vals_cap;
     if (size) {
+        if (!begin_launch(h, s)) return BF_E_DEVICE;      // (the kernels set no bit: BfLastStatus behind a lookup is 0, not what the call before it left)
         if (nkeys > 0) launch_dict_ids(p, s);
         scan_counts(h, nkeys, d_val_off, s);
     }
@@ -2250,7 +2255,7 @@ int IdsToTextBatchDevice(void *p, const int32_t *d_ids, const int64_t *d_id_offs
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     hipStream_t s = (hipStream_t)stream;
-    if (!clear_launch_words(h, s)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
     int rc = run_i2t_device(h, d_ids, d_id_offsets, nseq, nullptr, 0, d_text_offsets_out, skip_special, s);
     if (rc != 0 || !d_text_out) return rc;
     return run_i2t_device(h, d_ids, d_id_offsets, nseq, d_text_out, text_cap, d_text_offsets_out, skip_special, s);

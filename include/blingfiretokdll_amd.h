@@ -468,10 +468,18 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
-/* Status word of the last batch call (synchronises): 0 = ok; bit 0 (1) = ids_cap overflow; bit 1 (2) and bit 4 (16) = an internal
+/* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
+ * tokenizer calls, words and sentences, the row, pair-row, plane, packed, span-cell and MLM calls, IdsToText, DictGetInfo and
+ * WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
+ * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
+ * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
+ * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
+ * no status.
+ * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow; bit 1 (2) and bit 4 (16) = an internal
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
- * BF_E_INTERNAL); bit 3 (8) = a document's byte range was outside [0, total_bytes] (Device calls: see the precondition above) and was
- * treated as empty.  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
+ * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
+ * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
+ * [0, ids_len]; the span cells: a row whose item is out of range).  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
  * terminate (a skipped start position left without an arc, FATokenSegmentationTools_1best_bpe_t.h:299-313) got 0 ids; bit 6 (64) = a
  * BPE document's arcs did not fit the pool and it got 0 ids (only the ...BatchDevice forms: the host-buffer calls grow the pool and
  * run again; BfSetBpePoolBytes). */
