@@ -4,6 +4,7 @@
 #include <cstring>
 #include <vector>
 #include "hosttest.h"
+#include "ws_sizes.h"
 #include "../../blingfire_amd/csrc/bf_w2h.h"
 
 using namespace bfa;
@@ -37,7 +38,7 @@ long long bft_w2h_batch(void *hv, const unsigned char *text, const long long *of
     if (hy_len == 0) return -1;
     const W2hTables t = tables_of(m);
     const long long total = n > 0 ? off[n] : 0;
-    std::vector<uint16_t> cls((size_t)(total + 2 * n + 64), 0xDEAD);
+    std::vector<uint16_t> cls((size_t)ws_w2h_cells(n, total), 0xDEAD);      // ws_sizes.h: what the product reserves
     std::vector<int> nch((size_t)n + 1), srcb((size_t)n + 1), lens((size_t)n + 1);
     for (long long w = 0; w < n; ++w) {
         if (off[w] < 0 || off[w + 1] < off[w] || off[w + 1] > total) { nch[(size_t)w] = srcb[(size_t)w] = 0; continue; }

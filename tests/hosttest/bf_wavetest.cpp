@@ -9,10 +9,19 @@
 #include "../../blingfire_amd/csrc/bf_flat_body.h"
 #include "../../blingfire_amd/csrc/bf_bpe_seg_body.h"
 #include "hosttest.h"
+#include "ws_sizes.h"
 
 #include <vector>
 
 using namespace bfa;
+
+// The 64 spare cells at the end of a workspace sized by ws_sizes.h are as they were filled: the programs write their own slots only.  The cells are
+// addressed by the FORMULA, not by what was allocated, so a workspace that is shorter than the product's is an access outside it under the sanitizers.
+template <class T> static bool spare_intact(const T *p, int64_t formula_cells, T fill)
+{
+    for (int64_t k = formula_cells - 64; k < formula_cells; ++k) if (p[k] != fill) return false;
+    return true;
+}
 
 template <class LDS, int NU, bool OFFS = false, int TRIM = 0>
 static void run_cfg(const WpWaveParams &p, int nwaves, int grab)
@@ -53,7 +62,7 @@ long bft_emu_wave_batch(void *hv, const uint8_t *text, long text_bytes, const in
     if (!m.error.empty() || m.kind != KIND_WP || !m.wave_ok) return -1;
     if (max_ids < 0) max_ids = 0;
     const int64_t total = text_bytes;                              // what the caller's buffer really holds
-    std::vector<int32_t> tmp((size_t)(total + 8 * ndocs + 64 + 8), -77), counts((size_t)ndocs + 1, -55);
+    std::vector<int32_t> tmp((size_t)ws_tmp_cells(ndocs, total), -77), counts((size_t)ws_doc_cells(ndocs), -55);      // ws_sizes.h: what the product reserves, no more
     unsigned long long next_doc = 0; int status = 0;
     WpWaveParams p;
     p.T = m.wbd_t2.data(); p.acts = m.acts_pool.data(); p.acts_n = (int)m.acts_pool.size();
@@ -72,6 +81,7 @@ long bft_emu_wave_batch(void *hv, const uint8_t *text, long text_bytes, const in
         else run_cfg<WvLds<1024, 256, 8>, 1>(p, nwaves, grab);
     }
     if (status) return -5;
+    if (!spare_intact(tmp.data(), ws_tmp_cells(ndocs, total), -77) || counts.data()[ws_doc_cells(ndocs) - 1] != -55) return -13;
     // k_scan + k_compact, restated
     long o = 0;
     for (long d = 0; d < ndocs; ++d) {
@@ -96,7 +106,7 @@ long bft_emu_wave_batch_offsets(void *hv, const uint8_t *text, long text_bytes, 
     if (!m.error.empty() || m.kind != KIND_WP || !m.wave_ok) return -1;
     if (max_ids < 0) max_ids = 0;
     const int64_t total = text_bytes;
-    std::vector<int32_t> tmp((size_t)(total + 8 * ndocs + 64 + 8), -77), counts((size_t)ndocs + 1, -55), span(2 * (size_t)(total + 8 * ndocs + 64 + 8), -77);
+    std::vector<int32_t> tmp((size_t)ws_tmp_cells(ndocs, total), -77), counts((size_t)ws_doc_cells(ndocs), -55), span(2 * (size_t)ws_tmp_cells(ndocs, total), -77);
     unsigned long long next_doc = 0, stats[16] = {0}; int status = 0;
     WpWaveParams p;
     p.T = m.wbd_t2.data(); p.acts = m.acts_pool.data(); p.acts_n = (int)m.acts_pool.size();
@@ -113,6 +123,7 @@ long bft_emu_wave_batch_offsets(void *hv, const uint8_t *text, long text_bytes, 
         else run_cfg<WvLds<1024, 256, 8, true>, 1, true, 15>(p, nwaves, grab);                     // shipped
     }
     if (status) return -5;
+    if (!spare_intact(tmp.data(), ws_tmp_cells(ndocs, total), -77) || !spare_intact(span.data(), 2 * ws_tmp_cells(ndocs, total), -77) || counts.data()[ws_doc_cells(ndocs) - 1] != -55) return -13;
     long o = 0;
     for (long d = 0; d < ndocs; ++d) {
         id_off[d] = o;
@@ -155,8 +166,8 @@ long bft_emu_bpe_wave_batch(void *hv, const uint8_t *text, long text_bytes, cons
     (void)text_bytes;
     const int mul = m.dict_has_charmap ? 2 : 1;
     const int64_t total = ndocs > 0 ? doc_off[ndocs] : 0;
-    const size_t cells = (size_t)(mul * (total + ndocs + 1) + 64);
-    std::vector<uint16_t> stream(cells, (uint16_t)0xEEEE); std::vector<int32_t> tmp(cells, -77), lens((size_t)ndocs + 1, 0), counts((size_t)ndocs + 1, -55), flags((size_t)ndocs + 1, -55);
+    const size_t cells = (size_t)ws_sp_cells(mul, ndocs, total), docs = (size_t)ws_doc_cells(ndocs);      // ws_sizes.h: what the product reserves, no more
+    std::vector<uint16_t> stream(cells + (size_t)ws_sp_stream_slack, (uint16_t)0xEEEE); std::vector<int32_t> tmp((size_t)ws_sp_tmp_cells(mul, ndocs, total), -77), lens(docs, 0), counts(docs, -55), flags(docs, -55);
     std::vector<uint16_t> st;
     for (long d = 0; d < ndocs; ++d) {
         const int n = (int)(doc_off[d + 1] - doc_off[d]);
@@ -166,7 +177,7 @@ long bft_emu_bpe_wave_batch(void *hv, const uint8_t *text, long text_bytes, cons
         memcpy(stream.data() + (size_t)mul * (size_t)(doc_off[d] + d), st.data(), st.size() * 2);
     }
     unsigned long long next_doc = 0; int status = 0;
-    std::vector<uint32_t> scratch(6 * cells, 0xABABABABu);
+    std::vector<uint32_t> scratch((size_t)ws_bpe_scratch_words((int64_t)cells), 0xABABABABu);
     BpeWaveParams p;
     p.T = m.dict.t64.data(); p.info = (const SegInfo *)m.seg_info.data(); p.initial = m.dict.initial_base; p.cls_delim = m.sp_delim_code; p.id_offset = m.id_offset;
     p.prio = m.kind == KIND_BPE_MERGES ? m.bpe_prio.data() : nullptr; p.place_id = m.kind == KIND_BPE_MERGES ? m.bpe_place_id.data() : nullptr;
@@ -240,8 +251,8 @@ long bft_emu_bpe_seg_batch(void *hv, const uint8_t *text, const int64_t *doc_off
     if (max_ids < 0) max_ids = 0;
     const int mul = m.dict_has_charmap ? 2 : 1;
     const int64_t total = ndocs > 0 ? doc_off[ndocs] : 0;
-    const size_t cells = (size_t)(mul * (total + ndocs + 1) + 64);
-    std::vector<uint16_t> stream(cells, (uint16_t)0xEEEE); std::vector<int32_t> tmp(cells, -77), spans(2 * cells, -77), lens((size_t)ndocs + 1, 0), counts((size_t)ndocs + 1, -55);
+    const size_t cells = (size_t)ws_sp_cells(mul, ndocs, total), docs = (size_t)ws_doc_cells(ndocs);
+    std::vector<uint16_t> stream(cells + (size_t)ws_sp_stream_slack, (uint16_t)0xEEEE); std::vector<int32_t> tmp((size_t)ws_sp_tmp_cells(mul, ndocs, total), -77), spans(2 * cells, -77), lens(docs, 0), counts(docs, -55);
     std::vector<uint16_t> st;
     for (long d = 0; d < ndocs; ++d) {
         const int n = (int)(doc_off[d + 1] - doc_off[d]);
@@ -316,7 +327,7 @@ static long emu_flat_batch(void *hv, const uint8_t *text, long text_bytes, const
     if (nranges <= 0) nranges = nwaves * 4;
     if (nranges > ndocs) nranges = (int)ndocs;
     if (nranges < 1) nranges = 1;
-    std::vector<int64_t> range_doc((size_t)nranges + 1, 0);
+    std::vector<int64_t> range_doc((size_t)ws_flat_range_cells(nranges), 0);
     if (!unsafe) {
         const int64_t first = doc_off[0], span = doc_off[ndocs] - first;
         for (int r = 0; r <= nranges; ++r) {
@@ -326,12 +337,13 @@ static long emu_flat_batch(void *hv, const uint8_t *text, long text_bytes, const
             range_doc[(size_t)r] = lo;
         }
     }
-    std::vector<uint32_t> ent((size_t)total + 64, 0xDEADBEEFu);
-    std::vector<int32_t> home((size_t)total + 64, -77), entcnt((size_t)ndocs + 1, -55), dstat((size_t)ndocs + 1, 0), list((size_t)ndocs + 1, -1);
-    std::vector<int64_t> entoff((size_t)ndocs + 1, -1);
-    std::vector<int32_t> tmp((size_t)(total + 8 * ndocs + 64 + 8), -77), counts((size_t)ndocs + 1, 0), counts_hard((size_t)ndocs + 1, -55);
-    std::vector<int32_t> span(offs ? 2 * (size_t)(total + 8 * ndocs + 64 + 8) : 2, -77);
-    std::vector<uint32_t> espan(offs ? (size_t)total + 64 : 1, 0xDEADBEEFu), hspan(offs ? 2 * ((size_t)total + 64) : 1, 0xDEADBEEFu);
+    const size_t cells = (size_t)ws_flat_cells(total), docs = (size_t)ws_doc_cells(ndocs);      // ws_sizes.h: what reserve_flat_workspaces reserves, no more
+    std::vector<uint32_t> ent(cells, 0xDEADBEEFu);
+    std::vector<int32_t> home(cells, -77), entcnt(docs, -55), dstat(docs, 0), list(docs, -1);
+    std::vector<int64_t> entoff(docs, -1);
+    std::vector<int32_t> tmp((size_t)ws_tmp_cells(ndocs, total), -77), counts(docs, 0), counts_hard(docs, -55);
+    std::vector<int32_t> span(offs ? 2 * (size_t)ws_tmp_cells(ndocs, total) : 2, -77);
+    std::vector<uint32_t> espan(offs ? cells : 1, 0xDEADBEEFu), hspan(offs ? 2 * cells : 1, 0xDEADBEEFu);
     unsigned long long next_range = 0, next_doc = 0; int status = 0;
     WpWaveCold cold;
     cold.cpmap = DevCpMap{m.wbd_cpmap.l1.data(), m.wbd_cpmap.pages.data()};
@@ -344,7 +356,7 @@ static long emu_flat_batch(void *hv, const uint8_t *text, long text_bytes, const
     fp.ent = ent.data(); fp.home = home.data(); fp.ent_off = entoff.data(); fp.ent_cnt = entcnt.data(); fp.dstat = dstat.data(); fp.cold = cold;
     fp.espan = offs ? espan.data() : nullptr;
     (void)wrec_cap_in;
-    std::vector<uint32_t> wrec((size_t)((total >> WF_REC_SHIFT) + 64) * 4, 0xDEADBEEFu); std::vector<int32_t> wrec_cnt((size_t)nranges * 2 + 2, 0);
+    std::vector<uint32_t> wrec((size_t)ws_flat_records(total, WF_REC_SHIFT) * 4, 0xDEADBEEFu); std::vector<int32_t> wrec_cnt((size_t)ws_flat_range_cells(nranges) * 2, 0);
     fp.wrec = wrec.data(); fp.wrec_cnt = wrec_cnt.data();
     if (ndocs > 0) {
         std::vector<uint32_t> lut(WF_LUT);
@@ -468,6 +480,7 @@ static long emu_flat_batch(void *hv, const uint8_t *text, long text_bytes, const
         delete mlds;
     }
     if (over_any) return -9;
+    if (!spare_intact(ent.data(), ws_flat_cells(total), 0xDEADBEEFu) || !spare_intact(home.data(), ws_flat_cells(total), -77) || !spare_intact(tmp.data(), ws_tmp_cells(ndocs, total), -77)) return -13;
     return o;
 }
 
