@@ -111,6 +111,8 @@ def lib():
         L.RowsMlmMaskBatchDevice.restype = c_int
         L.RowsMlmMaskBatchDevice.argtypes = [c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int, c_void_p] + [c_double] * 3 + [c_int] * 4 + [
             c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]
+        L.RowsMlmPredictionsBatchDevice.restype = c_int
+        L.RowsMlmPredictionsBatchDevice.argtypes = L.RowsMlmMaskBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
         L.IdsToPackedRowsBatch.restype = c_int64
         L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
         L.IdsToPackedRowsBatchDevice.restype = c_int
@@ -906,8 +908,12 @@ def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None
 
 
 def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None, nrows=None, special_ids=(), select_prob=0.15, mask_prob=0.8, random_prob=0.1,
-                         mask_id, rand_range, ignore_label=-100, seed, epoch=0, inplace=False, stream=None):
+                         mask_id, rand_range, ignore_label=-100, seed, epoch=0, inplace=False, stream=None, max_predictions=0):
     """Masked-language-model masking of rows that are on the device (RowsMlmMaskBatchDevice): -> (ids int32[R, L], labels int32[R, L]).
+    max_predictions = P > 0 (RowsMlmPredictionsBatchDevice): at most P predictions per row -- the selected units in the order of a key they
+    draw, as long as they fit, whole words whole -- and -> (ids, labels, pred_cells int32[R, P], pred_labels int32[R, P], pred_count int32[R]):
+    the predicted cells of a row in cell order, their original ids, and how many there are; behind them, and in rows at or past nrows,
+    cell 0 and ignore_label.  hidden.gather(1, pred_cells.long()[..., None].expand(-1, -1, H)) are the positions to project.  L <= 4096 then.
     rows: int32[R, L] from any of the row calls; mask: uint8[R, L] or None; seg: int32[R, L] (the packed call's segment plane) or None; a cell
     outside the mask, in segment 0 or holding one of special_ids (at most 8) is never masked.  starts / ends: int32[R, L] planes of token
     offsets with a negative fill (both or neither): with them a run of byte-adjacent tokens is selected as a whole (whole-word masking for
@@ -933,6 +939,11 @@ def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None
     if len(special_ids) > 8:
         raise ValueError("rows_mlm_mask_device: at most 8 special ids")
     R, L = rows.shape
+    if isinstance(max_predictions, bool) or not isinstance(max_predictions, (int, np.integer)) or max_predictions < 0:
+        raise ValueError("rows_mlm_mask_device: max_predictions is an integer >= 0")
+    P = int(max_predictions)
+    if P > 0 and (L > 4096 or P > 1 << 20):
+        raise ValueError("rows_mlm_mask_device: max_predictions needs rows of at most 4096 cells and is at most 1 << 20")
     ids = rows if inplace else rows.clone()
     labels = torch.full((R, L), int(ignore_label), dtype=torch.int32, device=dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
@@ -940,6 +951,17 @@ def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None
 
     def addr(t):
         return None if t is None else t.data_ptr()
+    if P > 0:
+        cells = torch.zeros((R, P), dtype=torch.int32, device=dev)
+        plabels = torch.full((R, P), int(ignore_label), dtype=torch.int32, device=dev)
+        count = torch.zeros((R,), dtype=torch.int32, device=dev)
+        r = lib().RowsMlmPredictionsBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), addr(starts), addr(ends), len(special_ids),
+                                                c_special, float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]),
+                                                int(rand_range[1]), int(ignore_label), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, ids.data_ptr(),
+                                                labels.data_ptr(), P, cells.data_ptr(), plabels.data_ptr(), count.data_ptr(), c_void_p(s))
+        if r != 0:
+            raise RuntimeError("RowsMlmPredictionsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+        return ids, labels, cells, plabels, count
     r = lib().RowsMlmMaskBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), addr(starts), addr(ends), len(special_ids), c_special,
                                      float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]), int(rand_range[1]), int(ignore_label),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, ids.data_ptr(), labels.data_ptr(), c_void_p(s))
@@ -949,26 +971,28 @@ def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None
 
 
 def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mask_id, rand_range, seed, epoch=0, whole_word=False, packed=False, unk=0,
-                            special_ids=None, select_prob=0.15, mask_prob=0.8, random_prob=0.1, ignore_label=-100, rows_cap=None):
+                            special_ids=None, select_prob=0.15, mask_prob=0.8, random_prob=0.1, ignore_label=-100, rows_cap=None, max_predictions=0):
     """Text in HBM -> the tensors of a masked-language-model step, nothing on the host: encode_batch_device (with return_offsets=whole_word)
     or, with packed=True, encode_packed_batch_device, and rows_mlm_mask_device on one stream.  Returns the base call's tuple with the masked
     input ids in place of its rows and `labels` (int32[R, L], ignore_label where nothing is predicted) appended:
     (ids, mask, row_doc, row_offsets[, starts, ends], labels), or packed (ids, seg, pos, row_first_seq, seq_row, seq_col, nrows, labels).
     special_ids None: the cls_id, sep_id and pad_id there are.  Packed rows mask inside the segment plane; they have no offset planes, so
-    packed=True with whole_word=True raises ValueError.  rows_cap is the packed call's (None: its one read-back)."""
+    packed=True with whole_word=True raises ValueError.  rows_cap is the packed call's (None: its one read-back).  max_predictions = P > 0
+    caps the predictions of a row and appends (pred_cells int32[R, P], pred_labels int32[R, P], pred_count int32[R]) behind labels, in all
+    three forms (rows_mlm_mask_device)."""
     if packed and whole_word:
         raise ValueError("encode_mlm_batch_device: packed rows have no offset planes, so no whole-word masking")
     if special_ids is None:
         special_ids = [i for i in (_special(cls_id), _special(sep_id), _special(pad_id)) if i >= 0]
     kw = dict(special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id, rand_range=rand_range,
-              ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True)
+              ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True, max_predictions=max_predictions)
     if packed:
         out = encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
-        ids, labels = rows_mlm_mask_device(h, out[0], seg=out[1], nrows=out[6], **kw)
-        return (ids, *out[1:], labels)
+        ids, *tail = rows_mlm_mask_device(h, out[0], seg=out[1], nrows=out[6], **kw)
+        return (ids, *out[1:], *tail)
     out = encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, return_offsets=whole_word)
-    ids, labels = rows_mlm_mask_device(h, out[0], mask=out[1], starts=out[4] if whole_word else None, ends=out[5] if whole_word else None, nrows=out[3][-1:], **kw)
-    return (ids, *out[1:], labels)
+    ids, *tail = rows_mlm_mask_device(h, out[0], mask=out[1], starts=out[4] if whole_word else None, ends=out[5] if whole_word else None, nrows=out[3][-1:], **kw)
+    return (ids, *out[1:], *tail)
 
 
 def dict_get_info_batch(h, keys):

@@ -2404,6 +2404,31 @@ int RowsMlmMaskBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t 
     return hip_ok(hipGetLastError(), "RowsMlmMask kernel") ? 0 : BF_E_DEVICE;
 }
 
+/* ---- additive: the same masking with a cap on the predictions of a row and the kept cells gathered (bf_mlm.h, k_rows_mlm_cap); max_pred = 0 is the base call */
+int RowsMlmPredictionsBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows, const uint8_t *d_mask, const int32_t *d_seg,
+                                  const int32_t *d_start_plane, const int32_t *d_end_plane, int nspecial, const int32_t *special_ids, double select_prob, double mask_prob,
+                                  double random_prob, int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch, int32_t *d_ids_out,
+                                  int32_t *d_labels_out, int max_pred, int32_t *d_pred_cell_out, int32_t *d_pred_label_out, int32_t *d_pred_count_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    MlmSpec spec;
+    const bool gathered = d_pred_cell_out || d_pred_label_out || d_pred_count_out;
+    if (!h || row_len < 1 || row_len > MLM_MAX_LEN || rows_cap < 0 || (d_start_plane != nullptr) != (d_end_plane != nullptr)) return BF_E_ARG;
+    if (max_pred < 0 || max_pred > MLM_CAP_MAX_PRED || (max_pred > 0 && row_len > MLM_CAP_MAX_LEN) || (max_pred == 0 && gathered)) return BF_E_ARG;
+    if (!mlm_spec(nspecial, special_ids, select_prob, mask_prob, random_prob, mask_id, rand_lo, rand_hi, ignore_label, seed, epoch, &spec)) return BF_E_ARG;
+    if (rows_cap > 0 && (!d_rows || (!d_ids_out && !d_labels_out && !gathered))) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    if (rows_cap > 0) {
+        const RowsMlmParams m{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, d_start_plane, d_end_plane, spec, d_ids_out, d_labels_out};
+        if (max_pred == 0) launch_rows_mlm(m, s);
+        else launch_rows_mlm_cap(RowsMlmCapParams{m, max_pred, d_pred_cell_out, d_pred_label_out, d_pred_count_out}, s);
+    }
+    return hip_ok(hipGetLastError(), "RowsMlmPredictions kernel") ? 0 : BF_E_DEVICE;
+}
+
 /* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */
 int IdsToPackedRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
                                int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,

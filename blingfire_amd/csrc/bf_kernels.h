@@ -310,6 +310,15 @@ struct RowsMlmParams {
 };
 void launch_rows_mlm(const RowsMlmParams &p, hipStream_t s);
 
+// RowsMlmPredictionsBatchDevice (additive; k_rows_mlm_cap in bf_kernels_mlm.hip): the same masking with at most max_pred > 0 predictions per row, gathered
+struct RowsMlmCapParams {
+    RowsMlmParams m;                             // as above; labels_out and ids_out may both be NULL when a gathered output is taken
+    int max_pred;                                // P, 1 .. MLM_CAP_MAX_PRED; row_len <= MLM_CAP_MAX_LEN
+    int32_t *pred_cell, *pred_label;             // [rows_cap * P] each: the kept cells in cell order and their original ids, then 0 / ignore_label; either may be NULL
+    int32_t *pred_count;                         // [rows_cap]: kept cells of the row; may be NULL
+};
+void launch_rows_mlm_cap(const RowsMlmCapParams &p, hipStream_t s);
+
 // IdsToPackedRowsBatch (additive; bf_packed.h has the lane code, bf_kernels_packed.hip the kernels): several sequences per row, with a segment
 // and a position plane.  Every workspace array has nseq + 1 entries (index nseq = the end of the chain) unless noted.
 struct PackedParams {

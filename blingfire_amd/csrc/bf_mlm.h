@@ -1,6 +1,7 @@
 // bf_mlm.h -- masked-language-model masking of rows that are already there: masked ids and labels, token by token or whole words.
 //
-// Additive (the reference has no counterpart; include/blingfiretokdll_amd.h RowsMlmMaskBatchDevice is the specification).  Every cell of a row
+// Additive (the reference has no counterpart; include/blingfiretokdll_amd.h RowsMlmMaskBatchDevice is the specification, RowsMlmPredictionsBatchDevice that
+// of the cap on a row's predictions at the end of this file).  Every cell of a row
 // draws from a counter-based generator keyed by (seed, row, cell, epoch) -- Philox4x32-10 -- so what a cell gets depends on nothing but its
 // own coordinates: not on the grid, not on the lane partition, not on the order of calls.  A unit is a cell (token masking) or a run of cells
 // whose tokens are byte-adjacent in the text (whole-word masking, over an offset plane pair); the draw of the unit's first cell selects the
@@ -126,6 +127,66 @@ BF_HD void mlm_decide(const MlmSpec &s, int64_t r, int j, int h, int32_t id, boo
     *label_out = id;
     if ((uint64_t)w.v[1] < s.t_mask) *id_out = s.mask_id;
     else if ((uint64_t)w.v[1] < s.t_mask_random) *id_out = s.rand_lo + (int32_t)(((uint64_t)w.v[2] * (uint64_t)s.rand_span) >> 32);
+}
+
+// ---- the cap on a row's predictions (RowsMlmPredictionsBatchDevice is the specification; k_rows_mlm_cap runs this per lane).  Every cell holds one
+// 64-bit word: the key of its unit when the unit is selected, MLM_CAP_NONE otherwise (no key is all ones: a head is below 2^32 - 1).
+constexpr int MLM_CAP_MAX_LEN = 4096;               // row_len above this is refused when max_pred > 0 (BF_MLM_CAP_MAX_LEN)
+constexpr int MLM_CAP_MAX_PRED = 1 << 20;           // max_pred above this is refused
+constexpr uint64_t MLM_CAP_NONE = ~(uint64_t)0;
+
+// K(h) = (W(r, h)[3] << 32) | h
+BF_HD uint64_t mlm_cap_key(uint32_t w3, int h) { return ((uint64_t)w3 << 32) | (uint64_t)(uint32_t)h; }
+
+// the word of a cell: the head's draw decides selection (word 0) and carries the key (word 3)
+BF_HD uint64_t mlm_cap_word(const MlmSpec &s, bool eligible, const Philox4 &wh, int h)
+{
+    return eligible && (uint64_t)wh.v[0] < s.t_select ? mlm_cap_key(wh.v[3], h) : MLM_CAP_NONE;
+}
+
+// the compare: a cell counts towards g(t) = #{cells : key < t} (MLM_CAP_NONE is below no t)
+BF_HD bool mlm_cap_below(uint64_t key, uint64_t t) { return key < t; }
+
+// The threshold search.  g is monotone, T = max { t : g(t) <= P } is built from the high bit down, and a cell is kept iff key < T (a cell with
+// key k is kept iff f = g(k + 1) <= P iff k + 1 <= T).  Only bits a key can have are probed: the 32 of W[3] and the hb = ceil(log2 row_len) low bits
+// of the head -- bits hb .. 31 of every key are zero, so the largest t with those bits zero separates the keys exactly as the largest t does
+// (were a key k with T <= k kept, k + 1 or, past the last head of its high word, (hi + 1) << 32 would be a larger such t).  That argument needs a
+// key behind T, so the search is run only where the row's selected cells exceed P; where they do not, every selected cell is kept.
+BF_HD int mlm_cap_head_bits(int row_len) { int b = 0; while (((int64_t)1 << b) < row_len) ++b; return b; }
+
+BF_HD int mlm_cap_rounds(int head_bits) { return 32 + head_bits; }
+
+// round i = rounds - 1 .. 0 probes T with one more bit set
+BF_HD uint64_t mlm_cap_probe(uint64_t T, int i, int head_bits) { return T | ((uint64_t)1 << (i < head_bits ? i : i - head_bits + 32)); }
+
+// n = g(probe): the probe becomes T when it still fits
+BF_HD uint64_t mlm_cap_take(uint64_t T, uint64_t probe, int n, int P) { return n <= P ? probe : T; }
+
+// kept: selected, and uncapped (P = 0), or the whole row fits, or in front of the threshold
+BF_HD bool mlm_cap_kept(uint64_t key, int selected_cells, int P, uint64_t T) { return key != MLM_CAP_NONE && (P == 0 || selected_cells <= P || key < T); }
+
+// the gather slot of a kept cell = the kept cells in front of it: those of the chunks before (the carry) and those of the lanes below it in its
+// own chunk.  `kept_lanes` has bit l set when lane l of the cell's group keeps its cell (the group's bits of a ballot, shifted down to bit 0).
+struct MlmCapCarry { int kept; };
+
+BF_HD MlmCapCarry mlm_cap_carry_none() { return MlmCapCarry{0}; }
+
+BF_HD int mlm_popcount64(uint64_t x)
+{
+    return __builtin_popcountll(x);
+}
+
+BF_HD int mlm_cap_slot(MlmCapCarry carry, uint64_t kept_lanes, int lane) { return carry.kept + mlm_popcount64(kept_lanes & (((uint64_t)1 << lane) - 1)); }
+
+BF_HD MlmCapCarry mlm_cap_carry_next(MlmCapCarry carry, uint64_t kept_lanes) { return MlmCapCarry{carry.kept + mlm_popcount64(kept_lanes)}; }
+
+// what a kept cell puts into ids: its own draw picks the action, as in mlm_decide
+BF_HD int32_t mlm_kept_id(const MlmSpec &s, int64_t r, int j, int32_t id)
+{
+    const Philox4 w = mlm_draw(s, r, j);
+    if ((uint64_t)w.v[1] < s.t_mask) return s.mask_id;
+    if ((uint64_t)w.v[1] < s.t_mask_random) return s.rand_lo + (int32_t)(((uint64_t)w.v[2] * (uint64_t)s.rand_span) >> 32);
+    return id;
 }
 
 } // namespace bfa

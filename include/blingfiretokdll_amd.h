@@ -322,13 +322,53 @@ BF_API int RowsSpanCellsBatchDevice(void *ModelPtr, const int32_t *d_start_plane
  * The call clears the status word first, like every batch call, and sets no bit of it; it enqueues on `stream`, does not synchronise and
  * returns 0 or BF_E_*.  It has no workspace: it allocates nothing, with and without BfReserve.  Every pointer needs only the natural
  * alignment of its type.  A wave shares a row (a power-of-two slice of a wave when row_len <= 32) and walks it in chunks of as many cells.
- * Not here: a cap on the predictions of a row, span (n-gram) masking, a host-buffer form, offset planes of packed rows. */
+ * Not here: span (n-gram) masking, a host-buffer form, offset planes of packed rows.  (A cap on the predictions of a row, with the kept cells
+ * gathered: RowsMlmPredictionsBatchDevice below.) */
 #define BF_MLM_MAX_SPECIAL 8
 BF_API int RowsMlmMaskBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
                            const uint8_t *d_mask, const int32_t *d_seg, const int32_t *d_start_plane, const int32_t *d_end_plane,
                            int nspecial, const int32_t *special_ids, double select_prob, double mask_prob, double random_prob,
                            int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch,
                            int32_t *d_ids_out, int32_t *d_labels_out, void *stream);
+
+/* additive (no counterpart in the reference; this comment is the specification): MLM PREDICTIONS -- RowsMlmMaskBatchDevice with a cap of
+ * max_pred predictions per row (max_predictions_per_seq of the BERT data pipeline) and the predicted cells gathered, so that the output
+ * projection of a masked language model runs on [rows, P] positions of a fixed shape instead of [rows, row_len].
+ * Every argument from d_rows to d_labels_out is RowsMlmMaskBatchDevice's, and so are, word for word: the rows processed
+ * (r < min(rows_cap, *d_nrows)), the draw W(r, j), eligibility, the units h(j), the thresholds, selection (W(r, h)[0] < Ts, a unit is selected
+ * whole) and the action of a cell from its own w[1], w[2].  New:
+ * Key.  A selected unit with head h has the 64-bit key K(h) = ((uint64)W(r, h)[3] << 32) | (uint32)h -- word 3 of the draw, which the base
+ * call does not use.  Keys of distinct units of a row differ because their heads differ.
+ * Count.  f(h) = the number of selected cells j' of the row with K(h(j')) <= K(h): the cells of the unit itself and of every selected unit
+ * with a smaller key.
+ * Cap.  max_pred = 0: every selected unit is kept.  max_pred = P > 0: a selected unit is kept iff f(h) <= P.  The kept units are therefore a
+ * prefix of the selected units in key order, cut in front of the first unit that no longer fits: a later, smaller unit is NOT taken after
+ * the cut.  A unit of more than P cells is never kept; where such a unit has the row's smallest key, the row has no predictions.  The rule
+ * depends on (seed, r, epoch) and the row alone, prefers no position of the row (the keys are draws), keeps whole words whole and needs no
+ * sequential walk.
+ * Cells.  A cell of a kept unit gets what a selected cell gets in the base call: labels = d_rows[c], ids by its own draw.  Every other cell
+ * -- a selected cell that the cap dropped included -- gets ids = d_rows[c], labels = ignore_label.  n_r = the kept cells of row r; n_r <= P.
+ * Where P >= the selected cells of every row, ids and labels are byte for byte the base call's.
+ * Gathered outputs (P > 0 only).  With j_0 < ... < j_{n_r - 1} the kept cells of row r in cell order:
+ *     d_pred_cell_out[r * P + k] = j_k;   d_pred_label_out[r * P + k] = the ORIGINAL d_rows[r * row_len + j_k] (also when the call runs in place);
+ *     for n_r <= k < P the two entries are 0 and ignore_label (a weight plane is label != ignore_label);   d_pred_count_out[r] = n_r
+ * Their shapes are [rows_cap * P], [rows_cap * P] and [rows_cap].  Nothing at or past the row bound is written in any of the five outputs.
+ * Any of the five outputs may be NULL; all five NULL with rows_cap > 0 is BF_E_ARG.  d_ids_out == d_rows (in place) stays allowed; the
+ * gathered outputs must not overlap d_rows.
+ * BF_E_ARG for whatever the base call refuses; max_pred < 0 or max_pred > 1 << 20; max_pred > 0 with row_len > BF_MLM_CAP_MAX_LEN (the
+ * call has no workspace: the keys of a row stay on the chip, 8 bytes per cell, and beyond that length they do not fit a wave's share of
+ * LDS); max_pred == 0 with a gathered output that is not NULL (there is no width to lay it out in).
+ * With max_pred == 0 the call IS the base call: the same kernel launch and byte for byte the same outputs.
+ * As there: the call clears the status word first and sets no bit of it; it enqueues on `stream`, does not synchronise and returns 0 or
+ * BF_E_*; it has no workspace and allocates nothing, with and without BfReserve; every pointer needs only the natural alignment of its type.
+ * Not here: BERT's skip-and-continue (a later unit that still fits is taken there: a sequential walk), span masking. */
+#define BF_MLM_CAP_MAX_LEN 4096
+BF_API int RowsMlmPredictionsBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
+                           const uint8_t *d_mask, const int32_t *d_seg, const int32_t *d_start_plane, const int32_t *d_end_plane,
+                           int nspecial, const int32_t *special_ids, double select_prob, double mask_prob, double random_prob,
+                           int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch,
+                           int32_t *d_ids_out, int32_t *d_labels_out, int max_pred, int32_t *d_pred_cell_out, int32_t *d_pred_label_out,
+                           int32_t *d_pred_count_out, void *stream);
 
 /* additive (no counterpart in the reference; this comment is the specification): PACKED rows -- several sequences share a row, a segment
  * plane keeps a model's attention block-diagonal and a position plane restarts at every sequence.  Where IdsToRowsBatch pads every sequence
