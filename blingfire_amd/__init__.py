@@ -117,6 +117,10 @@ def lib():
         L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
         L.IdsToPackedRowsBatchDevice.restype = c_int
         L.IdsToPackedRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64] + [c_void_p] * 4
+        L.IdsToPackedRowsPlanesBatch.restype = c_int64
+        L.IdsToPackedRowsPlanesBatch.argtypes = L.IdsToPackedRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p]
+        L.IdsToPackedRowsPlanesBatchDevice.restype = c_int
+        L.IdsToPackedRowsPlanesBatchDevice.argtypes = L.IdsToPackedRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
         L.BfLastKernelMs.restype = c_int
         L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
         L.BfLastStatus.restype = c_int
@@ -838,61 +842,92 @@ def ids_to_packed_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id
     Returns (rows int32[R, L], seg int32[R, L], pos int32[R, L], row_first_seq int32[R + 1], seq_row int32[nseq], seq_col int32[nseq]):
     seg numbers the sequences of a row from 1 (0 = padding), pos restarts at every sequence, row r holds the sequences
     [row_first_seq[r], row_first_seq[r + 1]), and sequence q begins at cell seq_col[q] of row seq_row[q]."""
+    return _packed_host("IdsToPackedRowsBatch", h, ids, id_off, L, cls_id, sep_id, pad_id)
+
+
+def _packed_host(name, h, ids, id_off, L, cls_id, sep_id, pad_id, extra=None):
+    """the host forms of the packed call: the size query, then every output.  extra = (nplanes, tail) of _plane_tail: the ...Planes call, whose
+    int32 [R, L] planes are appended to the result as a list"""
     ids = np.ascontiguousarray(ids, dtype=np.int32)
     id_off = np.ascontiguousarray(id_off, dtype=np.int64)
     nseq = len(id_off) - 1
-    fn = lib().IdsToPackedRowsBatch
+    fn = getattr(lib(), name)
+    nextra, tail = extra if extra else (0, lambda outs: ())
     pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
     seq_row = np.empty(nseq, dtype=np.int32)
     seq_col = np.empty(nseq, dtype=np.int32)
-    n = fn(*pre, None, None, None, None, 0, seq_row.ctypes.data, seq_col.ctypes.data)
+    n = fn(*pre, None, None, None, None, 0, seq_row.ctypes.data, seq_col.ctypes.data, *tail(None))
     if n < 0:
-        raise RuntimeError("IdsToPackedRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+        raise RuntimeError("%s failed: %d (%s)" % (name, n, lib().BfLastError().decode("utf-8", "replace")))
     planes = [np.empty((n, L), dtype=np.int32) for _ in range(3)]
+    more = [np.empty((n, L), dtype=np.int32) for _ in range(nextra)]
     first = np.empty(n + 1, dtype=np.int32)
-    r = fn(*pre, *[p.ctypes.data for p in planes], first.ctypes.data, n, seq_row.ctypes.data, seq_col.ctypes.data)
+    r = fn(*pre, *[p.ctypes.data for p in planes], first.ctypes.data, n, seq_row.ctypes.data, seq_col.ctypes.data, *tail(more))
     if r != n:
-        raise RuntimeError("IdsToPackedRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return (*planes, first, seq_row, seq_col)
+        raise RuntimeError("%s failed: %d (%s)" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
+    return (*planes, first, seq_row, seq_col, more) if extra else (*planes, first, seq_row, seq_col)
 
 
-def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, rows_cap=None, stream=None):
+def ids_to_packed_rows_planes_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, src=(), fill=()):
+    """ids_to_packed_rows_batch with companion planes (IdsToPackedRowsPlanesBatch): src = up to 4 int32 arrays parallel to ids (token offsets,
+    labels, ...), fill = one int per array.  Returns ids_to_packed_rows_batch's six results and the list of planes, int32[R, L] each: a cell
+    that holds an id holds that id's element of the array, every other cell (cls_id, sep_id, padding) the array's fill."""
+    src = [_np_i32(x) for x in src]
+    return _packed_host("IdsToPackedRowsPlanesBatch", h, ids, id_off, L, cls_id, sep_id, pad_id, _plane_tail([src], fill, lambda a: a.ctypes.data))
+
+
+def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, rows_cap=None, stream=None, planes=None, fill=None):
     """Device-resident ids_to_packed_rows_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are)
     -> (rows, seg, pos, row_first_seq, seq_row, seq_col, nrows) as tensors on that device, enqueued on torch's current stream (or `stream`);
     nrows is int64[1], the row count R.  rows_cap None: a size query whose R is read back (one synchronisation), the tensors have R rows.
     With a rows_cap of the caller's nothing is read back: the planes have rows_cap rows and row_first_seq rows_cap + 1 entries, of which
-    min(R, rows_cap) rows and one entry more are written; rows beyond it are dropped (BfLastStatus bit 0)."""
+    min(R, rows_cap) rows and one entry more are written; rows beyond it are dropped (BfLastStatus bit 0).
+    planes: a list of up to 4 int32 tensors on that device, parallel to d_ids (the starts / ends of text_to_ids_with_offsets_batch_device as
+    they are, per-token labels, ...), fill: one int per tensor (IdsToPackedRowsPlanesBatchDevice).  The gathered planes, int32[rows, L] each,
+    are appended behind nrows: a cell that holds an id holds that id's element, every other cell the fill."""
     import torch
     dev = d_ids.device
     nseq = d_id_off.numel() - 1
-    fn = lib().IdsToPackedRowsBatchDevice
+    if planes is None and fill:
+        raise ValueError("ids_to_packed_rows_batch_device: fill without planes")
+    nextra, tail = 0, lambda outs: ()
+    if planes is not None:
+        nextra, tail = _plane_tail([[_dev_i32(t, dev, "ids_to_packed_rows_batch_device: planes[%d]" % k) for k, t in enumerate(planes)]],
+                                   () if fill is None else fill, lambda t: t.data_ptr())
+    name = "IdsToPackedRowsBatchDevice" if planes is None else "IdsToPackedRowsPlanesBatchDevice"
+    fn = getattr(lib(), name)
     s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
     pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
     nrows = torch.empty(1, dtype=torch.int64, device=dev)
 
-    def call(outs, cap, seq):
-        r = fn(*pre, *outs, cap, *seq, nrows.data_ptr(), s)
+    def call(outs, cap, seq, more=None):
+        r = fn(*pre, *outs, cap, *seq, nrows.data_ptr(), *tail(more), s)
         if r != 0:
-            raise RuntimeError("IdsToPackedRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+            raise RuntimeError("%s failed (%d): %s" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
     if rows_cap is None:
         call([None] * 4, 0, [None] * 2)
         if stream is not None:
             torch.cuda.synchronize(dev)                   # (a raw stream handle: nothing finer to wait on)
         rows_cap = int(nrows.item())
-    planes = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(3)]
+    base = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(3)]
+    more = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(nextra)]
     first = torch.empty(rows_cap + 1, dtype=torch.int32, device=dev)
     seq = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(2)]
-    call([t.data_ptr() for t in planes] + [first.data_ptr()], rows_cap, [t.data_ptr() for t in seq])
-    return (*planes, first, *seq, nrows)
+    call([t.data_ptr() for t in base] + [first.data_ptr()], rows_cap, [t.data_ptr() for t in seq], more)
+    return (*base, first, *seq, nrows, *more)
 
 
-def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None):
+def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None, return_offsets=False):
     """Text in HBM -> packed tensors a model takes, nothing on the host: text_to_ids_batch_device (every document tokenised up to the ids
     a row can hold) and ids_to_packed_rows_batch_device on one stream.  Returns what ids_to_packed_rows_batch_device returns; with a
-    rows_cap of the caller's nothing is read back."""
+    rows_cap of the caller's nothing is read back.  With return_offsets also (starts int32[R, L], ends int32[R, L]) behind nrows: every
+    token's first and last byte in its document, -1 in cells without a token."""
     body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
     if body < 1:
         raise ValueError("encode_packed_batch_device: L leaves no room for ids")
+    if return_offsets:
+        d_ids, d_st, d_en, d_id_off = text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, body, unk)
+        return ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, rows_cap, planes=[d_st, d_en], fill=[-1, -1])
     d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, body, unk)
     return ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, rows_cap)
 
@@ -976,8 +1011,9 @@ def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mas
     or, with packed=True, encode_packed_batch_device, and rows_mlm_mask_device on one stream.  Returns the base call's tuple with the masked
     input ids in place of its rows and `labels` (int32[R, L], ignore_label where nothing is predicted) appended:
     (ids, mask, row_doc, row_offsets[, starts, ends], labels), or packed (ids, seg, pos, row_first_seq, seq_row, seq_col, nrows, labels).
-    special_ids None: the cls_id, sep_id and pad_id there are.  Packed rows mask inside the segment plane; they have no offset planes, so
-    packed=True with whole_word=True raises ValueError.  rows_cap is the packed call's (None: its one read-back).  max_predictions = P > 0
+    special_ids None: the cls_id, sep_id and pad_id there are.  Packed rows mask inside the segment plane; this function gives them no offset
+    planes, so packed=True with whole_word=True raises ValueError: whole-word masking over packed rows is encode_packed_mlm_batch_device.
+    rows_cap is the packed call's (None: its one read-back).  max_predictions = P > 0
     caps the predictions of a row and appends (pred_cells int32[R, P], pred_labels int32[R, P], pred_count int32[R]) behind labels, in all
     three forms (rows_mlm_mask_device)."""
     if packed and whole_word:
@@ -992,6 +1028,28 @@ def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mas
         return (ids, *out[1:], *tail)
     out = encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, return_offsets=whole_word)
     ids, *tail = rows_mlm_mask_device(h, out[0], mask=out[1], starts=out[4] if whole_word else None, ends=out[5] if whole_word else None, nrows=out[3][-1:], **kw)
+    return (ids, *out[1:], *tail)
+
+
+def encode_packed_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mask_id, rand_range, seed, epoch=0, whole_word=True, unk=0,
+                                   special_ids=None, select_prob=0.15, mask_prob=0.8, random_prob=0.1, ignore_label=-100, rows_cap=None, max_predictions=0):
+    """Text in HBM -> the packed tensors of a masked-language-model step with whole-word masking, nothing on the host: the tokenizer with
+    offsets, the packed call with the offsets as companion planes (encode_packed_batch_device(..., return_offsets=True)) and
+    rows_mlm_mask_device over the segment plane and the two offset planes, on one stream.  Returns
+    (ids, seg, pos, row_first_seq, seq_row, seq_col, nrows, starts, ends, labels[, pred_cells, pred_labels, pred_count]): the masked input ids
+    in place of the rows, the packed call's outputs, the offset planes (-1 in cells without a token) and `labels` (ignore_label where nothing
+    is predicted); the last three with max_predictions = P > 0 (rows_mlm_mask_device).  The remaining keywords are encode_mlm_batch_device's.
+    whole_word=False masks token by token (the planes are returned all the same).  With whole_word=True a row needs cls_id or sep_id: the
+    special between two sequences is what keeps a unit from joining the last token of one sequence to the first token of the next when their
+    byte offsets happen to be adjacent; without either, ValueError."""
+    if whole_word and _special(cls_id) < 0 and _special(sep_id) < 0:
+        raise ValueError("encode_packed_mlm_batch_device: whole-word masking over packed rows needs cls_id or sep_id (units could join across sequences)")
+    if special_ids is None:
+        special_ids = [i for i in (_special(cls_id), _special(sep_id), _special(pad_id)) if i >= 0]
+    out = encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, rows_cap, return_offsets=True)
+    ids, *tail = rows_mlm_mask_device(h, out[0], seg=out[1], starts=out[7] if whole_word else None, ends=out[8] if whole_word else None, nrows=out[6],
+                                      special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id,
+                                      rand_range=rand_range, ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True, max_predictions=max_predictions)
     return (ids, *out[1:], *tail)
 
 

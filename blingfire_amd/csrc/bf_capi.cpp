@@ -1563,9 +1563,10 @@ bool reserve_packed_workspaces(Handle *h, int64_t nseq)
 }
 
 int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, int32_t *d_rows, int32_t *d_seg,
-                      int32_t *d_pos, int32_t *d_row_first, int64_t rows_cap, int32_t *d_seq_row, int32_t *d_seq_col, int64_t *d_nrows, hipStream_t s)
+                      int32_t *d_pos, int32_t *d_row_first, int64_t rows_cap, int32_t *d_seq_row, int32_t *d_seq_col, int64_t *d_nrows, hipStream_t s,
+                      const PlaneArgs &planes = PlaneArgs{})
 {
-    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || ids_len < 0 || !d_id_off || !d_nrows || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || ids_len < 0 || !d_id_off || !d_nrows || (ids_len > 0 && !d_ids) || !plane_args_ok(planes, true, ids_len)) return BF_E_ARG;
     if (!reserve_packed_workspaces(h, nseq)) return BF_E_DEVICE;
     if (!begin_launch(h, s)) return BF_E_DEVICE;
     PackedParams p;
@@ -1573,7 +1574,7 @@ int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, i
     p.widths = h->w_counts.as<int32_t>(); p.W = h->w_pkW.as<int64_t>(); p.jmp[0] = h->w_pkjmp[0].as<int32_t>(); p.jmp[1] = h->w_pkjmp[1].as<int32_t>();
     p.mark = h->w_pkmark.as<int32_t>(); p.mark_off = h->w_pkmoff.as<int64_t>(); p.f = h->w_pkf.as<int32_t>();
     p.rows_cap = rows_cap; p.rows = d_rows; p.seg = d_seg; p.pos = d_pos; p.row_first = d_row_first; p.seq_row = d_seq_row; p.seq_col = d_seq_col; p.nrows = d_nrows;
-    // the events BfLastKernelMs reads: [0] widths + scan, [1] next + the doubling rounds, [5] the rounds alone, [2] the scan of the marks, rows and cols, [3] fill
+    // the events BfLastKernelMs reads: [0] widths + scan, [1] next + the doubling rounds, [5] the rounds alone, [2] the scan of the marks, rows and cols, [3] fill (and the planes)
     (void)hipEventRecord(h->ev[EV_BEGIN], s);
     if (nseq > 0) launch_packed_widths(p, s);
     scan_counts(h, nseq, p.W, s);
@@ -1588,6 +1589,17 @@ int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, i
     if (nseq > 0 && d_seq_col) launch_packed_cols(p, s);
     (void)hipEventRecord(h->ev[EV_SCAN], s);
     if (nseq > 0 && rows_cap > 0 && (d_rows || d_seg || d_pos)) launch_packed_fill(p, s);
+    // the companion planes the caller takes (IdsToPackedRowsPlanesBatch; none = the base call, with the launches of the base call).  Also with
+    // rows_cap = 0: the kernel reports the rows dropped from a plane, which k_packed_rows does for the base outputs alone
+    PackedPlanesParams pp;
+    bool any = false;
+    pp.nplanes = planes.nplanes;
+    for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
+        const bool in = k < planes.nplanes;
+        pp.src[k] = in && planes.src_a ? planes.src_a[k] : nullptr; pp.fill[k] = in ? planes.fill[k] : 0; pp.out[k] = in ? planes.out[k] : nullptr;
+        any = any || pp.out[k];
+    }
+    if (nseq > 0 && any) { pp.pk = p; launch_packed_planes(pp, s); }
     (void)hipEventRecord(h->ev[EV_COMPACT], s);
     h->ev_valid = true;
     return hip_ok(hipGetLastError(), "IdsToPackedRows kernels") ? 0 : BF_E_DEVICE;
@@ -1596,11 +1608,11 @@ int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, i
 // IdsToPackedRowsBatch on host buffers: the ids through stage_ragged, a size pass that also answers the per-sequence outputs, the capacity check,
 // the fill pass.  As in two_pass_host, whatever ends the call early after work was queued synchronises the stream first.
 int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const PackedSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
-                        int32_t *row_first_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
+                        int32_t *row_first_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out, const PlaneArgs &planes = PlaneArgs{})
 {
     if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || !id_off) return BF_E_ARG;
     const int64_t ids_len = host_side_len(id_off, nseq);
-    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    if (ids_len < 0 || (ids_len > 0 && !ids) || !plane_args_ok(planes, true, ids_len)) return BF_E_ARG;
     std::lock_guard<std::mutex> dlock(h->defer_mu);
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
@@ -1611,18 +1623,25 @@ int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
     int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
     if (rc != 0) return rc;
     auto fail = [s](int64_t e) { (void)hipStreamSynchronize(s); return e; };
+    const int32_t *d_src[ROWS_MAX_PLANES] = {};
+    rc = stage_planes(h, planes.src_a, planes.nplanes, 0, id_off, nseq, ids_len, h->w_docoff, s, d_src);
+    if (rc != 0) return fail(rc);                                              // (the ids' copies are queued)
+    int32_t *d_plane[ROWS_MAX_PLANES] = {};                                    // the size pass takes no plane
     auto pass = [&](int32_t *d_rows, int32_t *d_seg, int32_t *d_pos, int32_t *d_first, int64_t cap) {
         return run_packed_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, d_rows, d_seg, d_pos, d_first, cap,
-                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s);
+                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s,
+                                 PlaneArgs{planes.nplanes, d_src, nullptr, planes.fill, d_plane});
     };
     rc = pass(nullptr, nullptr, nullptr, nullptr, 0);
     if (rc != 0) return fail(rc);
+    bool any_plane = false;
+    for (int k = 0; k < planes.nplanes; ++k) any_plane = any_plane || planes.out[k];
     int64_t R = 0;
     if (!hip_ok(hipMemcpyAsync(&R, h->w_idoff.p, 8, hipMemcpyDeviceToHost, s), "D2H row count") ||
         (seq_row_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_row_out, h->w_starts.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence rows")) ||
         (seq_col_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_col_out, h->w_ends.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence cells"))) return fail(BF_E_DEVICE);
     if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    if (!rows_out && !seg_out && !pos_out && !row_first_out) return R;         // (a size query needs no capacity)
+    if (!rows_out && !seg_out && !pos_out && !row_first_out && !any_plane) return R;         // (a size query needs no capacity)
     if (R > rows_cap) return BF_E_CAPACITY;
     const size_t plane_bytes = (size_t)R * (size_t)spec.row_len * 4, first_bytes = (size_t)(R + 1) * 4;
     struct { int32_t *host; DevBuf *dev; size_t bytes; const char *what; } outs[4] = {{rows_out, &h->w_out, plane_bytes, "D2H rows"}, {seg_out, &h->w_vals, plane_bytes, "D2H segments"},
@@ -1633,10 +1652,17 @@ int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
         if (!outs[i].dev->reserve(outs[i].bytes + 16)) return BF_E_DEVICE;
         d_out[i] = outs[i].dev->as<int32_t>();
     }
+    for (int k = 0; k < planes.nplanes; ++k) {
+        if (!planes.out[k]) continue;
+        if (!h->w_plout[k].reserve(plane_bytes + 16)) return BF_E_DEVICE;
+        d_plane[k] = h->w_plout[k].as<int32_t>();
+    }
     rc = pass(d_out[0], d_out[1], d_out[2], d_out[3], R);
     if (rc != 0) return fail(rc);
     for (const auto &o : outs)
         if (o.host && o.bytes && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, o.bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
+    for (int k = 0; k < planes.nplanes; ++k)
+        if (d_plane[k] && plane_bytes && !hip_ok(hipMemcpyAsync(planes.out[k], d_plane[k], plane_bytes, hipMemcpyDeviceToHost, s), "D2H plane")) return fail(BF_E_DEVICE);
     return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
 }
 
@@ -2450,6 +2476,33 @@ int64_t IdsToPackedRowsBatch(void *p, const int32_t *ids, const int64_t *id_offs
     PackedSpec spec;
     if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec)) return BF_E_ARG;
     return run_packed_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, row_first_seq_out, rows_cap, seq_row_out, seq_col_out);
+}
+
+/* ---- additive: packed rows with companion planes (k_packed_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */
+int IdsToPackedRowsPlanesBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
+                                     int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
+                                     int32_t *d_seq_row_out, int32_t *d_seq_col_out, int64_t *d_nrows_out, int nplanes, const int32_t *const *d_src, const int32_t *fill,
+                                     int32_t *const *d_planes_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    PackedSpec spec;
+    const PlaneArgs planes{nplanes, d_src, nullptr, fill, d_planes_out};
+    if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec) || ids_len < 0 || !plane_args_ok(planes, true, ids_len)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_packed_device(h, spec, d_ids, ids_len, d_id_offsets, nseq, d_rows_out, d_seg_out, d_pos_out, d_row_first_seq_out, rows_cap, d_seq_row_out, d_seq_col_out,
+                             d_nrows_out, (hipStream_t)stream, planes);
+}
+
+int64_t IdsToPackedRowsPlanesBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                                   int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *row_first_seq_out, int64_t rows_cap, int32_t *seq_row_out,
+                                   int32_t *seq_col_out, int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out)
+{
+    Handle *h = as_handle(p);
+    PackedSpec spec;
+    if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec)) return BF_E_ARG;
+    return run_packed_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, row_first_seq_out, rows_cap, seq_row_out, seq_col_out,
+                           PlaneArgs{nplanes, src, nullptr, fill, planes_out});
 }
 
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */

@@ -342,6 +342,16 @@ void launch_packed_double(const PackedParams &p, int round, hipStream_t s);     
 void launch_packed_rows(const PackedParams &p, hipStream_t s);                  // behind the scan of the marks: f, row_first, seq_row, nrows, status bit 0
 void launch_packed_cols(const PackedParams &p, hipStream_t s);                  // seq_col
 void launch_packed_fill(const PackedParams &p, hipStream_t s);                  // the three planes
+// IdsToPackedRowsPlanesBatch (additive): up to ROWS_MAX_PLANES int32 arrays parallel to the ids, gathered into planes with the layout of `rows` by
+// k_packed_planes, behind the kernels of the base call.  A struct of its own: the kernels above keep their arguments where they are.
+struct PackedPlanesParams {
+    PackedParams pk;             // the call's packed stage as its kernels saw it: W, f and the row count are in the workspaces when the kernel runs
+    int nplanes;
+    const int32_t *src[ROWS_MAX_PLANES];         // parallel to the ids; read at id cells alone (NULL only where there is no id to read)
+    int32_t fill[ROWS_MAX_PLANES];               // what a cell without an id gets
+    int32_t *out[ROWS_MAX_PLANES];               // [rows_cap * row_len] each; NULL = not taken
+};
+void launch_packed_planes(const PackedPlanesParams &p, hipStream_t s);          // the planes taken; rows dropped from them (status bit 0)
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

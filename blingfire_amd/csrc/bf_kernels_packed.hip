@@ -14,6 +14,8 @@
 //                   cell space min(R, rows_cap) x row_len, stepping like k_rowstage_fill.  A lane finds its unit by a binary search of the row's own
 //                   slice W[f[r] .. f[r+1]]: the lanes of a row read the same few cache lines, usually 4 .. 20 entries, so the slice is not staged in
 //                   LDS (a row maps to no fixed group of lanes: row_len is any number from 1 to 2^20).
+//  k_packed_planes  (IdsToPackedRowsPlanesBatch only, behind the kernels above) the fill's cell space, stepping and two forms; a lane finds its unit
+//                   by the same search and gathers, for each of its cells, the element of every companion array that the cell's id has.
 // No lane walks the chain of rows, a row's units or a unit's cells: 10^5 empty sequences in one row cost a search of 17 steps.
 #include "bf_kernels_common.h"
 
@@ -110,6 +112,47 @@ __global__ __launch_bounds__(256) void k_packed_fill(PackedParams p)
     }
 }
 
+// The companion planes, behind the fill: the fill's cell space and stepping, C cells per lane in the same two forms.  A lane asks packed_where --
+// the fill's steps with the fetch left out (bf_packed.h) -- which element each of its cells holds and gathers that element of every source, or takes the plane's
+// fill.  The sources are read with plain dword loads: a sequence starts anywhere.  No LDS, no atomics but the one status report: k_packed_rows
+// reports rows dropped from the base outputs, lane 0 here those dropped from a plane (the call may take planes alone).
+template <int C>
+__global__ __launch_bounds__(256) void k_packed_planes(PackedPlanesParams pp)
+{
+    const PackedParams &p = pp.pk;
+    const int64_t total = p.mark_off[p.nseq], nrows = total < p.rows_cap ? total : p.rows_cap;
+    const int row_len = p.spec.row_len, lw = row_len / C;              // lanes per row
+    const int64_t nlanes = nrows * lw, stride = (int64_t)gridDim.x * 256;
+    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0 && total > p.rows_cap) atomicOr(p.status, 1);
+    if (i >= nlanes) return;
+    int64_t r = i / lw;                                                // (one division per lane, none per round: k_packed_fill)
+    int jw = (int)(i - r * lw);
+    const int64_t dr = stride / lw;
+    const int dj = (int)(stride - dr * lw);
+    for (;;) {
+        const int64_t s = p.f[r], e = p.f[r + 1];
+        int64_t q = s;
+        int64_t from[C];
+#pragma unroll
+        for (int k = 0; k < C; ++k) from[k] = packed_where(p.spec, p.W, s, e, jw * C + k, p.id_off, &q);
+        const int64_t at = r * row_len + (int64_t)jw * C;
+#pragma unroll
+        for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
+            if (k >= pp.nplanes || !pp.out[k]) continue;
+            int32_t v[C];
+#pragma unroll
+            for (int x = 0; x < C; ++x) v[x] = from[x] != PACKED_NONE ? pp.src[k][from[x]] : pp.fill[k];
+            if constexpr (C == 4) *(int4 *)(pp.out[k] + at) = make_int4(v[0], v[1], v[2], v[3]);
+            else pp.out[k][at] = v[0];
+        }
+        i += stride;
+        if (i >= nlanes) break;
+        r += dr; jw += dj;
+        if (jw >= lw) { jw -= lw; ++r; }
+    }
+}
+
 void launch_packed_widths(const PackedParams &p, hipStream_t s) { hipLaunchKernelGGL(k_packed_widths, dim3(rows_blocks(p.nseq)), dim3(256), 0, s, p); }
 void launch_packed_next(const PackedParams &p, hipStream_t s) { hipLaunchKernelGGL(k_packed_next, dim3(rows_blocks(p.nseq + 1)), dim3(256), 0, s, p); }
 void launch_packed_double(const PackedParams &p, int round, hipStream_t s)
@@ -127,6 +170,19 @@ void launch_packed_fill(const PackedParams &p, hipStream_t s)
     const int64_t lanes = rows * (row_len / (wide ? 4 : 1));
     if (wide) hipLaunchKernelGGL(k_packed_fill<4>, dim3(rows_blocks(lanes)), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(k_packed_fill<1>, dim3(rows_blocks(lanes)), dim3(256), 0, s, p);
+}
+
+// (with rows_cap = 0 one block: lane 0 still reports the rows dropped)
+void launch_packed_planes(const PackedPlanesParams &pp, hipStream_t s)
+{
+    const PackedParams &p = pp.pk;
+    const int row_len = p.spec.row_len;
+    bool wide = row_len % 4 == 0;
+    for (int k = 0; k < pp.nplanes; ++k) wide = wide && ((uintptr_t)pp.out[k] & 15) == 0;
+    const int64_t rows = p.rows_cap < p.nseq ? p.rows_cap : p.nseq;      // (R is at most nseq: launch_packed_fill)
+    const int64_t lanes = rows * (row_len / (wide ? 4 : 1));
+    if (wide) hipLaunchKernelGGL(k_packed_planes<4>, dim3(rows_blocks(lanes)), dim3(256), 0, s, pp);
+    else hipLaunchKernelGGL(k_packed_planes<1>, dim3(rows_blocks(lanes)), dim3(256), 0, s, pp);
 }
 
 } // namespace bfa

@@ -82,20 +82,44 @@ struct PackedCell { int32_t id, seg, pos; };
 
 BF_HD PackedCell packed_pad_cell(const PackedSpec &sp) { return PackedCell{sp.pad_id, 0, 0}; }
 
-// cell x of the unit of sequence q (width w > x) in the row that starts at sequence s.  The ids are read only where the unit holds one: the
-// sequence's range is good then (a bad range is read as empty)
+// Where a cell reads.  The fill (packed_cell) and the companion planes (packed_where, k_packed_planes) find a cell's unit by the same steps and
+// name the element it holds by the same call:
+//   packed_locate  the unit the cell lies in and its place there, or "padding" -- packed_cell keeps these five lines in its own body, word for
+//                  word: routed through the call, k_packed_fill<4> compiled to 15 % more instructions and the base call ran slower than the parent's
+//   packed_id_at   for a place that holds an id, that id's element of the ids -- and of every array parallel to them
+// A unit's first place holds cls_id when there is a lead, its last one sep_id when there is a trail, every other place an id.
+// tests/hosttest/bf_packedplanestest.cpp holds the two to each other cell by cell: where packed_cell fetched ids[i], packed_where says i.
+
+// cell j of the row [s, e) (s = f[r], e = f[r + 1]): false = padding; else *q_io is the cell's unit, *w its width and *x the cell's place in it.
+// *q_io comes in as a unit of the row at or in front of the cell's (s to begin with): a lane that fills cells from left to right searches
+// only where the cell left the unit of the cell before
+BF_HD bool packed_locate(const int64_t *W, int64_t s, int64_t e, int j, int64_t *q_io, int32_t *w, int32_t *x)
+{
+    const int64_t base = W[s], target = base + j;
+    if (target >= W[e]) return false;
+    int64_t q = *q_io;
+    if (W[q + 1] <= target) q = packed_find_unit(W, q + 1, e, target);
+    *q_io = q;
+    *w = (int32_t)(W[q + 1] - W[q]); *x = (int32_t)(target - W[q]);
+    return true;
+}
+
+// the element that place x of the unit of sequence q holds, for a place that holds an id: the sequence's range is good then (a bad range is read
+// as empty: its unit has no such place), so the index is inside [0, ids_len)
+BF_HD int64_t packed_id_at(const PackedSpec &sp, int64_t q, int32_t x, const int64_t *id_off) { return id_off[q] + x - sp.lead; }
+
+// cell x of the unit of sequence q (width w > x) in the row that starts at sequence s
 BF_HD PackedCell packed_unit_cell(const PackedSpec &sp, int64_t s, int64_t q, int32_t w, int32_t x, const int32_t *ids, const int64_t *id_off)
 {
     PackedCell c;
     c.seg = (int32_t)(q - s + 1); c.pos = x;
     if (sp.lead && x == 0) c.id = sp.cls_id;
     else if (sp.trail && x == w - 1) c.id = sp.sep_id;
-    else c.id = ids[id_off[q] + x - sp.lead];
+    else c.id = ids[packed_id_at(sp, q, x, id_off)];
     return c;
 }
 
-// cell j of the row [s, e) (s = f[r], e = f[r + 1]).  *q_io: a unit of the row at or in front of the cell's (s to begin with): a lane that
-// fills cells from left to right searches only where the cell left the unit of the cell before
+// cell j of the row [s, e); *q_io as in packed_locate, whose steps these are
 BF_HD PackedCell packed_cell(const PackedSpec &sp, const int64_t *W, int64_t s, int64_t e, int j, const int32_t *ids, const int64_t *id_off, int64_t *q_io)
 {
     const int64_t base = W[s], target = base + j;
@@ -104,6 +128,17 @@ BF_HD PackedCell packed_cell(const PackedSpec &sp, const int64_t *W, int64_t s, 
     if (W[q + 1] <= target) q = packed_find_unit(W, q + 1, e, target);
     *q_io = q;
     return packed_unit_cell(sp, s, q, (int32_t)(W[q + 1] - W[q]), (int32_t)(target - W[q]), ids, id_off);
+}
+
+// the element index of the id that cell j of the row [s, e) holds, PACKED_NONE where it holds cls_id, sep_id or padding: packed_cell with the
+// fetch left out (what a companion plane gathers by)
+constexpr int64_t PACKED_NONE = -1;
+BF_HD int64_t packed_where(const PackedSpec &sp, const int64_t *W, int64_t s, int64_t e, int j, const int64_t *id_off, int64_t *q_io)
+{
+    int32_t w, x;
+    if (!packed_locate(W, s, e, j, q_io, &w, &x)) return PACKED_NONE;
+    if ((sp.lead && x == 0) || (sp.trail && x == w - 1)) return PACKED_NONE;
+    return packed_id_at(sp, *q_io, x, id_off);
 }
 
 } // namespace bfa

@@ -239,7 +239,7 @@ BF_API int64_t IdsToPairRowsBatch(void *ModelPtr, const int32_t *ids_a, const in
  * alignment of its type: with row_len % 4 == 0 and every taken plane aligned to 16 bytes a lane makes one 16-byte store per plane, otherwise
  * it writes one cell; the sources are read element by element, because a sequence starts anywhere.
  * Host forms: each source is staged beside the ids (read, like them, from the side's first offset to its largest one); BF_E_CAPACITY with
- * complete offsets and nothing else written, exactly as the base calls.  Packed rows (IdsToPackedRowsBatch) have no companion planes. */
+ * complete offsets and nothing else written, exactly as the base calls.  Packed rows have companion planes of their own: IdsToPackedRowsPlanesBatch below. */
 #define BF_ROWS_MAX_PLANES 4
 BF_API int IdsToRowsPlanesBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
                                int row_len, int cls_id, int sep_id, int pad_id, int stride, int max_rows_per_seq, int flags,
@@ -322,8 +322,9 @@ BF_API int RowsSpanCellsBatchDevice(void *ModelPtr, const int32_t *d_start_plane
  * The call clears the status word first, like every batch call, and sets no bit of it; it enqueues on `stream`, does not synchronise and
  * returns 0 or BF_E_*.  It has no workspace: it allocates nothing, with and without BfReserve.  Every pointer needs only the natural
  * alignment of its type.  A wave shares a row (a power-of-two slice of a wave when row_len <= 32) and walks it in chunks of as many cells.
- * Not here: span (n-gram) masking, a host-buffer form, offset planes of packed rows.  (A cap on the predictions of a row, with the kept cells
- * gathered: RowsMlmPredictionsBatchDevice below.) */
+ * Not here: span (n-gram) masking, a host-buffer form.  (A cap on the predictions of a row, with the kept cells gathered:
+ * RowsMlmPredictionsBatchDevice below.  Offset planes of packed rows: IdsToPackedRowsPlanesBatchDevice below, which also says when a unit can span
+ * two sequences of a packed row.) */
 #define BF_MLM_MAX_SPECIAL 8
 BF_API int RowsMlmMaskBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
                            const uint8_t *d_mask, const int32_t *d_seg, const int32_t *d_start_plane, const int32_t *d_end_plane,
@@ -411,6 +412,47 @@ BF_API int64_t IdsToPackedRowsBatch(void *ModelPtr, const int32_t *ids, const in
                              int row_len, int cls_id, int sep_id, int pad_id, int flags,
                              int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *row_first_seq_out, int64_t rows_cap,
                              int32_t *seq_row_out, int32_t *seq_col_out);
+
+/* additive (no counterpart in the reference; this comment is the specification): COMPANION PLANES for packed rows -- what IdsToRowsPlanesBatch
+ * is to IdsToRowsBatch: up to BF_ROWS_MAX_PLANES int32 arrays that run parallel to the ids (the tokenizer's starts and ends, per-token labels, word
+ * indices, ...) are gathered into int32 planes of [rows_cap * row_len] cells with the layout of d_rows_out, in the same call.  Element i of a
+ * source belongs to d_ids[i].
+ * IdsToPackedRowsPlanesBatchDevice / IdsToPackedRowsPlanesBatch take every argument of IdsToPackedRowsBatchDevice / IdsToPackedRowsBatch, with the
+ * same meaning, checks, status bits and capacity rules, and behind them (Device form: in front of `stream`): nplanes, d_src, fill, d_planes_out
+ * -- three HOST arrays of nplanes entries whose values travel to the kernel by value, exactly as in IdsToRowsPlanesBatchDevice (d_src[k] and
+ * d_planes_out[k] are device pointers in the Device form, host pointers in the host form).  d_planes_out[k] may be NULL: that plane is skipped.
+ * Cells.  In plane k, a cell that holds id number i of its sequence q (unit q at place x = lead + i, in the terms above) gets
+ * src[k][off[q] + i]; only i < k_q is read, what a row truncates is not.  A cell that holds cls_id, sep_id or padding gets fill[k].
+ * Reads and writes.  src[k] is read for at most ids_len elements, and only at cells that hold an id; a sequence read as empty (BfLastStatus
+ * bit 3) has no id cells.  No row r >= rows_cap of a plane is written.  Rows dropped from a plane the caller takes set BfLastStatus bit 0,
+ * also when d_rows_out, d_seg_out, d_pos_out and d_row_first_seq_out are all NULL.
+ * The calls are supersets of the base calls: rows, seg, pos, row_first_seq, seq_row, seq_col and nrows are byte for byte what the base call
+ * writes for the same arguments; with nplanes = 0 the call IS the base call, with the launches of the base call; a size query is the four row
+ * outputs and every plane NULL.
+ * BF_E_ARG for nplanes outside 0 .. BF_ROWS_MAX_PLANES, a NULL fill or d_planes_out with nplanes > 0, a NULL d_src or d_src[k] with
+ * ids_len > 0 (host form: with any id to read), and for whatever the base call refuses.
+ * The Device form allocates nothing after BfReserve(h, max_docs >= nseq, ...), with planes or without: it has no workspace of its own, one
+ * kernel behind the base call's reads what that call left in the handle's workspaces.  Every pointer needs only the natural alignment of its
+ * type: with row_len % 4 == 0 and every taken plane aligned to 16 bytes a lane makes one 16-byte store per plane, otherwise it writes one cell;
+ * the sources are read element by element, because a sequence starts anywhere.
+ * Host form: each source is staged beside the ids (read, like them, from id_offsets[0] to the largest offset), and the call makes the base
+ * host form's two passes; when R > rows_cap with a row output or a plane taken it returns BF_E_CAPACITY with seq_row_out / seq_col_out complete
+ * and nothing else written.
+ * Units across sequences (whole-word masking, RowsMlmMaskBatchDevice over two planes of token offsets).  With at least one of cls_id / sep_id
+ * present two units of a row are separated by a special; with that special among special_ids its cell is not eligible, so no unit of the MLM
+ * call spans two sequences.  Without any special two sequences can be byte-adjacent by accident -- one ends at byte 2 of its document, the next
+ * starts at byte 3 of its own behind a byte-order mark -- and their cells then join into one unit: the planes here do nothing about that, and
+ * the MLM kernel's unit rule does not look at the segment plane. */
+BF_API int IdsToPackedRowsPlanesBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                                     int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                                     int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
+                                     int32_t *d_seq_row_out, int32_t *d_seq_col_out, int64_t *d_nrows_out,
+                                     int nplanes, const int32_t *const *d_src, const int32_t *fill, int32_t *const *d_planes_out, void *stream);
+BF_API int64_t IdsToPackedRowsPlanesBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                                   int row_len, int cls_id, int sep_id, int pad_id, int flags,
+                                   int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *row_first_seq_out, int64_t rows_cap,
+                                   int32_t *seq_row_out, int32_t *seq_col_out,
+                                   int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out);
 
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
@@ -504,7 +546,8 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * call's own stream.  Synchronises with those events.  Fills up to n floats (milliseconds):
  * [0] prep (decode+normalise+classify)  [1] tokenise (lexer / segmenter)  [2] scan  [3] compact  [4] total  [5] the dominant kernel of the
  * tokenise segment alone.  After IdsToPackedRowsBatchDevice: [0] widths + scan, [1] next + the doubling rounds, [2] the scan of the marks and the
- * per-row / per-sequence outputs, [3] the fill of the planes, [4] total, [5] the doubling rounds alone.
+ * per-row / per-sequence outputs, [3] the fill of the planes, [4] total, [5] the doubling rounds alone.  After IdsToPackedRowsPlanesBatchDevice with a plane taken, [3] covers the
+ * fill and the kernel of the companion planes behind it.
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
