@@ -121,6 +121,10 @@ def lib():
         L.IdsToPackedRowsPlanesBatch.argtypes = L.IdsToPackedRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p]
         L.IdsToPackedRowsPlanesBatchDevice.restype = c_int
         L.IdsToPackedRowsPlanesBatchDevice.argtypes = L.IdsToPackedRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.IdsToStreamRowsBatch.restype = c_int64
+        L.IdsToStreamRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 6 + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p]
+        L.IdsToStreamRowsBatchDevice.restype = c_int
+        L.IdsToStreamRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 6 + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4
         L.BfLastKernelMs.restype = c_int
         L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
         L.BfLastStatus.restype = c_int
@@ -940,6 +944,85 @@ def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None
     d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
     d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
     return encode_packed_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
+
+
+def _stream_flags(drop_last, pos_from_row, labels_within_doc):
+    return (1 if drop_last else 0) | (2 if pos_from_row else 0) | (4 if labels_within_doc else 0)
+
+
+def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,
+                             labels_within_doc=False):
+    """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> STREAM rows for causal-LM training (IdsToStreamRowsBatch): every sequence
+    closed by its specials, all of them laid end to end, the stream cut into rows of exactly L cells; a sequence runs over a row's edge into the
+    next row, nothing is truncated and nothing is padded but the tail.  bos_id / eos_id None = no such special.
+    Returns (rows, seg, pos, labels int32[R, L], row_first_seq, row_first_pos int32[R], seq_row, seq_col int32[nseq]): labels are the next
+    element of the stream (ignore_label behind the last one, and, with labels_within_doc, where the next element belongs to another sequence);
+    seg numbers the sequences of a row from 1 (0 = padding); pos is the place in the sequence, continuing across rows (pos_from_row: counted
+    from the row's edge for a sequence that continues from the row before); row r begins at place row_first_pos[r] of sequence
+    row_first_seq[r]; sequence q begins at cell seq_col[q] of row seq_row[q].  drop_last drops the last row when it is incomplete."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
+    nseq = len(id_off) - 1
+    fn = lib().IdsToStreamRowsBatch
+    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(bos_id), _special(eos_id), int(pad_id), int(ignore_label),
+           _stream_flags(drop_last, pos_from_row, labels_within_doc))
+    seq = [np.empty(nseq, dtype=np.int32) for _ in range(2)]
+    n = fn(*pre, *[None] * 6, 0, *[a.ctypes.data for a in seq])
+    if n < 0:
+        raise RuntimeError("IdsToStreamRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    outs = [np.empty((n, L), dtype=np.int32) for _ in range(4)] + [np.empty(n, dtype=np.int32) for _ in range(2)]
+    r = fn(*pre, *[a.ctypes.data for a in outs], n, *[a.ctypes.data for a in seq])
+    if r != n:
+        raise RuntimeError("IdsToStreamRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return (*outs, *seq)
+
+
+def ids_to_stream_rows_batch_device(h, d_ids, d_id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,
+                                    labels_within_doc=False, rows_cap=None, stream=None):
+    """Device-resident ids_to_stream_rows_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are)
+    -> (rows, seg, pos, labels, row_first_seq, row_first_pos, seq_row, seq_col, nrows) as tensors on that device, enqueued on torch's current
+    stream (or `stream`); nrows is int64[2] = {R, T}: the row count and the length of the stream.  Nothing is read back: rows_cap None uses the
+    bound the host knows, ceil((d_ids.numel() + specials * nseq) / L).  The row outputs have rows_cap rows, of which min(R, rows_cap) are
+    written; rows beyond rows_cap are dropped (BfLastStatus bit 0)."""
+    import torch
+    dev = d_ids.device
+    nseq = d_id_off.numel() - 1
+    L = int(L)
+    if rows_cap is None:
+        specials = (1 if _special(bos_id) >= 0 else 0) + (1 if _special(eos_id) >= 0 else 0)
+        rows_cap = -(-(d_ids.numel() + specials * nseq) // L) if L > 0 else 0
+    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    outs = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(4)] + [torch.empty(rows_cap, dtype=torch.int32, device=dev) for _ in range(2)]
+    seq = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(2)]
+    nrows = torch.empty(2, dtype=torch.int64, device=dev)
+    r = lib().IdsToStreamRowsBatchDevice(c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, L, _special(bos_id), _special(eos_id), int(pad_id),
+                                         int(ignore_label), _stream_flags(drop_last, pos_from_row, labels_within_doc), *[t.data_ptr() for t in outs], rows_cap,
+                                         *[t.data_ptr() for t in seq], nrows.data_ptr(), s)
+    if r != 0:
+        raise RuntimeError("IdsToStreamRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    return (*outs, *seq, nrows)
+
+
+def encode_clm_batch_device(h, d_text, d_doc_off, L, bos_id, eos_id, pad_id, unk=0, ignore_label=-100, drop_last=False, pos_from_row=False,
+                            labels_within_doc=False, rows_cap=None, max_ids_per_doc=0x7fffffff):
+    """Text in HBM -> the tensors causal-LM training takes, nothing on the host and nothing read back: text_to_ids_batch_device (every
+    document tokenised, up to max_ids_per_doc ids) and ids_to_stream_rows_batch_device on one stream.  Returns a dict: input_ids, seg, pos,
+    labels (int32[rows_cap, L]), row_first_seq, row_first_pos (int32[rows_cap]), seq_row, seq_col (int32[ndocs]) and nrows (int64[2] = {R, T});
+    rows_cap None = the bound the host knows from the size of the tokenizer's id buffer."""
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_ids_per_doc), unk)
+    got = ids_to_stream_rows_batch_device(h, d_ids, d_id_off, L, bos_id, eos_id, pad_id, ignore_label, drop_last, pos_from_row, labels_within_doc, rows_cap)
+    return dict(zip(("input_ids", "seg", "pos", "labels", "row_first_seq", "row_first_pos", "seq_row", "seq_col", "nrows"), got))
+
+
+def encode_clm_batch(h, docs, L, bos_id, eos_id, pad_id, unk=0, ignore_label=-100, drop_last=False, pos_from_row=False, labels_within_doc=False,
+                     rows_cap=None, max_ids_per_doc=0x7fffffff):
+    """encode_clm_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed into one buffer, uploaded with
+    torch to the current device, encoded there."""
+    import torch
+    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
+    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
+    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
+    return encode_clm_batch_device(h, d_text, d_off, L, bos_id, eos_id, pad_id, unk, ignore_label, drop_last, pos_from_row, labels_within_doc, rows_cap, max_ids_per_doc)
 
 
 def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None, nrows=None, special_ids=(), select_prob=0.15, mask_prob=0.8, random_prob=0.1,

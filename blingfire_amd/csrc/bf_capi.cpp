@@ -1666,6 +1666,88 @@ int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
     return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
 }
 
+// IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
+// outputs the caller takes -- the fill.  The launches depend on nseq and on which outputs are taken, never on the data; the workspaces are the
+// first three of the packed stage (reserve_packed_workspaces): nothing here is sized by the row count.
+int run_stream_device(Handle *h, const StreamSpec &spec, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, int32_t *d_rows, int32_t *d_seg,
+                      int32_t *d_pos, int32_t *d_labels, int32_t *d_first_seq, int32_t *d_first_pos, int64_t rows_cap, int32_t *d_seq_row, int32_t *d_seq_col,
+                      int64_t *d_nrows, hipStream_t s)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || ids_len < 0 || !d_id_off || !d_nrows || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    const int64_t rows_bound = stream_rows_bound(spec, ids_len, nseq);          // (ids_len + 2 * nseq + row_len stays far inside int64)
+    if (rows_bound > 0x7fffffff) return BF_E_ARG;
+    if (!reserve_packed_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    StreamParams p;
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
+    p.widths = h->w_counts.as<int32_t>(); p.W = h->w_pkW.as<int64_t>();
+    p.rows_cap = rows_cap; p.rows = d_rows; p.seg = d_seg; p.pos = d_pos; p.labels = d_labels; p.row_first_seq = d_first_seq; p.row_first_pos = d_first_pos;
+    p.seq_row = d_seq_row; p.seq_col = d_seq_col; p.nrows = d_nrows;
+    // the events BfLastKernelMs reads: [0] widths + scan, [1] and [5] nothing, [2] the per-sequence outputs and the counts, [3] the fill
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (nseq > 0) launch_stream_widths(p, s);
+    scan_counts(h, nseq, p.W, s);
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    launch_stream_seq(p, s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    if (rows_cap > 0 && (d_rows || d_seg || d_pos || d_labels || d_first_seq || d_first_pos)) launch_stream_fill(p, rows_bound, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "IdsToStreamRows kernels") ? 0 : BF_E_DEVICE;
+}
+
+// IdsToStreamRowsBatch on host buffers: the ids through stage_ragged, a size pass that also answers the per-sequence outputs, the capacity check,
+// the fill pass (run_packed_host's shape).  Whatever ends the call early after work was queued synchronises the stream first.
+int64_t run_stream_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const StreamSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
+                        int32_t *labels_out, int32_t *first_seq_out, int32_t *first_pos_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || rows_cap < 0 || !id_off) return BF_E_ARG;
+    const int64_t ids_len = host_side_len(id_off, nseq);
+    if (ids_len < 0 || (ids_len > 0 && !ids) || stream_rows_bound(spec, ids_len, nseq) > 0x7fffffff) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    const size_t seq_bytes = (size_t)nseq * 4;
+    if (!h->w_idoff.reserve(16) || !h->w_starts.reserve(seq_bytes + 16) || !h->w_ends.reserve(seq_bytes + 16)) return BF_E_DEVICE;
+    Staged st;
+    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    auto fail = [s](int64_t e) { (void)hipStreamSynchronize(s); return e; };
+    auto pass = [&](int32_t *const d[6], int64_t cap) {
+        return run_stream_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, d[0], d[1], d[2], d[3], d[4], d[5], cap,
+                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s);
+    };
+    int32_t *d_out[6] = {};
+    rc = pass(d_out, 0);
+    if (rc != 0) return fail(rc);
+    int64_t R = 0;
+    if (!hip_ok(hipMemcpyAsync(&R, h->w_idoff.p, 8, hipMemcpyDeviceToHost, s), "D2H row count") ||
+        (seq_row_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_row_out, h->w_starts.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence rows")) ||
+        (seq_col_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_col_out, h->w_ends.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence cells"))) return fail(BF_E_DEVICE);
+    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
+    if (!rows_out && !seg_out && !pos_out && !labels_out && !first_seq_out && !first_pos_out) return R;      // (a size query needs no capacity)
+    if (R > rows_cap) return BF_E_CAPACITY;
+    if (R == 0) return 0;
+    const size_t plane_bytes = (size_t)R * (size_t)spec.row_len * 4, first_bytes = (size_t)R * 4;
+    struct { int32_t *host; DevBuf *dev; size_t bytes; const char *what; } outs[6] = {
+        {rows_out, &h->w_out, plane_bytes, "D2H rows"}, {seg_out, &h->w_vals, plane_bytes, "D2H segments"}, {pos_out, &h->w_text, plane_bytes, "D2H positions"},
+        {labels_out, &h->w_plout[0], plane_bytes, "D2H labels"}, {first_seq_out, &h->w_outoff, first_bytes, "D2H row sequences"}, {first_pos_out, &h->w_plout[1], first_bytes, "D2H row positions"}};
+    for (int i = 0; i < 6; ++i) {
+        if (!outs[i].host) continue;
+        if (!outs[i].dev->reserve(outs[i].bytes + 16)) return BF_E_DEVICE;
+        d_out[i] = outs[i].dev->as<int32_t>();
+    }
+    rc = pass(d_out, R);
+    if (rc != 0) return fail(rc);
+    for (const auto &o : outs)
+        if (o.host && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, o.bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
+}
+
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
 bool ensure_dict_tables(Handle *h)
 {
@@ -2503,6 +2585,31 @@ int64_t IdsToPackedRowsPlanesBatch(void *p, const int32_t *ids, const int64_t *i
     if (!h || !packed_spec(row_len, cls_id, sep_id, pad_id, flags, &spec)) return BF_E_ARG;
     return run_packed_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, row_first_seq_out, rows_cap, seq_row_out, seq_col_out,
                            PlaneArgs{nplanes, src, nullptr, fill, planes_out});
+}
+
+/* ---- additive: stream rows (bf_stream.h): the units laid end to end and cut into rows of exactly row_len cells, with next-token labels */
+int IdsToStreamRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int bos_id, int eos_id, int pad_id,
+                               int ignore_label, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_labels_out,
+                               int32_t *d_row_first_seq_out, int32_t *d_row_first_pos_out, int64_t rows_cap, int32_t *d_seq_row_out, int32_t *d_seq_col_out,
+                               int64_t *d_nrows_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    StreamSpec spec;
+    if (!h || !stream_spec(row_len, bos_id, eos_id, pad_id, ignore_label, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_stream_device(h, spec, d_ids, ids_len, d_id_offsets, nseq, d_rows_out, d_seg_out, d_pos_out, d_labels_out, d_row_first_seq_out, d_row_first_pos_out, rows_cap,
+                             d_seq_row_out, d_seq_col_out, d_nrows_out, (hipStream_t)stream);
+}
+
+int64_t IdsToStreamRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int row_len, int bos_id, int eos_id, int pad_id, int ignore_label, int flags,
+                             int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *labels_out, int32_t *row_first_seq_out, int32_t *row_first_pos_out,
+                             int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
+{
+    Handle *h = as_handle(p);
+    StreamSpec spec;
+    if (!h || !stream_spec(row_len, bos_id, eos_id, pad_id, ignore_label, flags, &spec)) return BF_E_ARG;
+    return run_stream_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, labels_out, row_first_seq_out, row_first_pos_out, rows_cap, seq_row_out, seq_col_out);
 }
 
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */

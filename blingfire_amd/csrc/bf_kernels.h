@@ -12,6 +12,7 @@
 #include "bf_rows.h"
 #include "bf_pairs.h"
 #include "bf_packed.h"
+#include "bf_stream.h"
 #include "bf_mlm.h"
 #include "bf_variant.h"
 
@@ -352,6 +353,22 @@ struct PackedPlanesParams {
     int32_t *out[ROWS_MAX_PLANES];               // [rows_cap * row_len] each; NULL = not taken
 };
 void launch_packed_planes(const PackedPlanesParams &p, hipStream_t s);          // the planes taken; rows dropped from them (status bit 0)
+// IdsToStreamRowsBatch (additive; bf_stream.h has the lane code, bf_kernels_stream.hip the kernels): the units laid end to end and cut into rows,
+// with labels, a segment and a position plane.  Its workspaces are the first three of the packed stage: widths, block sums, W.
+struct StreamParams {
+    StreamSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    int32_t *widths;             // [nseq] unit widths, scanned into W
+    int64_t *W;                  // [nseq + 1] exclusive scan of the widths; W[nseq] = T
+    int64_t rows_cap;            // no row r >= rows_cap of a row output is written
+    int32_t *rows, *seg, *pos, *labels;          // [rows_cap * row_len] each, any may be NULL
+    int32_t *row_first_seq, *row_first_pos;      // [rows_cap] each, either may be NULL
+    int32_t *seq_row, *seq_col;  // [nseq] each, either may be NULL
+    int64_t *nrows;              // [2] = {R, T}
+};
+void launch_stream_widths(const StreamParams &p, hipStream_t s);                // lane per sequence: widths, status bit 3
+void launch_stream_seq(const StreamParams &p, hipStream_t s);                   // behind the scan: seq_row, seq_col, nrows, status bit 0
+void launch_stream_fill(const StreamParams &p, int64_t rows_bound, hipStream_t s);      // the four planes and the row-first pair, tile by tile
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -454,6 +454,62 @@ BF_API int64_t IdsToPackedRowsPlanesBatch(void *ModelPtr, const int32_t *ids, co
                                    int32_t *seq_row_out, int32_t *seq_col_out,
                                    int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): STREAM rows -- "concatenate and chunk", the input of causal-LM
+ * pretraining: every sequence closed by its specials, all of them laid end to end, the stream cut into rows of exactly row_len cells, with
+ * next-token labels, a segment plane and a position plane.  Where IdsToPackedRowsBatch truncates a sequence longer than a row and never splits
+ * one, here a sequence runs over a row's edge into the next row: nothing is truncated, and nothing is padded but the tail of the last row.
+ * Units.  Sequence q of nseq = ids[off[q] .. off[q+1]), n_q ids; a range outside [0, ids_len] or with decreasing offsets is read as empty and
+ * sets BfLastStatus bit 3, exactly as in IdsToRowsBatchDevice; a sequence of more than INT32_MAX - 2 ids is read the same way (the widths are
+ * int32 like every count the scan takes).  lead = (bos_id >= 0), trail = (eos_id >= 0).  Unit q is [bos_id] ids[0 .. n_q) [eos_id], every id
+ * and none dropped, of width w_q = lead + n_q + trail.  W is the int64 exclusive scan of the widths, T = W[nseq] the length of the stream S,
+ * the units laid end to end.
+ * Rows.  Row r is S[r * L .. (r+1) * L), L = row_len.  R = ceil(T / L); with flags bit 0 ("drop the last incomplete row") R = floor(T / L).
+ * T = 0 gives R = 0: that is nseq = 0, and also every unit of width 0 (the packed call writes one row of padding there; this call does not).
+ * Cells.  Cell j of row r is stream position t = r * L + j.  For t < T: q = the last q in [0, nseq) with W[q] <= t -- units of width 0 share
+ * their W with the unit behind them, so this is the unit the cell lies in -- and x = t - W[q].  rows: bos_id at x = 0 when lead, eos_id at
+ * x = w_q - 1 when trail, else ids[off[q] + x - lead].  seg: q - f[r] + 1, where f[r] is the unit of cell 0 of the row (it always has positive
+ * width); units of width 0 are counted, so f[r] + seg - 1 is the sequence, as in the packed call, and a unit that continues from the row before
+ * has seg 1.  pos: x, the position within the unit, continuing across rows; with flags bit 1 pos = min(x, j): a unit that continues from the
+ * row before counts from the row's edge (what a model needs whose attention is confined to the row and the segment).  labels: with t + 1 < T,
+ * S[t + 1] -- the stream's next element, which may be a special, and for j = L - 1 is the next row's first: it is taken from the stream, whether
+ * or not that row is written; with flags bit 2 a label whose t + 1 lies in another unit than t is ignore_label; with t + 1 = T, ignore_label.
+ * t >= T is padding, always on the right of the last row: rows = pad_id, seg = 0, pos = 0, labels = ignore_label.
+ * Per-row outputs, [rows_cap] int32 each: d_row_first_seq_out[r] = f[r], d_row_first_pos_out[r] = r * L - W[f[r]].
+ * Per-sequence outputs, [nseq] int32 each: d_seq_row_out[q] = W[q] / L and d_seq_col_out[q] = W[q] mod L, the cell where the unit begins.  They
+ * are complete whatever rows_cap and flags bit 0 are; a row >= R is a legitimate answer (a unit in the dropped tail, or units of width 0
+ * behind the last cell when L divides T).
+ * Counts.  d_nrows_out is int64[2] = {R, T}, and required; its first entry serves as the d_nrows of RowsMlmMaskBatchDevice and its relatives.
+ * Example: ids = 1000 .. 1009, off = [0,3,3,3,10], L = 4, bos 1, eos 2, pad 0, flags 0: T = 18, R = 5,
+ *   rows = [1 1000 1001 1002] [2 1 2 1] [2 1 1003 1004] [1005 1006 1007 1008] [1009 2 0 0]
+ *   seg  = [1 1 1 1] [1 2 2 3] [1 2 2 2] [1 1 1 1] [1 1 0 0]        pos = [0 1 2 3] [4 0 1 0] [1 0 1 2] [3 4 5 6] [7 8 0 0]
+ *   labels: row 0 = [1000 1001 1002 2], the last row = [2 -100 -100 -100] (ignore_label -100)
+ *   row_first_seq = [0 0 2 3 3], row_first_pos = [0 4 1 3 7], seq_row = [0 1 1 2], seq_col = [0 1 3 1].
+ * BF_E_ARG for row_len outside 1 .. 1 << 20 (there is no body >= 1 condition: L = 1 with both specials is fine, since units split), a flag bit
+ * above 2, nseq < 0 or nseq > INT32_MAX, rows_cap < 0, ids_len < 0, ceil((ids_len + (lead + trail) * nseq) / row_len) > INT32_MAX (the
+ * host-known bound of R: seq_row is int32), a NULL ModelPtr (any live handle of any kind serves), a NULL d_id_offsets or d_nrows_out, and a
+ * NULL d_ids with ids_len > 0.
+ * Device form: every output but d_nrows_out may be NULL; the six row outputs (rows, seg, pos, labels, row_first_seq, row_first_pos) all NULL is
+ * a size query.  No row r >= rows_cap of any row output is written; rows dropped that way from an output the caller takes set BfLastStatus
+ * bit 0.  The call clears the status word first, enqueues on `stream` (a hipStream_t), does not synchronise, reads nothing back and returns 0
+ * or BF_E_*.  The kernels it launches depend on nseq and on which outputs are taken, never on the data.  After BfReserve(h, max_docs >= nseq,
+ * ...) it allocates nothing: it has no workspace beyond the widths, block sums and W of the packed call, and none sized by the row count (R is
+ * not bounded by nseq here).  Every pointer needs only the natural alignment of its type; row_len % 4 == 0 with every taken plane aligned to
+ * 16 bytes takes the 16-byte stores.
+ * Host form: it stages the ids like IdsToPackedRowsBatch (id_offsets[0] < 0 = BF_E_ARG), makes two passes and returns R.  The six row outputs
+ * all NULL is a size query, whatever rows_cap is; otherwise R > rows_cap returns BF_E_CAPACITY with seq_row_out / seq_col_out complete and
+ * nothing else written.
+ * Not here: overlapping rows, companion planes, shuffling, and a cap on the ids of a document (the tokenizer call's max_ids_per_doc is that). */
+BF_API int IdsToStreamRowsBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                               int row_len, int bos_id, int eos_id, int pad_id, int ignore_label, int flags,
+                               int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_labels_out,
+                               int32_t *d_row_first_seq_out, int32_t *d_row_first_pos_out, int64_t rows_cap,
+                               int32_t *d_seq_row_out, int32_t *d_seq_col_out, int64_t *d_nrows_out, void *stream);
+BF_API int64_t IdsToStreamRowsBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                             int row_len, int bos_id, int eos_id, int pad_id, int ignore_label, int flags,
+                             int32_t *rows_out, int32_t *seg_out, int32_t *pos_out, int32_t *labels_out,
+                             int32_t *row_first_seq_out, int32_t *row_first_pos_out, int64_t rows_cap,
+                             int32_t *seq_row_out, int32_t *seq_col_out);
+
 /* reference tokdll:1669-1679 */
 BF_API int SetNoDummyPrefix(void *ModelPtr, bool fNoDummyPrefix);
 
@@ -547,7 +603,8 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * [0] prep (decode+normalise+classify)  [1] tokenise (lexer / segmenter)  [2] scan  [3] compact  [4] total  [5] the dominant kernel of the
  * tokenise segment alone.  After IdsToPackedRowsBatchDevice: [0] widths + scan, [1] next + the doubling rounds, [2] the scan of the marks and the
  * per-row / per-sequence outputs, [3] the fill of the planes, [4] total, [5] the doubling rounds alone.  After IdsToPackedRowsPlanesBatchDevice with a plane taken, [3] covers the
- * fill and the kernel of the companion planes behind it.
+ * fill and the kernel of the companion planes behind it.  After IdsToStreamRowsBatchDevice: [0] widths + scan, [2] the per-sequence outputs and
+ * the counts, [3] the fill, [4] total ([1] and [5] are 0).
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
