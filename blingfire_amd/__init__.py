@@ -113,6 +113,9 @@ def lib():
             c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]
         L.RowsMlmPredictionsBatchDevice.restype = c_int
         L.RowsMlmPredictionsBatchDevice.argtypes = L.RowsMlmMaskBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.RowsDenoiseBatchDevice.restype = c_int
+        L.RowsDenoiseBatchDevice.argtypes = [c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 3 + [c_int, c_void_p, c_double] + [c_int] * 8 + [c_uint64, c_uint32] + [
+            c_int, c_void_p, c_void_p, c_void_p] * 2 + [c_void_p, c_void_p]
         L.IdsToPackedRowsBatch.restype = c_int64
         L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
         L.IdsToPackedRowsBatchDevice.restype = c_int
@@ -1134,6 +1137,123 @@ def encode_packed_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_
                                       special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id,
                                       rand_range=rand_range, ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True, max_predictions=max_predictions)
     return (ids, *out[1:], *tail)
+
+
+def denoise_start_prob(noise_density, len_lo=1, len_hi=5):
+    """The start_prob of rows_denoise_device for which an interior cell (one with at least len_hi - 1 eligible cells in front of it) is noise
+    with probability noise_density.  A cell is noise unless none of the len_hi cells at distance k = 0 .. len_hi - 1 in front of it starts a span
+    longer than k:  1 - prod_k (1 - p * P(len > k)) = noise_density,  P(len > k) = 1 for k < len_lo and (len_hi - k) / (len_hi - len_lo + 1) above
+    that (lengths are uniform on [len_lo, len_hi]).  The left side rises with p; solved by bisection in double."""
+    d, lo, hi = float(noise_density), int(len_lo), int(len_hi)
+    if not (0.0 <= d <= 1.0) or not (1 <= lo <= hi):
+        raise ValueError("denoise_start_prob: noise_density in [0, 1] and 1 <= len_lo <= len_hi")
+    tail = [1.0 if k < lo else (hi - k) / float(hi - lo + 1) for k in range(hi)]
+
+    def density(p):
+        clean = 1.0
+        for t in tail:
+            clean *= 1.0 - p * t
+        return 1.0 - clean
+    a, b = 0.0, 1.0
+    if d <= 0.0:
+        return 0.0
+    if density(1.0) <= d:
+        return 1.0
+    for _ in range(200):
+        m = 0.5 * (a + b)
+        if m == a or m == b:
+            break
+        if density(m) < d:
+            a = m
+        else:
+            b = m
+    return a if abs(density(a) - d) <= abs(density(b) - d) else b
+
+
+def rows_denoise_device(h, rows, *, mask=None, seg=None, nrows=None, special_ids=(), start_prob, len_lo=1, len_hi=5, sentinel_first, sentinel_step=-1,
+                        max_sentinels=100, eos_id=None, pad_id=0, ignore_label=-100, seed, epoch=0, enc_len=None, dec_len=None, return_cells=False, stream=None):
+    """Span corruption of rows that are on the device (RowsDenoiseBatchDevice): the encoder inputs and the decoder targets of the T5 / mT5 / UL2
+    denoising objective.  -> a dict of int32 tensors: input_ids [R, enc_len] (noise runs collapsed to their sentinels, pad_id behind the row),
+    labels [R, dec_len] (every run's sentinel and ids, then eos_id if given, ignore_label behind them), enc_count, dec_count [R] (the
+    untruncated lengths) and span_count [R]; with return_cells also enc_cells and dec_cells: the cell of `rows` every copied id came from, -1
+    at sentinels, the eos and the padding -- other_plane.gather(1, cells.clamp(min=0).long()) carries any plane of the input into the new layout.
+    rows: int32[R, L] from any of the row calls; mask: uint8[R, L] or None; seg: int32[R, L] (the packed or the stream call's segment plane) or
+    None: a cell outside the mask or in segment 0 is dropped; a cell holding one of special_ids (at most 8) is copied and ends every span in front
+    of it.  An eligible cell starts a span with start_prob (denoise_start_prob gives it for a noise density), of a length uniform on
+    [len_lo, len_hi]; run k of a row gets the id sentinel_first + k * sentinel_step, runs past max_sentinels are copied.  nrows: an int64 tensor
+    of one element on the device that bounds the rows, or None.  enc_len None = L (always enough), dec_len None = L + 2 (always enough); a row
+    longer than a smaller value is cut there and sets BfLastStatus bit 0.  Rows at or past nrows hold pad_id / ignore_label / -1 and counts of 0.
+    The result is a function of (seed, epoch, row) and the row alone.  Like every batch call it clears the handle's status word first."""
+    import torch
+    dev = rows.device
+    _dev_i32(rows, dev, "rows_denoise_device: rows")
+    _dev_i32(seg, dev, "rows_denoise_device: seg")
+    if rows.dim() != 2 or any(t is not None and t.shape != rows.shape for t in (mask, seg)):
+        raise ValueError("rows_denoise_device: rows is an [R, L] plane; mask and seg have its shape")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev):
+        raise ValueError("rows_denoise_device: mask must be a contiguous torch.uint8 tensor on %s" % dev)
+    if nrows is not None and (not isinstance(nrows, torch.Tensor) or nrows.dtype != torch.int64 or nrows.numel() != 1 or nrows.device != dev):
+        raise ValueError("rows_denoise_device: nrows must be a torch.int64 tensor of one element on %s" % dev)
+    special_ids = [int(x) for x in special_ids]
+    if len(special_ids) > 8:
+        raise ValueError("rows_denoise_device: at most 8 special ids")
+    R, L = rows.shape
+    enc_len = L if enc_len is None else int(enc_len)
+    dec_len = L + 2 if dec_len is None else int(dec_len)
+    if enc_len < 1 or dec_len < 1:
+        raise ValueError("rows_denoise_device: enc_len and dec_len are at least 1")
+    enc = torch.full((R, enc_len), int(pad_id), dtype=torch.int32, device=dev)
+    dec = torch.full((R, dec_len), int(ignore_label), dtype=torch.int32, device=dev)
+    counts = [torch.zeros((R,), dtype=torch.int32, device=dev) for _ in range(3)]
+    cells = [torch.full((R, n), -1, dtype=torch.int32, device=dev) for n in (enc_len, dec_len)] if return_cells else [None, None]
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    c_special = (c_int32 * max(len(special_ids), 1))(*special_ids)
+
+    def addr(t):
+        return None if t is None else t.data_ptr()
+    r = lib().RowsDenoiseBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), len(special_ids), c_special, float(start_prob), int(len_lo),
+                                     int(len_hi), int(sentinel_first), int(sentinel_step), int(max_sentinels), _special(eos_id), int(pad_id), int(ignore_label),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, enc_len, enc.data_ptr(), addr(cells[0]), counts[0].data_ptr(), dec_len,
+                                     dec.data_ptr(), addr(cells[1]), counts[1].data_ptr(), counts[2].data_ptr(), c_void_p(s))
+    if r != 0:
+        raise RuntimeError("RowsDenoiseBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    out = dict(input_ids=enc, labels=dec, enc_count=counts[0], dec_count=counts[1], span_count=counts[2])
+    if return_cells:
+        out.update(enc_cells=cells[0], dec_cells=cells[1])
+    return out
+
+
+def encode_denoise_batch_device(h, d_text, d_doc_off, L, eos_id, pad_id, sentinel_first, seed, epoch=0, source="stream", unk=0, start_prob=None, noise_density=0.15,
+                                len_lo=1, len_hi=5, sentinel_step=-1, max_sentinels=100, special_ids=None, ignore_label=-100, enc_len=None, dec_len=None,
+                                return_cells=False, rows_cap=None, max_ids_per_doc=0x7fffffff):
+    """Text in HBM -> the tensors of a span-corruption step, nothing on the host and nothing read back: the tokenizer, a row call and
+    rows_denoise_device on one stream.  source="stream": ids_to_stream_rows_batch_device (no bos, eos_id behind every document, the documents laid
+    end to end and cut into rows of L cells; its segment plane keeps the padding out and its row count bounds the rows).  source="rows":
+    ids_to_rows_batch_device (one row per document, truncated, no cls, eos_id as the closing special; its mask keeps the padding out).
+    eos_id and pad_id are the special_ids unless the caller gives others: no span crosses the eos between two documents.  start_prob None:
+    denoise_start_prob(noise_density, len_lo, len_hi).  Returns rows_denoise_device's dict with `rows` (the uncorrupted rows), `nrows` (int64, one
+    element: the rows that count) and `seg` or `mask` added."""
+    if source not in ("stream", "rows"):
+        raise ValueError("encode_denoise_batch_device: source is \"stream\" or \"rows\"")
+    if _special(eos_id) < 0:
+        raise ValueError("encode_denoise_batch_device: eos_id closes every document and is required")
+    if special_ids is None:
+        special_ids = sorted({int(eos_id), int(pad_id)})
+    if start_prob is None:
+        start_prob = denoise_start_prob(noise_density, len_lo, len_hi)
+    kw = dict(special_ids=special_ids, start_prob=start_prob, len_lo=len_lo, len_hi=len_hi, sentinel_first=sentinel_first, sentinel_step=sentinel_step,
+              max_sentinels=max_sentinels, eos_id=eos_id, pad_id=pad_id, ignore_label=ignore_label, seed=seed, epoch=epoch, enc_len=enc_len, dec_len=dec_len,
+              return_cells=return_cells)
+    if source == "stream":
+        d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_ids_per_doc), unk)
+        got = ids_to_stream_rows_batch_device(h, d_ids, d_id_off, L, None, eos_id, pad_id, ignore_label, rows_cap=rows_cap)
+        out = rows_denoise_device(h, got[0], seg=got[1], nrows=got[8][:1], **kw)
+        out.update(rows=got[0], seg=got[1], nrows=got[8][:1])
+        return out
+    rows, mask, _, r_off = encode_batch_device(h, d_text, d_doc_off, L, None, eos_id, pad_id, unk)
+    out = rows_denoise_device(h, rows, mask=mask, nrows=r_off[-1:], **kw)
+    out.update(rows=rows, mask=mask, nrows=r_off[-1:])
+    return out
 
 
 def dict_get_info_batch(h, keys):

@@ -113,7 +113,7 @@ struct PinBuf {
 //   per launch   [0, 64)     on the stream, by begin_launch() in EVERY batch call that takes a handle of the caller's, whether its kernels use one of these
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
 //                            calls on one handle): run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, run_packed_device, run_i2t_host and
+//                            run_row_stage_device, RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsDenoiseBatchDevice, run_packed_device, run_i2t_host and
 //                            IdsToTextBatchDevice.  The fill passes of the two-pass calls keep the size pass's words.  NormalizeSpacesBatch and
 //                            TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for its status, and their
 //                            kernels use none of the words: they clear nothing.
@@ -2535,6 +2535,33 @@ int RowsMlmPredictionsBatchDevice(void *p, const int32_t *d_rows, int row_len, i
         else launch_rows_mlm_cap(RowsMlmCapParams{m, max_pred, d_pred_cell_out, d_pred_label_out, d_pred_count_out}, s);
     }
     return hip_ok(hipGetLastError(), "RowsMlmPredictions kernel") ? 0 : BF_E_DEVICE;
+}
+
+/* ---- additive: span corruption of rows that are on the device (bf_denoise.h, k_rows_denoise): the encoder row and the decoder row, compacted in one walk */
+int RowsDenoiseBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows, const uint8_t *d_mask, const int32_t *d_seg,
+                           int nspecial, const int32_t *special_ids, double start_prob, int len_lo, int len_hi, int sentinel_first, int sentinel_step,
+                           int max_sentinels, int eos_id, int pad_id, int ignore_label, uint64_t seed, uint32_t epoch, int enc_len, int32_t *d_enc_out,
+                           int32_t *d_enc_cell_out, int32_t *d_enc_count_out, int dec_len, int32_t *d_dec_out, int32_t *d_dec_cell_out, int32_t *d_dec_count_out,
+                           int32_t *d_span_count_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    DenoiseSpec spec;
+    const bool want_enc = d_enc_out || d_enc_cell_out, want_dec = d_dec_out || d_dec_cell_out;
+    const bool any_out = want_enc || want_dec || d_enc_count_out || d_dec_count_out || d_span_count_out;
+    if (!h || row_len < 1 || row_len > DENOISE_MAX_LEN || rows_cap < 0) return BF_E_ARG;
+    if ((want_enc && (enc_len < 1 || enc_len > DENOISE_MAX_LEN)) || (want_dec && (dec_len < 1 || dec_len > DENOISE_MAX_LEN))) return BF_E_ARG;
+    if (!denoise_spec(nspecial, special_ids, start_prob, len_lo, len_hi, sentinel_first, sentinel_step, max_sentinels, eos_id, pad_id, ignore_label, seed, epoch, &spec))
+        return BF_E_ARG;
+    if (rows_cap > 0 && (!d_rows || !any_out)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    if (rows_cap > 0)
+        launch_rows_denoise(RowsDenoiseParams{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, spec, want_enc ? enc_len : 0, d_enc_out, d_enc_cell_out,
+                                              want_dec ? dec_len : 0, d_dec_out, d_dec_cell_out, d_enc_count_out, d_dec_count_out, d_span_count_out,
+                                              &h->misc()->status}, s);
+    return hip_ok(hipGetLastError(), "RowsDenoise kernel") ? 0 : BF_E_DEVICE;
 }
 
 /* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */

@@ -14,6 +14,7 @@
 #include "bf_packed.h"
 #include "bf_stream.h"
 #include "bf_mlm.h"
+#include "bf_denoise.h"
 #include "bf_variant.h"
 
 namespace bfa {
@@ -319,6 +320,20 @@ struct RowsMlmCapParams {
     int32_t *pred_count;                         // [rows_cap]: kept cells of the row; may be NULL
 };
 void launch_rows_mlm_cap(const RowsMlmCapParams &p, hipStream_t s);
+
+// RowsDenoiseBatchDevice (additive; bf_denoise.h has the lane code, k_rows_denoise in bf_kernels_denoise.hip): span corruption of rows that are already
+// there, the encoder row and the decoder row compacted in one walk
+struct RowsDenoiseParams {
+    const int32_t *rows; int row_len;
+    int64_t rows_cap; const int64_t *nrows;      // rows below min(rows_cap, *nrows); nrows NULL = rows_cap
+    const uint8_t *mask; const int32_t *seg;     // either may be NULL: every cell counts
+    DenoiseSpec spec;                            // thresholds, lengths, sentinels, generator key, ids; the specials by value
+    int enc_len; int32_t *enc, *enc_cell;        // [rows_cap * enc_len] each, either may be NULL; enc_len counts only where one is taken
+    int dec_len; int32_t *dec, *dec_cell;        // [rows_cap * dec_len] each, likewise
+    int32_t *enc_count, *dec_count, *span_count; // [rows_cap] each, any may be NULL
+    int *status;                                 // bit 0: a row lost a cell of an output the caller takes
+};
+void launch_rows_denoise(const RowsDenoiseParams &p, hipStream_t s);
 
 // IdsToPackedRowsBatch (additive; bf_packed.h has the lane code, bf_kernels_packed.hip the kernels): several sequences per row, with a segment
 // and a position plane.  Every workspace array has nseq + 1 entries (index nseq = the end of the chain) unless noted.

@@ -322,7 +322,7 @@ BF_API int RowsSpanCellsBatchDevice(void *ModelPtr, const int32_t *d_start_plane
  * The call clears the status word first, like every batch call, and sets no bit of it; it enqueues on `stream`, does not synchronise and
  * returns 0 or BF_E_*.  It has no workspace: it allocates nothing, with and without BfReserve.  Every pointer needs only the natural
  * alignment of its type.  A wave shares a row (a power-of-two slice of a wave when row_len <= 32) and walks it in chunks of as many cells.
- * Not here: span (n-gram) masking, a host-buffer form.  (A cap on the predictions of a row, with the kept cells gathered:
+ * Not here: a host-buffer form.  (Span corruption, the T5 objective: RowsDenoiseBatchDevice below.  A cap on the predictions of a row, with the kept cells gathered:
  * RowsMlmPredictionsBatchDevice below.  Offset planes of packed rows: IdsToPackedRowsPlanesBatchDevice below, which also says when a unit can span
  * two sequences of a packed row.) */
 #define BF_MLM_MAX_SPECIAL 8
@@ -362,7 +362,8 @@ BF_API int RowsMlmMaskBatchDevice(void *ModelPtr, const int32_t *d_rows, int row
  * With max_pred == 0 the call IS the base call: the same kernel launch and byte for byte the same outputs.
  * As there: the call clears the status word first and sets no bit of it; it enqueues on `stream`, does not synchronise and returns 0 or
  * BF_E_*; it has no workspace and allocates nothing, with and without BfReserve; every pointer needs only the natural alignment of its type.
- * Not here: BERT's skip-and-continue (a later unit that still fits is taken there: a sequential walk), span masking. */
+ * Not here: BERT's skip-and-continue (a later unit that still fits is taken there: a sequential walk); span corruption is
+ * RowsDenoiseBatchDevice below. */
 #define BF_MLM_CAP_MAX_LEN 4096
 BF_API int RowsMlmPredictionsBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
                            const uint8_t *d_mask, const int32_t *d_seg, const int32_t *d_start_plane, const int32_t *d_end_plane,
@@ -370,6 +371,64 @@ BF_API int RowsMlmPredictionsBatchDevice(void *ModelPtr, const int32_t *d_rows, 
                            int mask_id, int rand_lo, int rand_hi, int ignore_label, uint64_t seed, uint32_t epoch,
                            int32_t *d_ids_out, int32_t *d_labels_out, int max_pred, int32_t *d_pred_cell_out, int32_t *d_pred_label_out,
                            int32_t *d_pred_count_out, void *stream);
+
+/* additive (no counterpart in the reference; this comment is the specification): SPAN CORRUPTION -- the encoder inputs and the decoder targets
+ * of the denoising objective of the T5 / mT5 / UL2 family.  Noise spans collapse to one sentinel id in the encoder row and are listed behind
+ * their sentinels in the decoder row, so every row is compacted twice, at different rates.  Device only: it reads rows that are already on the
+ * device ([rows_cap * row_len] int32), whatever call laid them out: rows, packed rows and stream rows alike.
+ * Rows processed.  Rows r < min(rows_cap, *d_nrows) are processed (d_nrows NULL = rows_cap rows; d_row_offsets_out + nseq of a row call or
+ * d_nrows_out of the packed or the stream call is the intended d_nrows: nothing is read back); nothing at or past that bound of any output is
+ * written.  c = r * row_len + j is cell j of row r.
+ * The draw.  W(r, j) is RowsMlmMaskBatchDevice's, word for word: Philox4x32-10(counter = {lo32(r), hi32(r), j, epoch}, key = {lo32(seed),
+ * hi32(seed)}), four 32-bit words.
+ * Present and eligible.  A cell is PRESENT iff (d_mask == NULL or d_mask[c] != 0) and (d_seg == NULL or d_seg[c] != 0).  It is ELIGIBLE iff it is
+ * present and d_rows[c] is none of special_ids[0 .. nspecial) -- a HOST array of at most BF_MLM_MAX_SPECIAL ids (eos_id, pad_id, ...).
+ * Starts and lengths.  Ts = (uint64) floor(start_prob * 4294967296.0), computed on the host in double and compared in 64 bits, so a
+ * probability of 1 means always.  An eligible cell h STARTS iff W(r, h)[0] < Ts, and then
+ *     len(h) = len_lo + (int)(((uint64)W(r, h)[1] * (uint64)(len_hi - len_lo + 1)) >> 32)
+ * -- uniform on [len_lo, len_hi], one Philox evaluation per eligible cell.
+ * Raw noise.  Cell j is raw noise iff it is eligible and there is an h <= j such that every cell of [h, j] is eligible, h starts and
+ * h + len(h) > j.  An ineligible cell (a special, padding, a cell outside the mask) therefore ends every span in front of it: no span
+ * crosses the [SEP] or </s> between two sequences of a packed or stream row, and a span that reaches past the row's end is cut there.
+ * Runs and the sentinel cap.  A run is a maximal stretch of consecutive raw-noise cells; overlapping and abutting spans are one run.  Runs
+ * are numbered k = 0, 1, ... in cell order.  A run with k >= max_sentinels is not noise: its cells are copied like any other.  NOISE cells are
+ * the cells of the runs k < max_sentinels; a run's BEGIN is its first cell; run k has the sentinel id sentinel_first + k * sentinel_step (T5:
+ * sentinel_first 32099, sentinel_step -1, max_sentinels 100).  keep(<j), noise(<j), begins(<j) count the present cells that are not noise, the
+ * noise cells and the begins in front of cell j; (<=j) includes j.
+ * Encoder row.  The present cells that are not noise, in cell order, with a run's sentinel standing where the run begins: cell j's output
+ * position is keep(<j) + begins(<j); a kept cell puts its id there, a begin its run's sentinel.  ne = keep + begins <= row_len, so
+ * enc_len = row_len always suffices.  Cells [ne, enc_len) get pad_id.
+ * Decoder row.  For every run in order its sentinel and then the ids of its cells; then eos_id when eos_id >= 0.  A noise cell's position is
+ * noise(<j) + begins(<=j), a sentinel's noise(<j) + begins(<j).  nd = noise + begins + (eos_id >= 0) <= row_len + 2.  Cells [nd, dec_len) get
+ * ignore_label, so the decoder row is a label tensor as it stands.
+ * Source-cell planes.  d_enc_cell_out [rows_cap * enc_len] and d_dec_cell_out [rows_cap * dec_len] hold the cell j a copied id came from, and
+ * -1 at a sentinel, at the eos and in the padding.  With them a caller gathers any other plane of the input rows (segment ids, positions, byte
+ * offsets) into the new layout with one gather; this call needs no "companion planes" form.
+ * Counts.  d_enc_count_out[r] = ne and d_dec_count_out[r] = nd, the UNTRUNCATED lengths; d_span_count_out[r] = the number of runs kept
+ * (min(runs, max_sentinels)).  [rows_cap] int32 each.
+ * Truncation.  An output position at or past enc_len / dec_len is not written.  A row that loses a cell this way (ne > enc_len or
+ * nd > dec_len), in an output the caller takes, sets BfLastStatus bit 0.  The call clears the status word first, like every batch call.
+ * NULL outputs.  Any of the seven outputs may be NULL; all seven NULL with rows_cap > 0 is BF_E_ARG.  enc_len is looked at only when d_enc_out
+ * or d_enc_cell_out is taken, dec_len only when d_dec_out or d_dec_cell_out is.
+ * Overlap.  No output may overlap d_rows, d_mask or d_seg (there is no in-place form): the compaction writes in front of cells that other lanes
+ * still read.  The call does not detect it.
+ * BF_E_ARG for row_len, enc_len (when used) or dec_len (when used) outside 1 .. 1 << 20; a negative rows_cap; a NULL d_rows with
+ * rows_cap > 0; nspecial outside 0 .. BF_MLM_MAX_SPECIAL or a NULL special_ids with nspecial > 0; start_prob outside [0, 1] (a NaN is);
+ * anything but 1 <= len_lo <= len_hi <= 1 << 20; max_sentinels outside 1 .. 1 << 20; sentinel_first or the last sentinel
+ * sentinel_first + (max_sentinels - 1) * sentinel_step (computed in 64 bits) outside [0, INT32_MAX]; a NULL ModelPtr (any live handle serves).
+ * The call has no workspace: it allocates nothing, with and without BfReserve.  It enqueues on `stream`, does not synchronise, reads nothing
+ * back and returns 0 or BF_E_*.  Every pointer needs only the natural alignment of its type.  The result depends on (seed, r, epoch) and the
+ * row alone: not on the grid, the number of rows or the order of calls.  A wave shares a row (a power-of-two slice of a wave when
+ * row_len <= 32) and walks it once, in chunks of as many cells.
+ * Not here: geometric span lengths; spans aligned to whole words; a host-buffer form; decoder_input_ids (the right shift is the model's);
+ * T5's exact-count noise mask (it needs a random partition of the row, which is a sequential shuffle). */
+BF_API int RowsDenoiseBatchDevice(void *ModelPtr, const int32_t *d_rows, int row_len, int64_t rows_cap, const int64_t *d_nrows,
+                           const uint8_t *d_mask, const int32_t *d_seg, int nspecial, const int32_t *special_ids,
+                           double start_prob, int len_lo, int len_hi, int sentinel_first, int sentinel_step, int max_sentinels,
+                           int eos_id, int pad_id, int ignore_label, uint64_t seed, uint32_t epoch,
+                           int enc_len, int32_t *d_enc_out, int32_t *d_enc_cell_out, int32_t *d_enc_count_out,
+                           int dec_len, int32_t *d_dec_out, int32_t *d_dec_cell_out, int32_t *d_dec_count_out,
+                           int32_t *d_span_count_out, void *stream);
 
 /* additive (no counterpart in the reference; this comment is the specification): PACKED rows -- several sequences share a row, a segment
  * plane keeps a model's attention block-diagonal and a position plane restarts at every sequence.  Where IdsToRowsBatch pads every sequence
@@ -609,13 +668,13 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
- * tokenizer calls, words and sentences, the row, pair-row, plane, packed, span-cell and MLM calls, IdsToText, DictGetInfo and
+ * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, span-cell, MLM and denoise calls, IdsToText, DictGetInfo and
  * WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
  * no status.
- * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow; bit 1 (2) and bit 4 (16) = an internal
+ * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow (RowsDenoiseBatchDevice: a row longer than enc_len / dec_len); bit 1 (2) and bit 4 (16) = an internal
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
  * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
  * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
