@@ -697,6 +697,10 @@ BF_API int BfModelKind(void *ModelPtr);
  * which synchronises the device and is not allowed inside a stream capture).  want_offsets != 0 also sizes the offsets API.
  * Every kind of handle has the workspaces of IdsToRowsBatchDevice and IdsToPairRowsBatchDevice (the same ones) and those of
  * IdsToPackedRowsBatchDevice (about 36 bytes per sequence) sized for max_docs sequences or pairs (an [i2w]-only handle has no others).
+ * The packed stage's workspaces also cover IdsToPackedRowsPlanesBatchDevice (one kernel behind the base call's, over what that call left
+ * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
+ * bound).  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
+ * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
  * A WordPiece handle also gets the buffers of TextToWordsBatchDevice / TextToSentencesBatchDevice (12 bytes per byte of text and 8 per
  * document); a handle with a [pos-dict] gets its lookup tables uploaded and the workspaces of DictGetInfoBatchDevice for max_docs keys; a
  * handle with [w2h] those of WordHyphenationBatchDevice for max_docs words.

@@ -5,7 +5,7 @@ A step is a name plus run(h, cx): it makes ONE C-ABI call (the Device calls on t
 returns (outputs, return value, BfLastStatus behind it).  Its `want` -- every output buffer in full, the return value, the status -- is computed
 here, once per process, from what the suite already trusts and never from the library under test: bfutil.reference() / bfutil.oracle() for ids and
 byte offsets, the checkers of secondary_cases for words, sentences, ids-to-text and the dictionary, the restatements of rows_cases, pair_cases,
-plane_cases, packed_cases and mlm_cases, the stored answers of w2h_cases.  A step sets the BfSetVariant value it needs (and BfSetHostChunkBytes
+plane_cases, packed_cases, packedplanes_cases, stream_cases, mlm_cases, mlmcap_cases and denoise_cases, the stored answers of w2h_cases.  A step sets the BfSetVariant value it needs (and BfSetHostChunkBytes
 where it takes the host path) at its start, so it never depends on what the step before it set, and every output goes into a buffer with TAIL
 entries of a sentinel behind its capacity: `want` holds the sentinel there too, so one comparison per buffer covers every element up to the
 count, what lies behind it and the offsets in full.
@@ -16,6 +16,16 @@ Two batch sizes, both of flat_cases / tiny_cases / bfutil.ADVERSARIAL material:
   small  37 documents of a few KB: below the limits of the mapped host path (256 documents, 64 KiB), no multiple of 64 or 4.
 A small step behind a big one of another program finds the big one's entries, lists, counts and spans just past its own extent.
 
+One catalogue per kind of handle (BUILDERS).  wordpiece, unigram and bpe cross the tokenizer programs with the host forms, the secondary calls and
+one step of each row stage; i2w crosses IdsToText -- its status 4 included -- with rows, packed rows, MLM, stream rows and a denoise call that
+ends with status 1; w2h has hyphenation.  `inputs`, on the WordPiece model again, is the catalogue of the model-input calls, kept apart from
+wordpiece because a walk grows with the square of its steps: a Device and a host tokenizer call that feed the others; the packed stage as the
+base call, as IdsToPackedRowsPlanesBatchDevice wide and narrow (a NULL plane among its slots) and as its host form; the stream stage, which
+borrows the packed stage's widths, block sums and W, with many sequences and few, cut by rows_cap (status 1), with a bad range (status 8) and as
+its host form; the host form of the rows-planes call, which owns the plane staging buffers the stream host form puts its labels in; the base MLM
+kernel beside RowsMlmPredictionsBatchDevice with max_pred > 0 (the capped kernel) and == 0 (the base kernel again); and RowsDenoiseBatchDevice
+with status 0 and with the status 1 its kernel sets by an atomic -- every one of them in front of and behind every other.
+
 The status a step wants is stated where the step is built, with its reason: 0, 1 (bit 0: its capacity was below the need), 8 (bit 3: a range outside
 the input) and, for IdsToText alone, 4 (bit 2: a sequence with an unknown id).  Bit 6 (the BPE pool too small) stays out: the pool only grows, so
 no step could bring it about again for the step behind it."""
@@ -25,13 +35,17 @@ import numpy as np
 
 import bfutil
 import blingfire_amd as bf
+import denoise_cases
 import flat_cases
 import mlm_cases
+import mlmcap_cases
 import packed_cases
+import packedplanes_cases
 import pair_cases
 import plane_cases
 import rows_cases
 import secondary_cases as sc
+import stream_cases
 import tiny_cases
 
 VP = ctypes.c_void_p
@@ -469,6 +483,227 @@ def mlm_step(name, size, ids, ido, st, en, L):
     return Step(name, call, want, 0, 0, "status 0: the call sets no bit", size)
 
 
+# ---- the model-input calls: packed planes, stream rows, capped MLM, span corruption, and the host-buffer forms of the row stages
+IGN = stream_cases.IGN
+BEHIND_ROWS = 3                                          # rows behind *d_nrows in the inputs and outputs of the denoise steps: never read, never written
+PRED_CAP = 2                                             # max_pred of the predictions step: tests/test_order_host.py proves that it binds in some rows and not in others
+DENOISE_TRUNCATED_DEC = 3                                # dec_len of the truncated denoise steps: a row with a span loses cells, a row without one (eos alone) does not
+
+
+def host_buffers(caps):
+    """sentinel-filled numpy outputs of a host-buffer call, one per (entries, dtype) with TAIL entries behind it"""
+    return [np.full(max(n + TAIL, 1), SENTINEL[np.dtype(t)], dtype=t) for n, t in caps]
+
+
+def packed_answer(ids, ido, L):
+    """packed_cases.restate with rows_cap == R, once per (ids, L); the status is 0"""
+    def compute():
+        out = packed_cases.restate(ids, ido, L, CLS, SEP, PAD, rows_cap=None)
+        assert out[7] == 0
+        return (ids, ido), frozen(*out[:6]) + (out[6],)                # (the key holds ids of objects: the entry keeps them alive)
+    return memo(("packed answer", id(ids), id(ido), L), compute)[1]
+
+
+def packed_wants(ids, ido, L, with_nrows):
+    rows, seg, pos, first, seq_row, seq_col, R = packed_answer(ids, ido, L)
+    nseq = len(ido) - 1
+    want = [Want(w, padded(a, R * L), ("rows", L)) for w, a in (("packed rows", rows), ("seg", seg), ("pos", pos))]
+    want += [Want("row_first_seq", padded(first, R + 1)), Want("seq_row", padded(seq_row, nseq)), Want("seq_col", padded(seq_col, nseq))]
+    if with_nrows:
+        want.append(Want("nrows", padded(np.array([R], dtype=np.int64), 1)))
+    return want, R
+
+
+def packed_planes_step(name, size, ids, ido, L, src, fill, narrow=False, skip_last=False):
+    """IdsToPackedRowsPlanesBatchDevice with rows_cap == R and one plane per source.  narrow: plane 0 begins 4 bytes behind a 16-byte boundary, one
+    sentinel entry into its buffer (as rows_step(narrow=True)), so every plane is stored cell by cell; skip_last: the last plane's out is NULL"""
+    nseq = len(ido) - 1
+    want, R = packed_wants(ids, ido, L, True)
+    planes = packedplanes_cases.restate_packed_planes(ido, L, CLS, SEP, src, fill, ids_len=len(ids))
+    taken = len(src) - (1 if skip_last else 0)
+    lead = 1 if narrow else 0
+    for k in range(taken):
+        front = np.full(lead if k == 0 else 0, -7, dtype=np.int32)
+        want.append(Want("plane %d" % k, np.concatenate([front, padded(planes[k], R * L)]), ("rows", L, len(front))))
+
+    def call(h, cx):
+        outs = [cx.full(R * L + TAIL, np.int32) for _ in range(3)] + [cx.full(R + 1 + TAIL, np.int32), cx.full(nseq + TAIL, np.int32), cx.full(nseq + TAIL, np.int32),
+                                                                       cx.full(1 + TAIL, np.int64)]
+        pl = [cx.full((lead if k == 0 else 0) + R * L + TAIL, np.int32) for k in range(taken)]
+        ptrs = [p.data_ptr() + (4 * lead if k == 0 else 0) for k, p in enumerate(pl)]
+        assert all(p.data_ptr() % 16 == 0 for p in pl) and (not narrow or ptrs[0] % 16 == 4)
+        c_src = (VP * len(src))(*[cx.ptr(s) for s in src])
+        c_fill = (ctypes.c_int32 * len(src))(*fill)
+        c_out = (VP * len(src))(*(ptrs + [None] * (len(src) - taken)))
+        r = bf.lib().IdsToPackedRowsPlanesBatchDevice(VP(h), cx.ptr(ids), len(ids), cx.ptr(ido), nseq, L, CLS, SEP, PAD, 0, *[o.data_ptr() for o in outs[:4]], R,
+                                                      *[o.data_ptr() for o in outs[4:]], len(src), c_src, c_fill, c_out, cx.stream)
+        return r, outs + pl
+    step = Step(name, call, want, 0, 0, "status 0: every id range inside [0, ids_len], rows_cap is R", size)
+    step.L, step.fill, step.taken, step.plane_lead = L, tuple(fill), taken, lead
+    return step
+
+
+def packed_planes_host_step(name, size, ids, ido, L, src, fill):
+    """IdsToPackedRowsPlanesBatch into numpy buffers with rows_cap == R; returns R"""
+    nseq = len(ido) - 1
+    want, R = packed_wants(ids, ido, L, False)
+    planes = packedplanes_cases.restate_packed_planes(ido, L, CLS, SEP, src, fill)
+    want += [Want("plane %d" % k, padded(p, R * L), ("rows", L)) for k, p in enumerate(planes)]
+
+    def call(h, cx):
+        outs = host_buffers([(R * L, np.int32)] * 3 + [(R + 1, np.int32), (nseq, np.int32), (nseq, np.int32)] + [(R * L, np.int32)] * len(src))
+        c_src = (VP * len(src))(*[s.ctypes.data for s in src])
+        c_fill = (ctypes.c_int32 * len(src))(*fill)
+        c_out = (VP * len(src))(*[o.ctypes.data for o in outs[6:]])
+        r = bf.lib().IdsToPackedRowsPlanesBatch(VP(h), ids.ctypes.data, ido.ctypes.data, nseq, L, CLS, SEP, PAD, 0, *[o.ctypes.data for o in outs[:4]], R,
+                                                outs[4].ctypes.data, outs[5].ctypes.data, len(src), c_src, c_fill, c_out)
+        return r, outs
+    step = Step(name, call, want, R, 0, "status 0: every id range inside the ids, rows_cap is R", size)
+    step.L, step.fill, step.taken, step.plane_lead = L, tuple(fill), len(src), 0
+    return step
+
+
+def rows_planes_host_step(name, size, ids, ido, L, stride, max_rows, src, fill):
+    """IdsToRowsPlanesBatch into numpy buffers with rows_cap == the exact total; returns the total"""
+    nseq = len(ido) - 1
+    rows, mask, seq, first, r_off, status = rows_cases.restate(ids, ido, L, CLS, SEP, PAD, stride, max_rows)
+    w_planes, seq2, _, r_off2, status2 = plane_cases.restate_planes(ido, L, CLS, SEP, stride, max_rows, False, src, fill, ids_len=len(ids))
+    assert status == 0 and status2 == 0 and np.array_equal(r_off2, r_off) and np.array_equal(seq2, seq)
+    R = len(seq)
+    want = [Want("rows", padded(rows, R * L), ("rows", L)), Want("mask", padded(mask, R * L), ("rows", L)), Want("row_seq", padded(seq, R)), Want("row_first", padded(first, R)),
+            Want("row offsets", r_off)]
+    want += [Want("plane %d" % k, padded(p, R * L), ("rows", L)) for k, p in enumerate(w_planes)]
+
+    def call(h, cx):
+        outs = host_buffers([(R * L, np.int32), (R * L, np.uint8), (R, np.int32), (R, np.int32)]) + [np.full(nseq + 1, -7, dtype=np.int64)]
+        pl = host_buffers([(R * L, np.int32)] * len(src))
+        c_src = (VP * len(src))(*[s.ctypes.data for s in src])
+        c_fill = (ctypes.c_int32 * len(src))(*fill)
+        c_out = (VP * len(src))(*[p.ctypes.data for p in pl])
+        r = bf.lib().IdsToRowsPlanesBatch(VP(h), ids.ctypes.data, ido.ctypes.data, nseq, L, CLS, SEP, PAD, stride, max_rows, 0, *[o.ctypes.data for o in outs[:4]], R,
+                                          outs[4].ctypes.data, len(src), c_src, c_fill, c_out)
+        return r, outs + pl
+    return Step(name, call, want, R, 0, "status 0: every id range inside the ids, rows_cap is the exact total", size)
+
+
+def stream_answer(ids, off, L, bos, eos, flags, ids_len=None):
+    """stream_cases.restate_np, once per input: tests/test_order_host.py holds it to the sequential stream_cases.restate on every small step"""
+    return memo(("stream answer", id(ids), id(off), L, bos, eos, flags, ids_len),
+                lambda: ((ids, off), stream_cases.restate_np(ids, off, L, bos, eos, PAD, IGN, flags, ids_len=len(ids) if ids_len is None else ids_len)))[1]
+
+
+def stream_step(name, size, ids, off, L, bos, eos, flags=0, rows_cap=None, host=False, status=0, why="status 0: every id range inside [0, ids_len], rows_cap is R"):
+    """IdsToStreamRowsBatchDevice with all eight outputs and d_nrows_out = {R, T}, or (host) IdsToStreamRowsBatch into numpy buffers, which returns R;
+    rows_cap None = R.  Nothing at or past rows_cap of a row output is written: `want` holds the sentinel there"""
+    nseq = len(off) - 1
+    ans = stream_answer(ids, off, L, bos, eos, flags)
+    R, T = ans[8], ans[9]
+    cap = R if rows_cap is None else rows_cap
+    assert status == (ans[10] | (1 if R > cap else 0)) and not (host and status)
+    want = [Want("stream " + w, padded(a, cap * L), ("rows", L)) for w, a in zip(stream_cases.NAMES[:4], ans[:4])]
+    want += [Want(w, padded(a, cap)) for w, a in zip(stream_cases.NAMES[4:6], ans[4:6])] + [Want(w, padded(a, nseq)) for w, a in zip(stream_cases.NAMES[6:], ans[6:8])]
+    caps = [(cap * L, np.int32)] * 4 + [(cap, np.int32)] * 2 + [(nseq, np.int32)] * 2
+    if not host:
+        want.append(Want("nrows", padded(np.array([R, T], dtype=np.int64), 2)))
+
+    def call_device(h, cx):
+        outs = [cx.full(n + TAIL, t) for n, t in caps] + [cx.full(2 + TAIL, np.int64)]
+        r = bf.lib().IdsToStreamRowsBatchDevice(VP(h), cx.ptr(ids), len(ids), cx.ptr(off), nseq, L, bos, eos, PAD, IGN, flags, *[o.data_ptr() for o in outs[:6]], cap,
+                                                *[o.data_ptr() for o in outs[6:]], cx.stream)
+        return r, outs
+
+    def call_host(h, cx):
+        outs = host_buffers(caps)
+        r = bf.lib().IdsToStreamRowsBatch(VP(h), ids.ctypes.data, off.ctypes.data, nseq, L, bos, eos, PAD, IGN, flags, *[o.ctypes.data for o in outs[:6]], cap,
+                                          outs[6].ctypes.data, outs[7].ctypes.data)
+        return r, outs
+    step = Step(name, call_host if host else call_device, want, R if host else 0, status, why, size)
+    step.stream = dict(ids=ids, off=off, L=L, bos=bos, eos=eos, flags=flags, rows_cap=cap, R=R, T=T)
+    return step
+
+
+def stream_rows(ids, ido, L, bos=CLS, eos=SEP):
+    """(rows, seg) of the restated stream rows, flags 0: the inputs of the denoise steps"""
+    ans = stream_answer(ids, ido, L, bos, eos, 0)
+    return ans[0], ans[1]
+
+
+def packed_mlm_inputs(ids, ido, st, en, L):
+    """(rows, seg, first-byte plane, last-byte plane) of the restated packed rows: the inputs of the predictions steps"""
+    def compute():
+        rows, seg = packed_answer(ids, ido, L)[:2]
+        S, E = packedplanes_cases.restate_packed_planes(ido, L, CLS, SEP, (st, en), (-1, -1), ids_len=len(ids))
+        return (ids, ido), frozen(rows, seg, S, E)
+    return memo(("packed mlm inputs", id(ids), id(ido), L), compute)[1]
+
+
+MLM_SPECIALS = (CLS, SEP, PAD)
+
+
+def predictions_step(name, size, ids, ido, st, en, L, max_pred):
+    """RowsMlmPredictionsBatchDevice over the packed rows with their segment plane and the two byte-offset planes (whole words).  max_pred > 0: all
+    five outputs (k_rows_mlm_cap); max_pred == 0: the gathered outputs NULL, the base kernel, and `want` is mlm_cases.restate_mlm's"""
+    rows, seg, S, E = packed_mlm_inputs(ids, ido, st, en, L)
+    R = len(rows)
+    kw = dict(special_ids=MLM_SPECIALS, probs=mlmcap_cases.PROBS, mask_id=mlm_cases.MASK, rand_range=mlm_cases.RAND_RANGE, ignore_label=-100, seed=MLM_SEED, epoch=MLM_EPOCH)
+    if max_pred:
+        w = mlmcap_cases.restate_cap(rows, None, seg, S, E, max_pred=max_pred, **kw)
+        want = [Want("masked ids", padded(w[0], R * L), ("rows", L)), Want("labels", padded(w[1], R * L), ("rows", L)), Want("prediction cells", padded(w[2], R * max_pred), ("rows", max_pred)),
+                Want("prediction labels", padded(w[3], R * max_pred), ("rows", max_pred)), Want("prediction count", padded(w[4], R))]
+    else:
+        w = mlm_cases.restate_mlm(rows, None, seg, S, E, **kw)
+        want = [Want("masked ids", padded(w[0], R * L), ("rows", L)), Want("labels", padded(w[1], R * L), ("rows", L))]
+
+    def call(h, cx):
+        outs = [cx.full(R * L + TAIL, np.int32) for _ in range(2)] + ([cx.full(R * max_pred + TAIL, np.int32), cx.full(R * max_pred + TAIL, np.int32), cx.full(R + TAIL, np.int32)] if max_pred else [])
+        c_spec = (ctypes.c_int32 * len(MLM_SPECIALS))(*MLM_SPECIALS)
+        gathered = [o.data_ptr() for o in outs[2:]] if max_pred else [None] * 3
+        r = bf.lib().RowsMlmPredictionsBatchDevice(VP(h), cx.ptr(rows), L, R, None, None, cx.ptr(seg), cx.ptr(S), cx.ptr(E), len(MLM_SPECIALS), c_spec, *mlmcap_cases.PROBS,
+                                                   mlm_cases.MASK, *mlm_cases.RAND_RANGE, -100, MLM_SEED, MLM_EPOCH, outs[0].data_ptr(), outs[1].data_ptr(), max_pred, *gathered, cx.stream)
+        return r, outs
+    step = Step(name, call, want, 0, 0, "status 0: the call sets no bit", size)
+    step.mlm = dict(rows=rows, seg=seg, S=S, E=E, max_pred=max_pred, kw=kw)
+    return step
+
+
+def denoise_spec():
+    """the case table's defaults (denoise_cases.DEFAULTS with the T5 sentinels) over rows of this model: [SEP] closes a sequence, so it is the eos, and
+    with [CLS] and the padding it is special -- no span crosses it"""
+    return dict(denoise_cases.DEFAULTS, special_ids=MLM_SPECIALS, eos_id=SEP, pad_id=PAD)
+
+
+def denoise_step(name, size, rows, seg, L, enc_len, dec_len, status, why):
+    """RowsDenoiseBatchDevice over R rows and their segment plane with rows_cap = R + BEHIND_ROWS and *d_nrows = R: the rows behind the bound hold
+    eligible cells in the input (if the call looked at them) and keep the sentinel in all seven outputs"""
+    R = len(rows)
+    cap = R + BEHIND_ROWS
+    spec = denoise_spec()
+    w = denoise_cases.restate_denoise(rows, None, seg, enc_len=enc_len, dec_len=dec_len, **spec)
+    assert w["status"] == status
+    width = dict(enc=enc_len, enc_cell=enc_len, dec=dec_len, dec_cell=dec_len, enc_count=1, dec_count=1, span_count=1)
+    want = [Want(n, padded(w[n], cap * width[n]), ("rows", width[n]) if width[n] > 1 else ("items",)) for n in denoise_cases.NAMES]
+    rows_in = frozen(np.concatenate([rows.reshape(-1), np.full(BEHIND_ROWS * L, 4242, dtype=np.int32)]))
+    seg_in = frozen(np.concatenate([seg.reshape(-1), np.ones(BEHIND_ROWS * L, dtype=np.int32)]))
+    nrows = frozen(np.array([R], dtype=np.int64))
+
+    def call(h, cx):
+        outs = [cx.full(cap * width[n] + TAIL, np.int32) for n in denoise_cases.NAMES]
+        c_spec = (ctypes.c_int32 * len(spec["special_ids"]))(*spec["special_ids"])
+        o = [t.data_ptr() for t in outs]
+        r = bf.lib().RowsDenoiseBatchDevice(VP(h), cx.ptr(rows_in), L, cap, cx.ptr(nrows), None, cx.ptr(seg_in), len(spec["special_ids"]), c_spec, spec["start_prob"], spec["len_lo"],
+                                            spec["len_hi"], spec["sentinel_first"], spec["sentinel_step"], spec["max_sentinels"], spec["eos_id"], spec["pad_id"], spec["ignore_label"],
+                                            spec["seed"], spec["epoch"], enc_len, o[0], o[1], o[2], dec_len, o[3], o[4], o[5], o[6], cx.stream)
+        return r, outs
+    step = Step(name, call, want, 0, status, why, size)
+    step.denoise = dict(rows=rows, seg=seg, L=L, enc_len=enc_len, dec_len=dec_len, answer=w)
+    return step
+
+
+def denoise_truncated_step(name, size, ids, ido, L=12):
+    rows, seg = stream_rows(ids, ido, L)
+    return denoise_step(name, size, rows, seg, L, L, DENOISE_TRUNCATED_DEC, 1, "status 1: a row's decoder targets are longer than dec_len (bit 0, set by the kernel's atomic)")
+
+
 # ---- the secondary calls
 def two_pass_step(name, size, fn_name, pre, n, w_flat, w_off, post=(), extras=(), query=False, status=0, why="status 0: the capacity is the exact total", where=None):
     """a Device call of the two-pass kind (IdsToText, DictGetInfo, WordHyphenation): pre = the arguments in front of the output, (array | int), post
@@ -669,6 +904,8 @@ def i2w():
     bi, bo = packed_in["ids to text big"]
     si, so = packed_in["ids to text small"]
     steps += [rows_step("rows L=12 windows small", "small", si, so, 12, 3, 0, narrow=True), packed_step("packed L=64 big", "big", bi, bo, 64), mlm_step("mlm L=12 small", "small", si, so, None, None, 12)]
+    # a handle without a tokenizer: the stream stage and the denoise call's status 1 meet IdsToText's status 4
+    steps += [stream_step("stream L=12 small", "small", si, so, 12, CLS, SEP), denoise_truncated_step("denoise L=12 small, truncated", "small", si, so)]
     return Catalogue("i2w", bfutil.model_path(model), steps)
 
 
@@ -708,7 +945,46 @@ def w2h():
     return Catalogue("w2h", wc.FIXTURE, steps)
 
 
-BUILDERS = {"wordpiece": wordpiece, "unigram": unigram, "bpe": bpe, "i2w": i2w, "w2h": w2h}
+STREAM_DROP_WITHIN = stream_cases.DROP_LAST | stream_cases.LABELS_WITHIN
+
+
+def inputs():
+    """the model-input calls on a WordPiece handle: the tokenizer calls that feed them (Device and host), the packed stage with its planes form, the
+    stream stage, the capped MLM call beside the base one, span corruption, and a host-buffer form of every row stage.  18 steps, three on the
+    big batch; the ids and byte offsets are the checker's, as in wordpiece()"""
+    model = bfutil.bert_model_name()
+    if not bfutil.have_model(model):
+        return None
+    pair = WP_PAIR
+    si, ss, se, so = offsets_answer(model, "small", pair)
+    bi, bs, be, bo = offsets_answer(model, "big", pair)
+    steps = [tok_device_step("wave small offsets", "small", batch("small"), (si, ss, se, so), 5, pair),
+             tok_device_step("flat big ids", "big", batch("big"), ids_answer(model, "big", pair), 4, pair),
+             host_batch_step("TextToIdsBatch small", "small", ids_answer(model, "small", pair), 3, pair),
+             packed_step("packed L=12 small", "small", si, so, 12),
+             packed_planes_step("packed planes L=12 big", "big", bi, bo, 12, (bs, be), (-1, -1)),
+             packed_planes_step("packed planes L=64 small, narrow", "small", si, so, 64, (ss, se, si), (-1, -1, -1), narrow=True, skip_last=True),
+             packed_planes_host_step("packed planes host L=12 small", "small", si, so, 12, (ss, se), (-1, -1)),
+             rows_planes_host_step("rows planes host L=12 small", "small", si, so, 12, 3, 0, (ss, se), (-1, -1)),
+             stream_step("stream L=64 big", "big", bi, bo, 64, CLS, SEP),
+             stream_step("stream L=13 small", "small", si, so, 13, -1, SEP, STREAM_DROP_WITHIN)]
+    R12 = stream_answer(si, so, 12, CLS, SEP, 0)[8]
+    bad = bad_range_offsets(so)
+    steps += [stream_step("stream L=12 small overflow", "small", si, so, 12, CLS, SEP, rows_cap=R12 // 2, status=1,
+                          why="status 1: rows_cap is below the row count (bit 0); nothing at or past rows_cap is written"),
+              stream_step("stream small bad range", "small", si, bad, 12, CLS, SEP, status=8,
+                          why="status 8: the last sequence claims ids behind ids_len (bit 3) and is read as empty; every other sequence keeps its answer"),
+              stream_step("stream host L=12 small", "small", si, so, 12, CLS, SEP, host=True),
+              mlm_step("mlm mask L=64 small", "small", si, so, ss, se, 64),
+              predictions_step("mlm predictions L=12 small", "small", si, so, ss, se, 12, PRED_CAP),
+              predictions_step("mlm predictions max_pred=0 L=12 small", "small", si, so, ss, se, 12, 0)]
+    rows, seg = stream_rows(si, so, 64)
+    steps += [denoise_step("denoise L=64 small", "small", rows, seg, 64, 64, 66, 0, "status 0: enc_len = L and dec_len = L + 2 hold every row"),
+              denoise_truncated_step("denoise L=12 small, truncated", "small", si, so)]
+    return Catalogue("inputs", bfutil.model_path(model), steps)
+
+
+BUILDERS = {"wordpiece": wordpiece, "unigram": unigram, "bpe": bpe, "i2w": i2w, "w2h": w2h, "inputs": inputs}
 
 
 def catalogue(kind):

@@ -109,6 +109,14 @@ def seq_shapes(D, long_len=3000):
             "ones": [1] * D, "empty": [], "half": [mix[(i + 3) % len(mix)] for i in range(D // 2)]}
 
 
+STREAM_ROW_LENS = (16, 2)                   # of the stream stage: the row length of the other row stages, and one at which `one_long` gives far more rows than sequences
+
+
+def stream_row_count(lens, L, specials=2):
+    """the rows IdsToStreamRowsBatch cuts sequences of these lengths into, every sequence with `specials` ids around it (the last row may be incomplete)"""
+    return -(-(sum(lens) + specials * len(lens)) // L)
+
+
 def hyphenation_words():
     """name -> words of the hyphenation case: the text shapes of the small bound, a document standing for a word (D words, B bytes)"""
     return shapes(*SMALL)

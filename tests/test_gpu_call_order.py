@@ -2,7 +2,10 @@
 nothing in a workspace is cleared between calls and the control words are cleared call by call, so a forgotten clear or a kernel that reads one element
 past its own extent shows only in what the NEXT call on the handle computes.  Per kind of handle the steps of tests/order_cases.py -- the tokenizer programs
 on a big and a small batch, the host forms, words and sentences, rows, pair rows, planes, packed rows, span cells, MLM, ids-to-text, the dictionary lookup,
-hyphenation, calls that end with status 1, 4 or 8 -- run in the order of order_cases.circuit(), in which every ordered pair, a step behind itself included,
+hyphenation, calls that end with status 1, 4 or 8; and, as the kind `inputs` on a WordPiece handle of its own, the model-input calls: packed rows with
+their planes form, stream rows, the capped MLM call beside the base one, span corruption, and the host-buffer forms of the packed, stream and rows-planes
+stages, crossed with each other and with a Device and a host tokenizer call (the i2w kind crosses stream rows and a denoise call of status 1 with
+IdsToText's status 4) -- run in the order of order_cases.circuit(), in which every ordered pair, a step behind itself included,
 is neighbours exactly once (tests/test_order_host.py asserts that).  Behind every call: its return value, BfLastStatus -- the rule is that it is the call's
 OWN, whatever the call before it left -- and every output buffer in full (every element up to the count, the sentinel behind it, the offsets) against the
 checker's answer, on the device; a failure names the pair and the first document or row that differs, and ends the walk of that handle.

@@ -17,12 +17,17 @@ import pytest
 
 import bfutil
 import blingfire_amd as bf
+import denoise_cases
+import mlm_cases
+import mlmcap_cases
 import packed_cases
+import packedplanes_cases
 import pair_cases
 import plane_cases
 import reserve_cases as rv
 import rows_cases
 import secondary_cases as sc
+import stream_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -291,7 +296,9 @@ def test_word_hyphenation_allocates_nothing_after_reserve(at_scale, L):
 
 
 # ------------------------------------------------------------------------------------------------
-# the row stages: on a WordPiece handle and on an [i2w]-only handle (every kind of handle has their workspaces)
+# the row stages: on a WordPiece handle and on an [i2w]-only handle (every kind of handle has their workspaces).  The planes form of the packed
+# call and the stream rows live in the packed stage's workspaces; the MLM, predictions and denoise calls have none, and run here over the rows
+# the packed and the rows call of the same handle just left on the device
 # ------------------------------------------------------------------------------------------------
 ROW_L, ROW_STRIDE = 16, 4
 
@@ -320,7 +327,9 @@ def stage_rows(r, lens, name):
     with torch_().cuda.stream(r.stream):
         got = bf.ids_to_rows_batch_device(r.h, d_ids, d_off, ROW_L, CLS, SEP, PAD, ROW_STRIDE, 0, False, stream=r.stream.cuda_stream)
     what = r.check("IdsToRowsBatchDevice, shape %s" % name)
-    _same(got, rows_cases.restate(ids, off, ROW_L, CLS, SEP, PAD, ROW_STRIDE, 0, False)[:5], what)
+    want = rows_cases.restate(ids, off, ROW_L, CLS, SEP, PAD, ROW_STRIDE, 0, False)
+    _same(got, want[:5], what)
+    return got, want
 
 
 def stage_pairs(r, lens, name):
@@ -386,10 +395,84 @@ def stage_packed(r, lens, name):
     want = packed_cases.restate(ids, off, ROW_L, CLS, SEP, PAD)
     _same(got[:6], want[:6], what)
     assert int(got[6].item()) == want[6], what
+    return got, want
+
+
+def stage_packed_planes(r, lens, name):
+    """the planes form of the packed call: one kernel behind the base call's, over what that call left in the packed stage's workspaces"""
+    ids, off = packed_cases.ragged(lens)
+    src = list(_token_spans(len(ids)))
+    d_ids, d_off, s0, s1 = _dev(r.stream, ids, off, *src)
+    with torch_().cuda.stream(r.stream):
+        got = bf.ids_to_packed_rows_batch_device(r.h, d_ids, d_off, ROW_L, CLS, SEP, PAD, stream=r.stream.cuda_stream, planes=[s0, s1], fill=[-1, -1])
+    what = r.check("IdsToPackedRowsPlanesBatchDevice, shape %s" % name)
+    want = packed_cases.restate(ids, off, ROW_L, CLS, SEP, PAD)
+    _same(got[:6], want[:6], what)
+    assert int(got[6].item()) == want[6] and len(got) == 9, what
+    _same(got[7:], packedplanes_cases.restate_packed_planes(off, ROW_L, CLS, SEP, src, [-1, -1], ids_len=len(ids)), what)
+
+
+def stage_stream(r, lens, name):
+    """stream rows with both specials, at every row length of rv.STREAM_ROW_LENS: on `one_long` the rows are several times the sequences (R is not bounded
+    by nseq), and the claim that no workspace is sized by the row count is on trial (tests/test_reserve_cases_host.py counts the rows)"""
+    ids, off = packed_cases.ragged(lens)
+    d_ids, d_off = _dev(r.stream, ids, off)
+    for L in rv.STREAM_ROW_LENS:
+        with torch_().cuda.stream(r.stream):
+            got = bf.ids_to_stream_rows_batch_device(r.h, d_ids, d_off, L, CLS, SEP, PAD, stream=r.stream.cuda_stream)
+        what = r.check("IdsToStreamRowsBatchDevice, row_len %d, shape %s" % (L, name))
+        want = stream_cases.restate_np(ids, off, L, CLS, SEP, PAD)
+        assert want[8] == rv.stream_row_count(lens, L) and want[10] == 0, what
+        _same(got[:8], want[:8], what)
+        assert got[8].tolist() == [want[8], want[9]], what
+
+
+MLM_SPECIALS = (CLS, SEP, PAD)
+MLM_KW = dict(special_ids=MLM_SPECIALS, probs=mlmcap_cases.PROBS, mask_id=mlm_cases.MASK, rand_range=mlm_cases.RAND_RANGE, ignore_label=-100, seed=0x51ED, epoch=2)
+MLM_MAX_PRED = 2
+DENOISE_KW = dict(denoise_cases.DEFAULTS, special_ids=MLM_SPECIALS, eos_id=SEP, pad_id=PAD, seed=0x51ED, epoch=2)
+
+
+def _row_sources(r, lens, name):
+    """the rows of stage_packed (with their segment plane) and of stage_rows (with their mask) of this call sequence, as the calls left them on the
+    device, each with its row bound and with the restated rows: (rows, keywords of the planes and the bound, restated rows, mask, seg)"""
+    pg, pw = stage_packed(r, lens, name)
+    rg, rw = stage_rows(r, lens, name)
+    return [("packed rows", pg[0], dict(seg=pg[1], nrows=pg[6]), (pw[0], None, pw[1])), ("rows", rg[0], dict(mask=rg[1], nrows=rg[4][-1:]), (rw[0], rw[1], None))]
+
+
+def stage_mlm(r, lens, name, max_pred=0):
+    """RowsMlmMaskBatchDevice (max_pred 0) / RowsMlmPredictionsBatchDevice: no workspace, so the counter must not move"""
+    for src, d_rows, planes, (w_rows, w_mask, w_seg) in _row_sources(r, lens, name):
+        with torch_().cuda.stream(r.stream):
+            got = bf.rows_mlm_mask_device(r.h, d_rows, **planes, special_ids=MLM_SPECIALS, select_prob=MLM_KW["probs"][0], mask_prob=MLM_KW["probs"][1], random_prob=MLM_KW["probs"][2],
+                                          mask_id=MLM_KW["mask_id"], rand_range=MLM_KW["rand_range"], seed=MLM_KW["seed"], epoch=MLM_KW["epoch"], stream=r.stream.cuda_stream,
+                                          max_predictions=max_pred)
+        what = r.check("%s over %s, shape %s" % ("RowsMlmPredictionsBatchDevice" if max_pred else "RowsMlmMaskBatchDevice", src, name))
+        if max_pred:
+            want = mlmcap_cases.restate_cap(w_rows, w_mask, w_seg, max_pred=max_pred, **MLM_KW)
+        else:
+            want = mlm_cases.restate_mlm(w_rows, w_mask, w_seg, **MLM_KW)
+        assert len(got) == len(want), what
+        _same(got, want, what)
+
+
+def stage_denoise(r, lens, name):
+    """RowsDenoiseBatchDevice with enc_len = L and dec_len = L + 2, which lose no cell (status 0): no workspace either"""
+    names = dict(input_ids="enc", labels="dec", enc_count="enc_count", dec_count="dec_count", span_count="span_count", enc_cells="enc_cell", dec_cells="dec_cell")
+    kw = {k: v for k, v in DENOISE_KW.items()}
+    for src, d_rows, planes, (w_rows, w_mask, w_seg) in _row_sources(r, lens, name):
+        with torch_().cuda.stream(r.stream):
+            got = bf.rows_denoise_device(r.h, d_rows, **planes, return_cells=True, stream=r.stream.cuda_stream, **kw)
+        what = r.check("RowsDenoiseBatchDevice over %s, shape %s" % (src, name))
+        want = denoise_cases.restate_denoise(w_rows, w_mask, w_seg, **kw)
+        assert want["status"] == 0 and set(got) == set(names), what
+        _same([got[k] for k in names], [want[n] for n in names.values()], what)
 
 
 STAGES = {"rows": stage_rows, "pair_rows": stage_pairs, "rows_planes": stage_rows_planes, "pair_rows_planes": stage_pair_planes, "span_cells": stage_span_cells,
-          "packed_rows": stage_packed}
+          "packed_rows": stage_packed, "packed_rows_planes": stage_packed_planes, "stream_rows": stage_stream, "mlm_mask": stage_mlm,
+          "mlm_predictions": lambda r, lens, name: stage_mlm(r, lens, name, MLM_MAX_PRED), "denoise": stage_denoise}
 
 
 @pytest.mark.parametrize("stage", list(STAGES))
@@ -400,5 +483,82 @@ def test_row_stages_allocate_nothing_after_reserve(model, stage):
     try:
         for name, lens in rv.seq_shapes(D, long_len=300).items():
             STAGES[stage](r, lens, name)
+    finally:
+        r.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# text to model inputs: the tokenizer and the stages behind it in one wrapper call, on the WordPiece handle
+# ------------------------------------------------------------------------------------------------
+UNK = 100
+SENTINEL_FIRST = 30521                  # made-up sentinel ids: the last ids of the BERT vocabulary, downwards
+
+
+def test_text_to_model_inputs_allocates_nothing_after_reserve():
+    """encode_clm_batch_device, encode_denoise_batch_device (both sources) and encode_packed_mlm_batch_device on a handle reserved with
+    want_offsets, on the text shapes that touch the bound with many documents (`even`) and with one long one (`one_long`: the stream rows are
+    several times the documents).  Every output is the restatement's over the tokenizer checker's ids and byte offsets."""
+    torch = torch_()
+    D, B = rv.SMALL
+    L = ROW_L
+    names = dict(input_ids="enc", labels="dec", enc_count="enc_count", dec_count="dec_count", span_count="span_count", enc_cells="enc_cell", dec_cells="dec_cell")
+    dn = dict(start_prob=0.2, len_lo=1, len_hi=4, sentinel_first=SENTINEL_FIRST, sentinel_step=-1, max_sentinels=100, seed=31, epoch=2)
+    r = Reserved(WP, D, B, True)
+    try:
+        shapes = rv.shapes(D, B)
+        for name in ("even", "one_long"):
+            docs = shapes[name]
+            ids, st, en, off = expected_ids(WP, UNK, (D, B, name), docs)
+            text, doc_off = rv.pack(docs)
+            d_text, d_off = _dev(r.stream, text, doc_off)
+
+            # causal LM: every id of every document, [CLS] and [SEP] around it
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_clm_batch_device(r.h, d_text, d_off, L, CLS, SEP, PAD, UNK)
+            what = r.check("encode_clm_batch_device, shape %s" % name)
+            want = stream_cases.restate_np(ids, off, L, CLS, SEP, PAD)
+            R, T = want[8], want[9]
+            assert got["nrows"].tolist() == [R, T] and got["input_ids"].shape[0] >= R, what
+            if name == "one_long":
+                assert R > 3 * D, (what, R)
+            _same([got[k][:R] for k in list(got)[:6]] + [got["seq_row"], got["seq_col"]], want[:8], what)
+
+            # span corruption over stream rows (no bos, [SEP] closes a document) ...
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_denoise_batch_device(r.h, d_text, d_off, L, SEP, PAD, SENTINEL_FIRST, dn["seed"], epoch=dn["epoch"], source="stream", unk=UNK,
+                                                     start_prob=dn["start_prob"], len_hi=dn["len_hi"], return_cells=True)
+            what = r.check("encode_denoise_batch_device from stream rows, shape %s" % name)
+            rows = stream_cases.restate_np(ids, off, L, -1, SEP, PAD)
+            n = rows[8]
+            assert int(got["nrows"].item()) == n > 0, what
+            _same([got["rows"][:n], got["seg"][:n]], rows[:2], what)
+            want = denoise_cases.restate_denoise(rows[0], None, rows[1], special_ids=sorted({SEP, PAD}), eos_id=SEP, pad_id=PAD, **dn)
+            assert want["status"] == 0 and (want["span_count"] > 0).any(), what
+            _same([got[k][:n] for k in names], [want[v] for v in names.values()], what)
+
+            # ... and over one truncated row per document
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_denoise_batch_device(r.h, d_text, d_off, L, SEP, PAD, SENTINEL_FIRST, dn["seed"], epoch=dn["epoch"], source="rows", unk=UNK,
+                                                     start_prob=dn["start_prob"], len_hi=dn["len_hi"], return_cells=True)
+            what = r.check("encode_denoise_batch_device from rows, shape %s" % name)
+            w_rows, w_mask = rows_cases.restate(ids, off, L, -1, SEP, PAD, 0, 1, False)[:2]
+            assert int(got["nrows"].item()) == D == len(w_rows), what
+            _same([got["rows"], got["mask"]], [w_rows, w_mask], what)
+            want = denoise_cases.restate_denoise(w_rows, w_mask, None, special_ids=sorted({SEP, PAD}), eos_id=SEP, pad_id=PAD, **dn)
+            assert want["status"] == 0, what
+            _same([got[k] for k in names], [want[v] for v in names.values()], what)
+
+            # whole-word MLM over packed rows: the offsets call, the packed call with its planes, the MLM call
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_packed_mlm_batch_device(r.h, d_text, d_off, L, CLS, SEP, PAD, mlm_cases.MASK, mlm_cases.RAND_RANGE, seed=MLM_KW["seed"], epoch=MLM_KW["epoch"],
+                                                        unk=UNK, select_prob=MLM_KW["probs"][0])
+            what = r.check("encode_packed_mlm_batch_device, shape %s" % name)
+            pk = packed_cases.restate(ids, off, L, CLS, SEP, PAD)
+            S, E = packedplanes_cases.restate_packed_planes(off, L, CLS, SEP, [st, en], [-1, -1], ids_len=len(ids))
+            w_ids, w_labels = mlm_cases.restate_mlm(pk[0], None, pk[1], S, E, special_ids=MLM_SPECIALS, probs=(MLM_KW["probs"][0],) + mlm_cases.DEFAULT_PROBS[1:],
+                                                    seed=MLM_KW["seed"], epoch=MLM_KW["epoch"])
+            assert len(got) == 10 and int(got[6].item()) == pk[6], what
+            _same(got[:6] + got[7:], [w_ids] + list(pk[1:6]) + [S, E, w_labels], what)
+            assert (w_labels != -100).any(), what
     finally:
         r.close()

@@ -94,3 +94,22 @@ def test_the_stored_hyphenation_answers_are_those_of_the_shapes():
         for w, t in zip(docs, want[name]):
             assert t == "" or min(len(w), 300) <= len(t) <= 2 * len(w), (name, w[:40], len(t))
     assert any("-" in t for t in want["even"])
+
+
+def test_the_stream_stage_has_more_rows_than_sequences_on_the_long_shape():
+    """IdsToStreamRowsBatchDevice claims that no workspace of its is sized by the row count: the shape that tries it has several times as many rows as
+    sequences, all of them inside the reserved number of sequences; the count is the sequential restatement's"""
+    import packed_cases
+    import stream_cases
+    D = rv.SMALL[0]
+    lens = rv.seq_shapes(D, long_len=300)["one_long"]
+    assert len(lens) == D
+    ids, off = packed_cases.ragged(lens)
+    counts = []
+    for L in rv.STREAM_ROW_LENS:
+        R = stream_cases.restate(ids, off, L, stream_cases.BOS, stream_cases.EOS)[8]
+        assert R == rv.stream_row_count(lens, L) == stream_cases.restate_np(ids, off, L, stream_cases.BOS, stream_cases.EOS)[8]
+        counts.append(R)
+    assert max(counts) > 3 * D, counts
+    for name, lens in rv.seq_shapes(D, long_len=300).items():
+        assert len(lens) <= D, name
