@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -112,11 +113,13 @@ struct PinBuf {
 // kernel of a step.  Kernels get the members' addresses, BfLastStatus / BfLexStats copy from them: the offsets are fixed.  Who clears what:
 //   per launch   [0, 64)     on the stream, by begin_launch() in EVERY batch call that takes a handle of the caller's, whether its kernels use one of these
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
-//                            calls on one handle): run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsDenoiseBatchDevice, run_packed_device, run_i2t_host and
-//                            IdsToTextBatchDevice.  The fill passes of the two-pass calls keep the size pass's words.  NormalizeSpacesBatch and
-//                            TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for its status, and their
-//                            kernels use none of the words: they clear nothing.
+//                            calls on one handle).  Nobody keeps a list of entry points here: begin_launch() is called by the drivers they all go
+//                            through -- run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
+//                            run_row_stage_device, run_packed_device, run_stream_device, run_i2t_host and IdsToTextBatchDevice -- and by rows_call(), the
+//                            prologue of every Rows...BatchDevice entry point (span cells, MLM mask, MLM predictions, denoise).  The host forms reach
+//                            it through the Device drivers they call.  The fill passes of the two-pass calls keep the size pass's words.
+//                            NormalizeSpacesBatch and TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for
+//                            its status, and their kernels use none of the words: they clear nothing.
 //                            w2t_copy_long_n once more by run_words_device in front of its copy pass
 //   statistics   [64, 192)   BfSetLexStats alone: the counters add up over launches
 //   flat program [192, 224)  enqueue_flat(), on the stream, behind begin_launch(): no other program reads or writes them
@@ -382,6 +385,18 @@ bool begin_launch(Handle *h, hipStream_t s)
     if (!clear_launch_words(h, s)) return false;
     h->small_status = -1;
     return true;
+}
+
+// What a Rows...BatchDevice entry point does behind its argument checks (a refused argument touches neither the device nor the status word): the
+// handle's lock, its device, begin_launch, launch(s) unless the call has no row to work on, and the launch's error.
+template <class F> int rows_call(Handle *h, void *stream, int64_t rows_cap, const char *what, F &&launch)
+{
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    if (rows_cap > 0) launch(s);
+    return hip_ok(hipGetLastError(), what) ? 0 : BF_E_DEVICE;
 }
 
 // the exclusive scan of w_counts[0 .. n) into d_off[0 .. n] (every call's step between counting and writing)
@@ -1404,6 +1419,22 @@ static bool plane_args_ok(const PlaneArgs &a, bool need_a, int64_t ids_len)
     return true;
 }
 
+// PlaneArgs as the plane kernels take them: per plane the source of each side (src_b: NULL where the parameters have one side), the fill and the
+// output, the entries past nplanes empty.  true = the caller takes a plane.
+static bool plane_params(const PlaneArgs &a, int *nplanes, const int32_t **src_a, const int32_t **src_b, int32_t *fill, int32_t **out)
+{
+    bool any = false;
+    *nplanes = a.nplanes;
+    for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
+        const bool in = k < a.nplanes;
+        src_a[k] = in && a.src_a ? a.src_a[k] : nullptr;
+        if (src_b) src_b[k] = in && a.src_b ? a.src_b[k] : nullptr;
+        fill[k] = in ? a.fill[k] : 0; out[k] = in ? a.out[k] : nullptr;
+        any = any || out[k];
+    }
+    return any;
+}
+
 // The row stage with companion planes: run_row_stage_device as the base call runs it (the map also where only planes are taken: it reports the
 // rows dropped and leaves a row's item and first id for the lanes), then k_rowstage_planes over the planes the caller takes.
 template <class S>
@@ -1411,14 +1442,7 @@ int run_row_planes_device(Handle *h, const S &src, int64_t nseq, void *const out
                           const char *what)
 {
     RowPlanesParams<S> pp;
-    bool any = false;
-    pp.nplanes = a.nplanes;
-    for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
-        const bool in = k < a.nplanes;
-        pp.src[CELL_SIDE_A][k] = in && a.src_a ? a.src_a[k] : nullptr; pp.src[CELL_SIDE_B][k] = in && a.src_b ? a.src_b[k] : nullptr;
-        pp.fill[k] = in ? a.fill[k] : 0; pp.out[k] = in ? a.out[k] : nullptr;
-        any = any || pp.out[k];
-    }
+    const bool any = plane_params(a, &pp.nplanes, pp.src[CELL_SIDE_A], pp.src[CELL_SIDE_B], pp.fill, pp.out);
     const int rc = run_row_stage_device(h, src, nseq, out, rows_cap, d_row_off, s, what, &pp.st, any);
     if (rc != 0 || !any || nseq == 0 || rows_cap == 0) return rc;
     launch_rowstage_planes(pp, s);
@@ -1435,10 +1459,13 @@ static int64_t host_side_len(const int64_t *off, int64_t nseq)
     return len;
 }
 
-// one optional output of the host form: the caller's array, the staging buffer it is filled in, its bytes per row (slots as run_row_stage_device's,
-// then the companion planes of the ...Planes calls; the base calls leave those empty)
-struct RowOut { void *host; DevBuf *dev; size_t row_bytes; const char *what; };
+// one optional output of a host form that counts its rows first: the caller's array, the staging buffer it is filled in, its bytes per row, the label
+// of its copy's error text, and the rows it holds beyond the row total (slots as run_row_stage_device's, then the companion planes of the ...Planes
+// calls; the base calls leave those empty)
+struct RowOut { void *host; DevBuf *dev; size_t row_bytes; const char *what; int more_rows = 0; };
 constexpr int ROW_HOST_OUTS = ROW_OUTS + ROWS_MAX_PLANES;
+// what the size pass has answered in a workspace and the caller takes as it is
+struct SizeAnswer { void *host; const DevBuf *dev; size_t bytes; const char *what; };
 
 // the planes of a host call in the output table, and the device arrays a pass gathers them into
 static void plane_outs(Handle *h, const PlaneArgs &a, size_t L, RowOut *outs)
@@ -1462,35 +1489,49 @@ static int stage_planes(Handle *h, const int32_t *const *src, int nplanes, int s
     return 0;
 }
 
-// Behind the staging of the host forms (the caller holds h->defer_mu, then h->mu -- w_ids, w_starts and w_ends may hold a sharded range's ids
-// that wait for their copy out -- and has reserved w_idoff): size pass, offsets to the caller, capacity check, fill pass, outputs to the caller.
-//   pass(d_out, cap)  run_row_stage_device over the staged source, with the row offsets in w_idoff
-// Returns the row total, or BF_E_CAPACITY with the offsets complete and nothing else written.  As in two_pass_host, whatever ends the call
-// early after work was queued synchronises the stream first.
-int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&outs)[ROW_HOST_OUTS], int64_t rows_cap, int64_t *row_off_out,
-                       const std::function<int(void *const d_out[ROW_HOST_OUTS], int64_t cap)> &pass)
+// Behind the staging (stage_ragged, stage_planes) of the host forms that count their rows first: rows and pair rows, packed rows, stream rows.  The
+// caller holds h->defer_mu, then h->mu -- w_ids, w_starts and w_ends may hold a sharded range's ids that wait for their copy out -- and has
+// reserved the workspaces of the answers.  Size pass, answers to the caller, capacity check, fill pass, outputs to the caller.
+//   pass(d_out, cap)  the Device form over the staged source: d_out[i] = the staging of outs[i], NULL in the size pass and where the caller takes none
+//   answers           copied behind the size pass: complete when BF_E_CAPACITY is answered, and nothing else is written then
+//   total_at          where the row total R stands once the answers have arrived
+//   fill_empty        R = 0 still makes the fill pass (an output with rows beyond R has something to copy)
+// Returns R -- whatever rows_cap is where the caller takes no output: a size query needs no capacity -- or BF_E_*.  As in two_pass_host, whatever
+// ends the call early after work was queued synchronises the stream first.
+int64_t count_fill_host(hipStream_t s, std::initializer_list<SizeAnswer> answers, const int64_t *total_at, const RowOut (&outs)[ROW_HOST_OUTS], int64_t rows_cap,
+                        bool fill_empty, const std::function<int(void *const d_out[ROW_HOST_OUTS], int64_t cap)> &pass)
 {
     auto fail = [s](int64_t rc) { (void)hipStreamSynchronize(s); return rc; };
     void *d_out[ROW_HOST_OUTS] = {};
     int rc = pass(d_out, 0);
     if (rc != 0) return fail(rc);
-    if (!hip_ok(hipMemcpyAsync(row_off_out, h->w_idoff.p, (size_t)(nseq + 1) * 8, hipMemcpyDeviceToHost, s), "D2H offsets")) return fail(BF_E_DEVICE);
+    for (const SizeAnswer &a : answers)
+        if (a.host && a.bytes && !hip_ok(hipMemcpyAsync(a.host, a.dev->p, a.bytes, hipMemcpyDeviceToHost, s), a.what)) return fail(BF_E_DEVICE);
     if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    const int64_t total = row_off_out[nseq];
+    const int64_t R = *total_at;
     bool any = false;
     for (const RowOut &o : outs) any = any || o.host;
-    if (total == 0 || !any) return total;                                     // (a size query needs no capacity)
-    if (total > rows_cap) return BF_E_CAPACITY;
+    if (!any || (R == 0 && !fill_empty)) return R;
+    if (R > rows_cap) return BF_E_CAPACITY;
+    auto bytes = [R](const RowOut &o) { return (size_t)(R + o.more_rows) * o.row_bytes; };
     for (int i = 0; i < ROW_HOST_OUTS; ++i) {
         if (!outs[i].host) continue;
-        if (!outs[i].dev->reserve((size_t)total * outs[i].row_bytes + 16)) return BF_E_DEVICE;
+        if (!outs[i].dev->reserve(bytes(outs[i]) + 16)) return BF_E_DEVICE;
         d_out[i] = outs[i].dev->p;
     }
-    rc = pass(d_out, total);
+    rc = pass(d_out, R);
     if (rc != 0) return fail(rc);
     for (const RowOut &o : outs)
-        if (o.host && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, (size_t)total * o.row_bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
-    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? total : BF_E_DEVICE;
+        if (o.host && bytes(o) && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, bytes(o), hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
+}
+
+// the row stage behind its staging: the answer is the row offsets (w_idoff, reserved by the caller), their last entry the total
+//   pass(d_out, cap)  run_row_stage_device over the staged source, with the row offsets in w_idoff
+static int64_t row_stage_host(Handle *h, hipStream_t s, int64_t nseq, const RowOut (&outs)[ROW_HOST_OUTS], int64_t rows_cap, int64_t *row_off_out,
+                              const std::function<int(void *const d_out[ROW_HOST_OUTS], int64_t cap)> &pass)
+{
+    return count_fill_host(s, {{row_off_out, &h->w_idoff, (size_t)(nseq + 1) * 8, "D2H offsets"}}, &row_off_out[nseq], outs, rows_cap, false, pass);
 }
 
 // IdsToRowsBatch on host buffers: the ids through stage_ragged, then row_stage_host
@@ -1592,21 +1633,14 @@ int run_packed_device(Handle *h, const PackedSpec &spec, const int32_t *d_ids, i
     // the companion planes the caller takes (IdsToPackedRowsPlanesBatch; none = the base call, with the launches of the base call).  Also with
     // rows_cap = 0: the kernel reports the rows dropped from a plane, which k_packed_rows does for the base outputs alone
     PackedPlanesParams pp;
-    bool any = false;
-    pp.nplanes = planes.nplanes;
-    for (int k = 0; k < ROWS_MAX_PLANES; ++k) {
-        const bool in = k < planes.nplanes;
-        pp.src[k] = in && planes.src_a ? planes.src_a[k] : nullptr; pp.fill[k] = in ? planes.fill[k] : 0; pp.out[k] = in ? planes.out[k] : nullptr;
-        any = any || pp.out[k];
-    }
+    const bool any = plane_params(planes, &pp.nplanes, pp.src, nullptr, pp.fill, pp.out);
     if (nseq > 0 && any) { pp.pk = p; launch_packed_planes(pp, s); }
     (void)hipEventRecord(h->ev[EV_COMPACT], s);
     h->ev_valid = true;
     return hip_ok(hipGetLastError(), "IdsToPackedRows kernels") ? 0 : BF_E_DEVICE;
 }
 
-// IdsToPackedRowsBatch on host buffers: the ids through stage_ragged, a size pass that also answers the per-sequence outputs, the capacity check,
-// the fill pass.  As in two_pass_host, whatever ends the call early after work was queued synchronises the stream first.
+// IdsToPackedRowsBatch on host buffers: the ids through stage_ragged, then count_fill_host, whose size pass also answers the per-sequence outputs
 int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const PackedSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
                         int32_t *row_first_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out, const PlaneArgs &planes = PlaneArgs{})
 {
@@ -1622,48 +1656,19 @@ int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
     Staged st;
     int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
     if (rc != 0) return rc;
-    auto fail = [s](int64_t e) { (void)hipStreamSynchronize(s); return e; };
     const int32_t *d_src[ROWS_MAX_PLANES] = {};
     rc = stage_planes(h, planes.src_a, planes.nplanes, 0, id_off, nseq, ids_len, h->w_docoff, s, d_src);
-    if (rc != 0) return fail(rc);                                              // (the ids' copies are queued)
-    int32_t *d_plane[ROWS_MAX_PLANES] = {};                                    // the size pass takes no plane
-    auto pass = [&](int32_t *d_rows, int32_t *d_seg, int32_t *d_pos, int32_t *d_first, int64_t cap) {
-        return run_packed_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, d_rows, d_seg, d_pos, d_first, cap,
-                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s,
-                                 PlaneArgs{planes.nplanes, d_src, nullptr, planes.fill, d_plane});
-    };
-    rc = pass(nullptr, nullptr, nullptr, nullptr, 0);
-    if (rc != 0) return fail(rc);
-    bool any_plane = false;
-    for (int k = 0; k < planes.nplanes; ++k) any_plane = any_plane || planes.out[k];
+    if (rc != 0) { (void)hipStreamSynchronize(s); return rc; }                  // (the ids' copies are queued)
+    const size_t L = (size_t)spec.row_len;
+    RowOut outs[ROW_HOST_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {seg_out, &h->w_vals, L * 4, "D2H segments"}, {pos_out, &h->w_text, L * 4, "D2H positions"},
+                                  {row_first_out, &h->w_outoff, 4, "D2H row starts", 1}};           // (R + 1 entries: also of no rows)
+    for (int k = 0; k < planes.nplanes; ++k) outs[4 + k] = RowOut{planes.out[k], &h->w_plout[k], L * 4, "D2H plane"};
     int64_t R = 0;
-    if (!hip_ok(hipMemcpyAsync(&R, h->w_idoff.p, 8, hipMemcpyDeviceToHost, s), "D2H row count") ||
-        (seq_row_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_row_out, h->w_starts.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence rows")) ||
-        (seq_col_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_col_out, h->w_ends.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence cells"))) return fail(BF_E_DEVICE);
-    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    if (!rows_out && !seg_out && !pos_out && !row_first_out && !any_plane) return R;         // (a size query needs no capacity)
-    if (R > rows_cap) return BF_E_CAPACITY;
-    const size_t plane_bytes = (size_t)R * (size_t)spec.row_len * 4, first_bytes = (size_t)(R + 1) * 4;
-    struct { int32_t *host; DevBuf *dev; size_t bytes; const char *what; } outs[4] = {{rows_out, &h->w_out, plane_bytes, "D2H rows"}, {seg_out, &h->w_vals, plane_bytes, "D2H segments"},
-                                                                                     {pos_out, &h->w_text, plane_bytes, "D2H positions"}, {row_first_out, &h->w_outoff, first_bytes, "D2H row starts"}};
-    int32_t *d_out[4] = {};
-    for (int i = 0; i < 4; ++i) {
-        if (!outs[i].host) continue;
-        if (!outs[i].dev->reserve(outs[i].bytes + 16)) return BF_E_DEVICE;
-        d_out[i] = outs[i].dev->as<int32_t>();
-    }
-    for (int k = 0; k < planes.nplanes; ++k) {
-        if (!planes.out[k]) continue;
-        if (!h->w_plout[k].reserve(plane_bytes + 16)) return BF_E_DEVICE;
-        d_plane[k] = h->w_plout[k].as<int32_t>();
-    }
-    rc = pass(d_out[0], d_out[1], d_out[2], d_out[3], R);
-    if (rc != 0) return fail(rc);
-    for (const auto &o : outs)
-        if (o.host && o.bytes && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, o.bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
-    for (int k = 0; k < planes.nplanes; ++k)
-        if (d_plane[k] && plane_bytes && !hip_ok(hipMemcpyAsync(planes.out[k], d_plane[k], plane_bytes, hipMemcpyDeviceToHost, s), "D2H plane")) return fail(BF_E_DEVICE);
-    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
+    return count_fill_host(s, {{&R, &h->w_idoff, 8, "D2H row count"}, {seq_row_out, &h->w_starts, seq_bytes, "D2H sequence rows"}, {seq_col_out, &h->w_ends, seq_bytes, "D2H sequence cells"}},
+                           &R, outs, rows_cap, true, [&](void *const d[ROW_HOST_OUTS], int64_t cap) {
+        return run_packed_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, (int32_t *)d[0], (int32_t *)d[1], (int32_t *)d[2], (int32_t *)d[3], cap,
+                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s,
+                                 PlaneArgs{planes.nplanes, d_src, nullptr, planes.fill, (int32_t *const *)(d + 4)}); });
 }
 
 // IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
@@ -1699,8 +1704,7 @@ int run_stream_device(Handle *h, const StreamSpec &spec, const int32_t *d_ids, i
     return hip_ok(hipGetLastError(), "IdsToStreamRows kernels") ? 0 : BF_E_DEVICE;
 }
 
-// IdsToStreamRowsBatch on host buffers: the ids through stage_ragged, a size pass that also answers the per-sequence outputs, the capacity check,
-// the fill pass (run_packed_host's shape).  Whatever ends the call early after work was queued synchronises the stream first.
+// IdsToStreamRowsBatch on host buffers: the ids through stage_ragged, then count_fill_host, whose size pass also answers the per-sequence outputs
 int64_t run_stream_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const StreamSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
                         int32_t *labels_out, int32_t *first_seq_out, int32_t *first_pos_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
 {
@@ -1716,36 +1720,16 @@ int64_t run_stream_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
     Staged st;
     int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
     if (rc != 0) return rc;
-    auto fail = [s](int64_t e) { (void)hipStreamSynchronize(s); return e; };
-    auto pass = [&](int32_t *const d[6], int64_t cap) {
-        return run_stream_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, d[0], d[1], d[2], d[3], d[4], d[5], cap,
-                                 seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr, h->w_idoff.as<int64_t>(), s);
-    };
-    int32_t *d_out[6] = {};
-    rc = pass(d_out, 0);
-    if (rc != 0) return fail(rc);
+    const size_t L = (size_t)spec.row_len;
+    const RowOut outs[ROW_HOST_OUTS] = {{rows_out, &h->w_out, L * 4, "D2H rows"}, {seg_out, &h->w_vals, L * 4, "D2H segments"}, {pos_out, &h->w_text, L * 4, "D2H positions"},
+                                        {labels_out, &h->w_plout[0], L * 4, "D2H labels"}, {first_seq_out, &h->w_outoff, 4, "D2H row sequences"},
+                                        {first_pos_out, &h->w_plout[1], 4, "D2H row positions"}};
     int64_t R = 0;
-    if (!hip_ok(hipMemcpyAsync(&R, h->w_idoff.p, 8, hipMemcpyDeviceToHost, s), "D2H row count") ||
-        (seq_row_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_row_out, h->w_starts.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence rows")) ||
-        (seq_col_out && seq_bytes && !hip_ok(hipMemcpyAsync(seq_col_out, h->w_ends.p, seq_bytes, hipMemcpyDeviceToHost, s), "D2H sequence cells"))) return fail(BF_E_DEVICE);
-    if (!hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize")) return BF_E_DEVICE;
-    if (!rows_out && !seg_out && !pos_out && !labels_out && !first_seq_out && !first_pos_out) return R;      // (a size query needs no capacity)
-    if (R > rows_cap) return BF_E_CAPACITY;
-    if (R == 0) return 0;
-    const size_t plane_bytes = (size_t)R * (size_t)spec.row_len * 4, first_bytes = (size_t)R * 4;
-    struct { int32_t *host; DevBuf *dev; size_t bytes; const char *what; } outs[6] = {
-        {rows_out, &h->w_out, plane_bytes, "D2H rows"}, {seg_out, &h->w_vals, plane_bytes, "D2H segments"}, {pos_out, &h->w_text, plane_bytes, "D2H positions"},
-        {labels_out, &h->w_plout[0], plane_bytes, "D2H labels"}, {first_seq_out, &h->w_outoff, first_bytes, "D2H row sequences"}, {first_pos_out, &h->w_plout[1], first_bytes, "D2H row positions"}};
-    for (int i = 0; i < 6; ++i) {
-        if (!outs[i].host) continue;
-        if (!outs[i].dev->reserve(outs[i].bytes + 16)) return BF_E_DEVICE;
-        d_out[i] = outs[i].dev->as<int32_t>();
-    }
-    rc = pass(d_out, R);
-    if (rc != 0) return fail(rc);
-    for (const auto &o : outs)
-        if (o.host && !hip_ok(hipMemcpyAsync(o.host, o.dev->p, o.bytes, hipMemcpyDeviceToHost, s), o.what)) return fail(BF_E_DEVICE);
-    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? R : BF_E_DEVICE;
+    return count_fill_host(s, {{&R, &h->w_idoff, 8, "D2H row count"}, {seq_row_out, &h->w_starts, seq_bytes, "D2H sequence rows"}, {seq_col_out, &h->w_ends, seq_bytes, "D2H sequence cells"}},
+                           &R, outs, rows_cap, false, [&](void *const d[ROW_HOST_OUTS], int64_t cap) {
+        return run_stream_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, (int32_t *)d[0], (int32_t *)d[1], (int32_t *)d[2], (int32_t *)d[3],
+                                 (int32_t *)d[4], (int32_t *)d[5], cap, seq_row_out ? h->w_starts.as<int32_t>() : nullptr, seq_col_out ? h->w_ends.as<int32_t>() : nullptr,
+                                 h->w_idoff.as<int64_t>(), s); });
 }
 
 // key -> info lookup: tables of the [pos-dict] in their lookup form, uploaded when the first call arrives
@@ -2482,14 +2466,10 @@ int RowsSpanCellsBatchDevice(void *p, const int32_t *d_start_plane, const int32_
     Handle *h = as_handle(p);
     if (!h || row_len < 1 || row_len > ROWS_MAX_LEN || rows_cap < 0 || nseq < 0) return BF_E_ARG;
     if (rows_cap > 0 && (!d_start_plane || !d_end_plane || !d_span_first || !d_span_last || !d_start_cell_out || !d_end_cell_out)) return BF_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    if (!begin_launch(h, s)) return BF_E_DEVICE;
-    if (rows_cap > 0)
+    return rows_call(h, stream, rows_cap, "RowsSpanCells kernel", [&](hipStream_t s) {
         launch_rows_span(RowsSpanParams{d_start_plane, d_end_plane, row_len, rows_cap, d_nrows, d_row_seq, nseq, d_span_first, d_span_last, none_cell,
                                         d_start_cell_out, d_end_cell_out, &h->misc()->status}, s);
-    return hip_ok(hipGetLastError(), "RowsSpanCells kernel") ? 0 : BF_E_DEVICE;
+    });
 }
 
 /* ---- additive: masked-language-model masking of rows that are on the device (bf_mlm.h, k_rows_mlm): masked ids and labels, token by token or whole words */
@@ -2503,13 +2483,9 @@ int RowsMlmMaskBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t 
     if (!h || row_len < 1 || row_len > MLM_MAX_LEN || rows_cap < 0 || (d_start_plane != nullptr) != (d_end_plane != nullptr)) return BF_E_ARG;
     if (!mlm_spec(nspecial, special_ids, select_prob, mask_prob, random_prob, mask_id, rand_lo, rand_hi, ignore_label, seed, epoch, &spec)) return BF_E_ARG;
     if (rows_cap > 0 && (!d_rows || (!d_ids_out && !d_labels_out))) return BF_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    if (!begin_launch(h, s)) return BF_E_DEVICE;
-    if (rows_cap > 0)
+    return rows_call(h, stream, rows_cap, "RowsMlmMask kernel", [&](hipStream_t s) {
         launch_rows_mlm(RowsMlmParams{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, d_start_plane, d_end_plane, spec, d_ids_out, d_labels_out}, s);
-    return hip_ok(hipGetLastError(), "RowsMlmMask kernel") ? 0 : BF_E_DEVICE;
+    });
 }
 
 /* ---- additive: the same masking with a cap on the predictions of a row and the kept cells gathered (bf_mlm.h, k_rows_mlm_cap); max_pred = 0 is the base call */
@@ -2525,16 +2501,11 @@ int RowsMlmPredictionsBatchDevice(void *p, const int32_t *d_rows, int row_len, i
     if (max_pred < 0 || max_pred > MLM_CAP_MAX_PRED || (max_pred > 0 && row_len > MLM_CAP_MAX_LEN) || (max_pred == 0 && gathered)) return BF_E_ARG;
     if (!mlm_spec(nspecial, special_ids, select_prob, mask_prob, random_prob, mask_id, rand_lo, rand_hi, ignore_label, seed, epoch, &spec)) return BF_E_ARG;
     if (rows_cap > 0 && (!d_rows || (!d_ids_out && !d_labels_out && !gathered))) return BF_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    if (!begin_launch(h, s)) return BF_E_DEVICE;
-    if (rows_cap > 0) {
+    return rows_call(h, stream, rows_cap, "RowsMlmPredictions kernel", [&](hipStream_t s) {
         const RowsMlmParams m{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, d_start_plane, d_end_plane, spec, d_ids_out, d_labels_out};
         if (max_pred == 0) launch_rows_mlm(m, s);
         else launch_rows_mlm_cap(RowsMlmCapParams{m, max_pred, d_pred_cell_out, d_pred_label_out, d_pred_count_out}, s);
-    }
-    return hip_ok(hipGetLastError(), "RowsMlmPredictions kernel") ? 0 : BF_E_DEVICE;
+    });
 }
 
 /* ---- additive: span corruption of rows that are on the device (bf_denoise.h, k_rows_denoise): the encoder row and the decoder row, compacted in one walk */
@@ -2553,15 +2524,11 @@ int RowsDenoiseBatchDevice(void *p, const int32_t *d_rows, int row_len, int64_t 
     if (!denoise_spec(nspecial, special_ids, start_prob, len_lo, len_hi, sentinel_first, sentinel_step, max_sentinels, eos_id, pad_id, ignore_label, seed, epoch, &spec))
         return BF_E_ARG;
     if (rows_cap > 0 && (!d_rows || !any_out)) return BF_E_ARG;
-    std::lock_guard<std::mutex> lock(h->mu);
-    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    if (!begin_launch(h, s)) return BF_E_DEVICE;
-    if (rows_cap > 0)
+    return rows_call(h, stream, rows_cap, "RowsDenoise kernel", [&](hipStream_t s) {
         launch_rows_denoise(RowsDenoiseParams{d_rows, row_len, rows_cap, d_nrows, d_mask, d_seg, spec, want_enc ? enc_len : 0, d_enc_out, d_enc_cell_out,
                                               want_dec ? dec_len : 0, d_dec_out, d_dec_cell_out, d_enc_count_out, d_dec_count_out, d_span_count_out,
                                               &h->misc()->status}, s);
-    return hip_ok(hipGetLastError(), "RowsDenoise kernel") ? 0 : BF_E_DEVICE;
+    });
 }
 
 /* ---- additive: packed rows (bf_packed.h): several sequences per row, greedy and in order, with a segment plane and a position plane */

@@ -2,10 +2,8 @@
 // the reach, the segmented scan, the run index and its cap, the running counts, the two positions; include/blingfiretokdll_amd.h
 // RowsDenoiseBatchDevice is the specification).
 //
-//  k_rows_denoise<G>  the partition of k_rows_mlm: G = span_group(row_len) lanes share a row (a wave, or a power-of-two slice of one for rows of at
-//                     most 32 cells: 64 / G rows per wave), every wave makes the same number of rounds (a row past the end is a group that loads
-//                     and stores nothing) and, inside a round, the same number of chunks: no cross-lane operation is divergent.  A row is walked
-//                     ONCE, in chunks of G cells in order, lane l takes cell j0 + l.  Per chunk:
+//  k_rows_denoise<G>  bf_rowwalk.h's partition (G lanes share a row, every wave the same rounds and, inside a round, the same chunks: no cross-lane
+//                     operation is divergent).  A row is walked ONCE, in chunks of G cells in order, lane l takes cell j0 + l.  Per chunk:
 //     loads           the cell's id, mask byte and segment (coalesced); one Philox evaluation where the cell is eligible -> its reach.
 //     scan            the segmented inclusive max-scan of (ineligible, reach) in log2 G steps of one shuffle (the pair travels as one word), closed
 //                     with the carried reach.
@@ -19,23 +17,19 @@
 // One pass, no LDS, no scratch.  An output position at or past enc_len / dec_len is not stored; positions are never negative, and rows at or
 // past min(rows_cap, *nrows) are not touched: every store lies inside [0, rows_cap * len) of its plane.  The outputs must not overlap the inputs:
 // the compacted rows are written in front of cells that lanes of a later chunk still read.
-#include "bf_kernels_common.h"
+#include "bf_rowwalk.h"
 
 namespace bfa {
 
 template <int G>
 __global__ __launch_bounds__(256) void k_rows_denoise(RowsDenoiseParams p)
 {
-    int64_t nrows = p.nrows ? *p.nrows : p.rows_cap;
-    if (nrows > p.rows_cap) nrows = p.rows_cap;
-    const int lane = threadIdx.x & (G - 1);
-    const int shift = (int)(threadIdx.x & 63u) & ~(G - 1);                              // the group's first lane in the wave
-    const uint64_t group = (G == 64 ? ~(uint64_t)0 : (((uint64_t)1 << G) - 1)) << shift;   // the group's lanes of a ballot
+    const int64_t nrows = rows_bound(p.nrows, p.rows_cap);
+    const int lane = group_lane<G>();
+    const GroupBallot group_ballot = group_ballots<G>();
     const bool want_enc = p.enc || p.enc_cell, want_dec = p.dec || p.dec_cell;
-    const int64_t per_grid = (int64_t)gridDim.x * (256 / G);                       // rows per round of the grid
-    const int64_t wave_row = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63)) / G; // the first row of this wave's round
-    for (int64_t r0 = wave_row; r0 < nrows; r0 += per_grid) {
-        const int64_t r = r0 + (threadIdx.x & 63) / G;
+    for (int64_t step = rows_per_round<G>(256), r0 = wave_first_row<G>(256); r0 < nrows; r0 += step) {
+        const int64_t r = group_row<G>(r0);
         const bool live = r < nrows;
         const int64_t base = r * p.row_len, ebase = r * (int64_t)p.enc_len, dbase = r * (int64_t)p.dec_len;
         DenoiseCarry carry = denoise_carry_none();
@@ -62,12 +56,12 @@ __global__ __launch_bounds__(256) void k_rows_denoise(RowsDenoiseParams p)
             int noise0_prev = __shfl_up(noise0, 1, G);
             if (lane == 0) noise0_prev = carry.noise0;
             const bool begin0 = denoise_begin0(noise0 != 0, noise0_prev != 0);
-            const uint64_t begin0_lanes = (__ballot(begin0) & group) >> shift;
+            const uint64_t begin0_lanes = group_ballot(begin0);
             const int run = denoise_run_index(carry, begin0_lanes, lane);
             const bool noise = denoise_noise(p.spec, noise0 != 0, run);
             const bool keep = present && !noise;
-            const uint64_t noise_lanes = (__ballot(noise) & group) >> shift;
-            const uint64_t keep_lanes = (__ballot(keep) & group) >> shift;
+            const uint64_t noise_lanes = group_ballot(noise);
+            const uint64_t keep_lanes = group_ballot(keep);
             const uint64_t begin_lanes = begin0_lanes & noise_lanes;
             const DenoiseSlots n = denoise_slots(carry, keep_lanes, noise_lanes, begin_lanes, lane);
             const bool begin = begin0 && noise;
@@ -120,24 +114,9 @@ __global__ __launch_bounds__(256) void k_rows_denoise(RowsDenoiseParams p)
     }
 }
 
-template <int G>
-static void launch_rows_denoise_g(const RowsDenoiseParams &p, hipStream_t s)
-{
-    const int64_t rows = p.rows_cap < ((int64_t)1 << 40) ? p.rows_cap : ((int64_t)1 << 40);      // (the row count is on the device: the capacity bounds it)
-    hipLaunchKernelGGL((k_rows_denoise<G>), dim3(rows_blocks(rows * G)), dim3(256), 0, s, p);
-}
-
 void launch_rows_denoise(const RowsDenoiseParams &p, hipStream_t s)
 {
-    switch (span_group(p.row_len)) {
-    case 1: launch_rows_denoise_g<1>(p, s); break;
-    case 2: launch_rows_denoise_g<2>(p, s); break;
-    case 4: launch_rows_denoise_g<4>(p, s); break;
-    case 8: launch_rows_denoise_g<8>(p, s); break;
-    case 16: launch_rows_denoise_g<16>(p, s); break;
-    case 32: launch_rows_denoise_g<32>(p, s); break;
-    default: launch_rows_denoise_g<64>(p, s); break;
-    }
+    dispatch_span_group(p.row_len, [&](auto g) { hipLaunchKernelGGL((k_rows_denoise<g()>), dim3(rows_grid(p.rows_cap, g())), dim3(256), 0, s, p); });
 }
 
 } // namespace bfa

@@ -2,15 +2,11 @@
 // code: the generator, eligibility, units, the decision, the cap; include/blingfiretokdll_amd.h RowsMlmMaskBatchDevice and RowsMlmPredictionsBatchDevice
 // are the specification).
 //
-//  k_rows_mlm<G, WW>  the partition of k_rows_span: G = span_group(row_len) lanes share a row (a wave, or a power-of-two slice of one for rows of
-//                     at most 32 cells: 64 / G rows per wave), every wave makes the same number of rounds (a row past the end is a group that
-//                     loads and stores nothing) and, inside a round, the same number of chunks: no cross-lane operation is divergent.  A row is
-//                     walked in chunks of G cells in order, lane l takes cell j0 + l (coalesced dword loads and stores).
+//  k_rows_mlm<G, WW>  bf_rowwalk.h's partition (G lanes share a row, every wave the same rounds and, inside a round, the same chunks: no
+//                     cross-lane operation is divergent).  A row is walked in chunks of G cells in order, lane l takes cell j0 + l.
 //     WW = false      token masking: a cell is its own unit, nothing crosses lanes, one Philox evaluation per eligible cell.
-//     WW = true       whole words over a start plane and an end plane: the end and the "joins a unit" flag of cell j - 1 come one lane up (lane 0:
-//                     the carry of the chunk before), the head of a cell's unit is an inclusive max-scan of (continues ? -1 : j) in log2 G
-//                     steps, lanes still at -1 take the carried head, and the last lane's (end, joins, head) is the next chunk's carry.  At most
-//                     two Philox evaluations per cell, one where the cell is its unit's head.
+//     WW = true       whole words over a start plane and an end plane: the head of a cell's unit comes from bf_rowwalk.h mlm_chunk_head, one
+//                     scan per chunk with a carry between chunks.  At most two Philox evaluations per cell, one where the cell is its unit's head.
 // No LDS, no atomics, no scratch; the status word is not touched (the call has cleared it).  In place (ids_out == rows): a lane reads its own
 // cell of `rows` and nothing else of it before it writes that cell; what it needs of its neighbour comes from the planes.
 //
@@ -31,20 +27,17 @@
 //                     tail [n, P) and its lane 0 writes the count.
 // No atomics, no scratch, the status word is not touched; the cross-lane operations (shuffles, ballots, the vote) are never under divergent
 // control flow: the loop bounds depend on row_len and the wave's round alone.
-#include "bf_kernels_common.h"
+#include "bf_rowwalk.h"
 
 namespace bfa {
 
 template <int G, bool WW>
 __global__ __launch_bounds__(256) void k_rows_mlm(RowsMlmParams p)
 {
-    int64_t nrows = p.nrows ? *p.nrows : p.rows_cap;
-    if (nrows > p.rows_cap) nrows = p.rows_cap;
-    const int lane = threadIdx.x & (G - 1);
-    const int64_t per_grid = (int64_t)gridDim.x * (256 / G);                       // rows per round of the grid
-    const int64_t wave_row = ((int64_t)blockIdx.x * 256 + (threadIdx.x & ~63)) / G; // the first row of this wave's round
-    for (int64_t r0 = wave_row; r0 < nrows; r0 += per_grid) {
-        const int64_t r = r0 + (threadIdx.x & 63) / G;
+    const int64_t nrows = rows_bound(p.nrows, p.rows_cap);
+    const int lane = group_lane<G>();
+    for (int64_t step = rows_per_round<G>(256), r0 = wave_first_row<G>(256); r0 < nrows; r0 += step) {
+        const int64_t r = group_row<G>(r0);
         const bool live = r < nrows;
         const int64_t base = r * p.row_len;
         MlmCarry carry = mlm_carry_none();
@@ -60,17 +53,7 @@ __global__ __launch_bounds__(256) void k_rows_mlm(RowsMlmParams p)
                 if (WW) { S = p.start_plane[c]; E = p.end_plane[c]; }
             }
             int h = j;
-            if (WW) {
-                const int joins = mlm_joins(eligible, S) ? 1 : 0;
-                int32_t end_prev = __shfl_up(E, 1, G);
-                int joins_prev = __shfl_up(joins, 1, G);
-                if (lane == 0) { end_prev = carry.end; joins_prev = carry.joins; }
-                h = mlm_head_seed(mlm_continues(joins_prev != 0, end_prev, joins != 0, S), j);
-#pragma unroll
-                for (int d = 1; d < G; d <<= 1) h = mlm_head_step(h, __shfl_up(h, d, G), lane >= d);
-                h = mlm_head_close(h, carry.head);
-                carry = MlmCarry{__shfl(E, G - 1, G), __shfl(joins, G - 1, G), __shfl(h, G - 1, G)};
-            }
+            if (WW) { const MlmHead m = mlm_chunk_head<G>(eligible, S, E, j, lane, carry); h = m.h; carry = m.carry; }
             if (in) {
                 int32_t id_out, label;
                 mlm_decide(p.spec, r, j, h, id, eligible, &id_out, &label);
@@ -79,15 +62,6 @@ __global__ __launch_bounds__(256) void k_rows_mlm(RowsMlmParams p)
             }
         }
     }
-}
-
-template <int G>
-static void launch_rows_mlm_g(const RowsMlmParams &p, hipStream_t s)
-{
-    const int64_t rows = p.rows_cap < ((int64_t)1 << 40) ? p.rows_cap : ((int64_t)1 << 40);      // (the row count is on the device: the capacity bounds it)
-    const dim3 grid(rows_blocks(rows * G));
-    if (p.start_plane) hipLaunchKernelGGL((k_rows_mlm<G, true>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((k_rows_mlm<G, false>), grid, dim3(256), 0, s, p);
 }
 
 // the words of a row's cells: registers (C chunks) or the wave's slice of LDS (C = 0)
@@ -122,18 +96,14 @@ __global__ __launch_bounds__(256) void k_rows_mlm_cap(RowsMlmCapParams q)
 {
     extern __shared__ uint64_t cap_lds[];
     const RowsMlmParams &p = q.m;
-    int64_t nrows = p.nrows ? *p.nrows : p.rows_cap;
-    if (nrows > p.rows_cap) nrows = p.rows_cap;
-    const int lane = threadIdx.x & (G - 1);
-    const int shift = (int)(threadIdx.x & 63u) & ~(G - 1);                              // the group's first lane in the wave
-    const uint64_t group = (G == 64 ? ~(uint64_t)0 : (((uint64_t)1 << G) - 1)) << shift;   // the group's lanes of a ballot
+    const int64_t nrows = rows_bound(p.nrows, p.rows_cap);
+    const int lane = group_lane<G>();
+    const GroupBallot group_ballot = group_ballots<G>();
     const int nchunks = (p.row_len + G - 1) / G, P = q.max_pred;
     const int head_bits = mlm_cap_head_bits(p.row_len), rounds = mlm_cap_rounds(head_bits);
     CapWords<C> words(cap_lds, nchunks);
-    const int64_t per_grid = (int64_t)gridDim.x * (blockDim.x / G);
-    const int64_t wave_row = ((int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) / G;
-    for (int64_t r0 = wave_row; r0 < nrows; r0 += per_grid) {
-        const int64_t r = r0 + (threadIdx.x & 63) / G;
+    for (int64_t step = rows_per_round<G>(blockDim.x), r0 = wave_first_row<G>(blockDim.x); r0 < nrows; r0 += step) {   // (the launcher sizes the block of the LDS form)
+        const int64_t r = group_row<G>(r0);
         const bool live = r < nrows;
         const int64_t base = r * p.row_len;
         // ---- A: the word of every cell, the selected cells of the row
@@ -151,21 +121,11 @@ __global__ __launch_bounds__(256) void k_rows_mlm_cap(RowsMlmCapParams q)
                 if (WW) { S = p.start_plane[cell]; E = p.end_plane[cell]; }
             }
             int h = j;
-            if (WW) {
-                const int joins = mlm_joins(eligible, S) ? 1 : 0;
-                int32_t end_prev = __shfl_up(E, 1, G);
-                int joins_prev = __shfl_up(joins, 1, G);
-                if (lane == 0) { end_prev = carry.end; joins_prev = carry.joins; }
-                h = mlm_head_seed(mlm_continues(joins_prev != 0, end_prev, joins != 0, S), j);
-#pragma unroll
-                for (int d = 1; d < G; d <<= 1) h = mlm_head_step(h, __shfl_up(h, d, G), lane >= d);
-                h = mlm_head_close(h, carry.head);
-                carry = MlmCarry{__shfl(E, G - 1, G), __shfl(joins, G - 1, G), __shfl(h, G - 1, G)};
-            }
+            if (WW) { const MlmHead m = mlm_chunk_head<G>(eligible, S, E, j, lane, carry); h = m.h; carry = m.carry; }
             uint64_t word = MLM_CAP_NONE;
             if (eligible) word = mlm_cap_word(p.spec, true, mlm_draw(p.spec, r, h), h);
             words.put(c, word, id);
-            selected += mlm_popcount64(__ballot(word != MLM_CAP_NONE) & group);
+            selected += mlm_popcount64(group_ballot.in_place(word != MLM_CAP_NONE));
         });
         // ---- B: the threshold, where a row of this wave does not fit
         uint64_t T = 0;
@@ -174,7 +134,7 @@ __global__ __launch_bounds__(256) void k_rows_mlm_cap(RowsMlmCapParams q)
             for (int i = rounds - 1; i >= 0; --i) {
                 const uint64_t probe = mlm_cap_probe(T, i, head_bits);
                 int n = 0;
-                cap_chunks<C>(nchunks, [&](int c) { n += mlm_popcount64(__ballot(mlm_cap_below(words.get(c), probe)) & group); });
+                cap_chunks<C>(nchunks, [&](int c) { n += mlm_popcount64(group_ballot.in_place(mlm_cap_below(words.get(c), probe))); });
                 T = mlm_cap_take(T, probe, n, P);
                 settled = settled || n == P;                         // g(T) = P: no later bit changes who is kept
                 if (__all(settled)) break;
@@ -186,7 +146,7 @@ __global__ __launch_bounds__(256) void k_rows_mlm_cap(RowsMlmCapParams q)
             const int j = c * G + lane;
             const bool in = live && j < p.row_len;
             const bool kept = in && mlm_cap_kept(words.get(c), selected, P, T);
-            const uint64_t kept_lanes = (__ballot(kept) & group) >> shift;
+            const uint64_t kept_lanes = group_ballot(kept);
             if (in) {
                 const int64_t cell = base + j;
                 const int32_t id = words.id(c, p.rows + cell);
@@ -214,15 +174,14 @@ __global__ __launch_bounds__(256) void k_rows_mlm_cap(RowsMlmCapParams q)
 template <int G, int C>
 static void launch_rows_mlm_cap_g(const RowsMlmCapParams &q, hipStream_t s)
 {
-    const int64_t rows = q.m.rows_cap < ((int64_t)1 << 40) ? q.m.rows_cap : ((int64_t)1 << 40);
     unsigned block = 256, lds = 0;
-    dim3 grid(rows_blocks(rows * G));
+    dim3 grid(rows_grid(q.m.rows_cap, G));
     if (C == 0) {                                                                    // G = 64: a wave per row, its words in LDS, at most 32 KiB per block
         const unsigned per_wave = (unsigned)((q.m.row_len + 63) / 64) * 64u * 8u;
         unsigned waves = (32u << 10) / per_wave;
         waves = waves < 1 ? 1 : waves > 4 ? 4 : waves;
         block = waves * 64; lds = waves * per_wave;
-        int64_t blocks = (rows + waves - 1) / waves;
+        int64_t blocks = (rows_bounded(q.m.rows_cap) + waves - 1) / waves;
         const int64_t most = (int64_t)device_cus() * 8 * (4 / waves);
         grid = dim3((unsigned)(blocks > most ? most : blocks < 1 ? 1 : blocks));
     }
@@ -232,33 +191,23 @@ static void launch_rows_mlm_cap_g(const RowsMlmCapParams &q, hipStream_t s)
 
 void launch_rows_mlm_cap(const RowsMlmCapParams &q, hipStream_t s)
 {
-    switch (span_group(q.m.row_len)) {
-    case 1: launch_rows_mlm_cap_g<1, 1>(q, s); break;
-    case 2: launch_rows_mlm_cap_g<2, 1>(q, s); break;
-    case 4: launch_rows_mlm_cap_g<4, 1>(q, s); break;
-    case 8: launch_rows_mlm_cap_g<8, 1>(q, s); break;
-    case 16: launch_rows_mlm_cap_g<16, 1>(q, s); break;
-    case 32: launch_rows_mlm_cap_g<32, 1>(q, s); break;
-    default:
-        if (q.m.row_len <= 64) launch_rows_mlm_cap_g<64, 1>(q, s);
-        else if (q.m.row_len <= 128) launch_rows_mlm_cap_g<64, 2>(q, s);
-        else if (q.m.row_len <= 256) launch_rows_mlm_cap_g<64, 4>(q, s);
-        else launch_rows_mlm_cap_g<64, 0>(q, s);
-        break;
-    }
+    dispatch_span_group(q.m.row_len, [&](auto g) {
+        constexpr int G = g();
+        if constexpr (G < 64) launch_rows_mlm_cap_g<G, 1>(q, s);                      // (one chunk; a wave per row: its chunks decide where the words live)
+        else if (q.m.row_len <= 64) launch_rows_mlm_cap_g<G, 1>(q, s);
+        else if (q.m.row_len <= 128) launch_rows_mlm_cap_g<G, 2>(q, s);
+        else if (q.m.row_len <= 256) launch_rows_mlm_cap_g<G, 4>(q, s);
+        else launch_rows_mlm_cap_g<G, 0>(q, s);
+    });
 }
 
 void launch_rows_mlm(const RowsMlmParams &p, hipStream_t s)
 {
-    switch (span_group(p.row_len)) {
-    case 1: launch_rows_mlm_g<1>(p, s); break;
-    case 2: launch_rows_mlm_g<2>(p, s); break;
-    case 4: launch_rows_mlm_g<4>(p, s); break;
-    case 8: launch_rows_mlm_g<8>(p, s); break;
-    case 16: launch_rows_mlm_g<16>(p, s); break;
-    case 32: launch_rows_mlm_g<32>(p, s); break;
-    default: launch_rows_mlm_g<64>(p, s); break;
-    }
+    dispatch_span_group(p.row_len, [&](auto g) {
+        const dim3 grid(rows_grid(p.rows_cap, g()));
+        if (p.start_plane) hipLaunchKernelGGL((k_rows_mlm<g(), true>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((k_rows_mlm<g(), false>), grid, dim3(256), 0, s, p);
+    });
 }
 
 } // namespace bfa

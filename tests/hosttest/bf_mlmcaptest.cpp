@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../blingfire_amd/csrc/bf_rows.h"
 #include "../../blingfire_amd/csrc/bf_mlm.h"
+#include "rowwalk_emu.h"
 
 using namespace bfa;
 
@@ -74,35 +75,22 @@ int bft_mlmcap_rows(const int32_t *rows, int row_len, int64_t nrows, int64_t row
     std::vector<uint64_t> words((size_t)row_len);
     std::vector<uint8_t> kept((size_t)row_len);
     std::vector<int32_t> slot((size_t)row_len);
-    std::vector<int> hd((size_t)G), next((size_t)G), joins((size_t)G);
-    std::vector<uint8_t> el((size_t)G);
+    std::vector<EmuHeadCell> cell((size_t)G);
+    std::vector<int> hd((size_t)G);
     for (int64_t r = 0; r < nrows; ++r) {
         const int64_t base = r * row_len;
         MlmCarry carry = mlm_carry_none();
         for (int j0 = 0; j0 < row_len; j0 += G) {             // A
             for (int l = 0; l < G; ++l) {
                 const int j = j0 + l;
-                el[(size_t)l] = j < row_len && mlm_eligible(sp, rows[base + j], mask ? mask[base + j] : (uint8_t)1, seg ? seg[base + j] : 1);
+                const bool in = j < row_len;
+                cell[(size_t)l] = EmuHeadCell{in && ww ? S[base + j] : -1, in && ww ? E[base + j] : 0,
+                                              in && mlm_eligible(sp, rows[base + j], mask ? mask[base + j] : (uint8_t)1, seg ? seg[base + j] : 1)};
                 hd[(size_t)l] = j;
             }
-            if (ww) {
-                auto Sx = [&](int l) { return j0 + l < row_len ? S[base + j0 + l] : -1; };
-                auto Ex = [&](int l) { return j0 + l < row_len ? E[base + j0 + l] : 0; };
-                for (int l = 0; l < G; ++l) joins[(size_t)l] = mlm_joins(el[(size_t)l] != 0, Sx(l)) ? 1 : 0;
-                for (int l = 0; l < G; ++l) {
-                    const int32_t end_prev = l ? Ex(l - 1) : carry.end;
-                    const int joins_prev = l ? joins[(size_t)l - 1] : carry.joins;
-                    hd[(size_t)l] = mlm_head_seed(mlm_continues(joins_prev != 0, end_prev, joins[(size_t)l] != 0, Sx(l)), j0 + l);
-                }
-                for (int d = 1; d < G; d <<= 1) {
-                    for (int l = 0; l < G; ++l) next[(size_t)l] = mlm_head_step(hd[(size_t)l], hd[(size_t)(l >= d ? l - d : l)], l >= d);
-                    hd = next;
-                }
-                for (int l = 0; l < G; ++l) hd[(size_t)l] = mlm_head_close(hd[(size_t)l], carry.head);
-                carry = MlmCarry{Ex(G - 1), joins[(size_t)G - 1], hd[(size_t)G - 1]};
-            }
+            if (ww) emu_chunk_head(cell.data(), G, j0, carry, hd.data());
             for (int l = 0; l < G && j0 + l < row_len; ++l)
-                words[(size_t)(j0 + l)] = el[(size_t)l] ? mlm_cap_word(sp, true, mlm_draw(sp, r + row_base, hd[(size_t)l]), hd[(size_t)l]) : MLM_CAP_NONE;
+                words[(size_t)(j0 + l)] = cell[(size_t)l].eligible ? mlm_cap_word(sp, true, mlm_draw(sp, r + row_base, hd[(size_t)l]), hd[(size_t)l]) : MLM_CAP_NONE;
         }
         const int n = cap_row(words.data(), row_len, G, P, kept.data(), slot.data());          // B, C
         for (int j = 0; j < row_len; ++j) {

@@ -1,13 +1,13 @@
 // bf_mlmtest.cpp -- TEST-ONLY: the lane code of the MLM masking call (blingfire_amd/csrc/bf_mlm.h: Philox, thresholds, eligibility, the continuation
 // predicate, the head scan with its carry, the decision) compiled for the host and driven in the lane partition of k_rows_mlm: G lanes per row, a
-// row walked in chunks of G cells, the neighbour's end and flag one lane up (lane 0: the carry), the head by an inclusive max-scan in log2 G
-// steps, the last lane's values carried into the next chunk.  With BF_MLMTEST_MAIN the file is a program of its own over exactly sized heap arrays
+// row walked in chunks of G cells, the whole-word head of a chunk from rowwalk_emu.h.  With BF_MLMTEST_MAIN the file is a program of its own over exactly sized heap arrays
 // (tests build it with -fsanitize=address,undefined).
 #include <stdint.h>
 #include <stddef.h>
 #include <vector>
 #include "../../blingfire_amd/csrc/bf_rows.h"
 #include "../../blingfire_amd/csrc/bf_mlm.h"
+#include "rowwalk_emu.h"
 
 using namespace bfa;
 
@@ -39,42 +39,26 @@ int bft_mlm_rows(const int32_t *rows, int row_len, int64_t nrows, int64_t row_ba
     if (!mlm_spec(nspecial, special_ids, select_prob, mask_prob, random_prob, mask_id, rand_lo, rand_hi, ignore_label, seed, epoch, &sp)) return -1;
     const int G = group > 0 ? group : span_group(row_len);
     const bool ww = S != nullptr;
-    struct Lane { int32_t id, S, E; bool in, eligible; int joins, h; };
-    std::vector<Lane> lane((size_t)G);
-    std::vector<int> next((size_t)G);
+    std::vector<EmuHeadCell> cell((size_t)G);
+    std::vector<int32_t> id((size_t)G);
+    std::vector<int> h((size_t)G);
     for (int64_t r = 0; r < nrows; ++r) {
         const int64_t base = r * row_len;
         MlmCarry carry = mlm_carry_none();
         for (int j0 = 0; j0 < row_len; j0 += G) {
             for (int l = 0; l < G; ++l) {                 // every lane loads its own cell
-                Lane &x = lane[(size_t)l];
                 const int j = j0 + l;
-                x = Lane{0, -1, 0, j < row_len, false, 0, j};
-                if (!x.in) continue;
-                x.id = rows[base + j];
-                x.eligible = mlm_eligible(sp, x.id, mask ? mask[base + j] : (uint8_t)1, seg ? seg[base + j] : 1);
-                if (ww) { x.S = S[base + j]; x.E = E[base + j]; }
+                cell[(size_t)l] = EmuHeadCell{-1, 0, false};
+                id[(size_t)l] = 0; h[(size_t)l] = j;
+                if (j >= row_len) continue;
+                id[(size_t)l] = rows[base + j];
+                cell[(size_t)l].eligible = mlm_eligible(sp, id[(size_t)l], mask ? mask[base + j] : (uint8_t)1, seg ? seg[base + j] : 1);
+                if (ww) { cell[(size_t)l].S = S[base + j]; cell[(size_t)l].E = E[base + j]; }
             }
-            if (ww) {
-                for (int l = 0; l < G; ++l) lane[(size_t)l].joins = mlm_joins(lane[(size_t)l].eligible, lane[(size_t)l].S) ? 1 : 0;
-                for (int l = 0; l < G; ++l) {             // one lane up; lane 0 takes the carry
-                    const int32_t end_prev = l ? lane[(size_t)l - 1].E : carry.end;
-                    const int joins_prev = l ? lane[(size_t)l - 1].joins : carry.joins;
-                    next[(size_t)l] = mlm_head_seed(mlm_continues(joins_prev != 0, end_prev, lane[(size_t)l].joins != 0, lane[(size_t)l].S), j0 + l);
-                }
-                for (int l = 0; l < G; ++l) lane[(size_t)l].h = next[(size_t)l];
-                for (int d = 1; d < G; d <<= 1) {         // the scan: every lane reads d lanes up, all at once
-                    for (int l = 0; l < G; ++l) next[(size_t)l] = mlm_head_step(lane[(size_t)l].h, lane[(size_t)(l >= d ? l - d : l)].h, l >= d);
-                    for (int l = 0; l < G; ++l) lane[(size_t)l].h = next[(size_t)l];
-                }
-                for (int l = 0; l < G; ++l) lane[(size_t)l].h = mlm_head_close(lane[(size_t)l].h, carry.head);
-                carry = MlmCarry{lane[(size_t)G - 1].E, lane[(size_t)G - 1].joins, lane[(size_t)G - 1].h};
-            }
-            for (int l = 0; l < G; ++l) {
-                const Lane &x = lane[(size_t)l];
-                if (!x.in) continue;
+            if (ww) emu_chunk_head(cell.data(), G, j0, carry, h.data());
+            for (int l = 0; l < G && j0 + l < row_len; ++l) {
                 int32_t id_out, label;
-                mlm_decide(sp, r + row_base, j0 + l, x.h, x.id, x.eligible, &id_out, &label);
+                mlm_decide(sp, r + row_base, j0 + l, h[(size_t)l], id[(size_t)l], cell[(size_t)l].eligible, &id_out, &label);
                 if (ids_out) ids_out[base + j0 + l] = id_out;
                 if (labels_out) labels_out[base + j0 + l] = label;
             }

@@ -11,6 +11,7 @@ import torch
 import bfutil
 import blingfire_amd as bf
 import mlm_cases as mc
+import mlmcap_cases as cc
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +112,21 @@ def test_1_equals_the_restatement(h, L):
                 want = check(h, rows, m, s, *planes, special_ids=sp, probs=(0.3, 0.8, 0.1), seed=1000 * L + n, epoch=n)
                 n += 1
     assert L < 4 or ((want[1] != -100).any() and (want[1] == -100).any() and (want[0] == mc.MASK).any())
+
+
+@pytest.mark.parametrize("whole_word", [False, True])
+@pytest.mark.parametrize("L", [2, 6, 12])
+def test_1_group_sizes_the_table_leaves_out(h, L, whole_word):
+    """G = 2, 8 and 16 (the table's row lengths give G = 1, 4, 32, 64): 70 rows, so the last wave is partly past the end at each of them.  The
+    whole-word inputs label 2, 8 and 18 units of more than one cell"""
+    rows, mask, seg, S, E = cc.table_inputs(L, 70)
+    planes = (S, E) if whole_word else (None, None)
+    want = check(h, rows, mask, seg, *planes, special_ids=cc.TABLE_SPECIALS, probs=cc.PROBS, seed=L + 1)
+    lab = want[1].reshape(70, L) != -100
+    assert lab.any() and not lab.all()
+    if whole_word:
+        hd = mc.heads(mc.eligible(rows, mask, seg, cc.TABLE_SPECIALS), S, E)
+        assert sum(1 for r, runs in enumerate(mc.unit_runs(hd)) for a, z in runs if lab[r, a:z + 1].all()) == {2: 2, 6: 8, 12: 18}[L]
 
 
 def test_1_units_across_the_chunk_boundary(h):

@@ -133,6 +133,18 @@ def test_1_equals_the_restatement(h, L):
             assert min(cc.shares(rows, mask, seg, S, E, P, special_ids=SPECIALS, probs=cc.PROBS, seed=7)[2] for P in (1, 2)) >= 0.04
 
 
+@pytest.mark.parametrize("whole_word", [False, True])
+@pytest.mark.parametrize("L", [2, 6, 12])
+def test_1_group_sizes_the_table_leaves_out(h, L, whole_word):
+    """G = 2, 8 and 16 (the table's row lengths give G = 1, 4, 32, 64): 70 rows, so the last wave is partly past the end at each of them; at P = 1
+    the cap binds in some rows and leaves others with their selection whole"""
+    rows, mask, seg, S, E = cc.table_inputs(L, 70)
+    planes = (S, E) if whole_word else (None, None)
+    check(h, rows, mask, seg, *planes, special_ids=SPECIALS, probs=cc.PROBS, seed=L + 1, max_pred=1)
+    binds, free, _ = cc.shares(rows, mask, seg, *planes, 1, special_ids=SPECIALS, probs=cc.PROBS, seed=L + 1)
+    assert binds > 0 and free > 0, (L, binds, free)
+
+
 # ---- 2. chunk boundaries
 def test_2_units_across_the_chunk_boundaries(h):
     """L = 130 at G = 64 (three chunks, keys in registers): units over cells 60 .. 70 and 40 .. 129, a row that is one unit.  P = 5 is smaller than

@@ -454,7 +454,7 @@ def test_5_handles_of_every_kind():
 
 
 # ---- 6. span cells
-SPAN_ROWS = {1: 1, 5: 7, 8: 300, 31: 33, 32: 64, 33: 65, 63: 100, 64: 129, 65: 17, 130: 50, 512: 9}
+SPAN_ROWS = {1: 1, 2: 70, 4: 70, 5: 7, 8: 300, 12: 70, 31: 33, 32: 64, 33: 65, 63: 100, 64: 129, 65: 17, 130: 50, 512: 9}
 
 
 def window_planes(L, R, left):
