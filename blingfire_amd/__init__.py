@@ -1,17 +1,24 @@
-"""blingfire_amd -- Python mirror of the reference wrapper for the TextToIds path.
+"""blingfire_amd -- the Python face of the MI355X-native ``libblingfiretokdll.so`` built in-tree by ``blingfire_amd/build.py``.
 
-Same function names, argument meaning and return conventions as the reference
-``dist-pypi/blingfire/__init__.py`` (load_model :229-234, free_model :237-240, text_to_ids :243-253,
-change_settings_dummy_prefix :287-288, text_to_words :85-102, text_to_words_with_model :105-122), bound to the MI355X-native ``libblingfiretokdll.so`` built
-in-tree by ``blingfire_amd/build.py``.  Additive: ``text_to_ids_batch`` (host buffers) and
-``text_to_ids_batch_device`` (torch tensors already resident in HBM).
+Three layers, top to bottom of the file:
+
+* the bindings: ``_SIGNATURES``, one ``(restype, argtypes)`` entry per symbol of ``include/blingfiretokdll_amd.h`` (and the three diagnostic
+  names of ``csrc/bf_internal.h`` the tests use), applied by ``_bind``; ``tests/test_wrapper_calls.py`` checks the table against the headers;
+* the mirror of the reference wrapper ``dist-pypi/blingfire/__init__.py``: same function names, argument meaning and return conventions
+  (load_model :229-234, free_model :237-240, text_to_ids :243-253, change_settings_dummy_prefix :287-288, text_to_words :85-102,
+  text_to_words_with_model :105-122, the sentence, offsets, hashes, hyphenation and ids_to_text calls);
+* what this project adds: the batch forms over host buffers (``*_batch``) and over torch tensors already resident in HBM (``*_batch_device``)
+  of the tokenizer and of the secondary calls, the row stage that turns ragged ids into model inputs (rows, pair rows, packed rows, stream
+  rows, each with companion planes), the per-row objectives (MLM masking, span corruption), the ``encode_*`` chains that run text to model
+  inputs on one stream, and the handle controls (devices, reserve, diagnostics).  The private helpers in front of them hold what these
+  share: status checks, input staging, the capacity retry and the count-then-fill drivers of the host and of the Device forms.
 
 There is no CPU fallback: if the shared library is missing or no HIP device is visible the calls
-raise / return the reference's error value, loudly.
+raise / return the reference's error value, loudly.  ``torch`` is imported only inside the functions that need it.
 """
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, byref, c_bool, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -19,6 +26,90 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libblingfiretokdll.so")
 
 _lib = None
+
+# ---------------------------------------------------------------------------------------------
+# the bindings: symbol -> (restype, argtypes), the mirror of include/blingfiretokdll_amd.h
+# ---------------------------------------------------------------------------------------------
+_P, _I, _L = c_void_p, c_int, c_int64
+_TEXT_TO_IDS = (_I, [_P, c_char_p, _I, _P, _I, _I])
+_TEXT_TO_IDS_OFFSETS = (_I, [_P, c_char_p, _I, _P, _P, _P, _I, _I])
+_STRING = (_I, [c_char_p, _I, _P, _I])                                # text, its length, the output buffer, its size
+_STRING_OFFSETS = (_I, [c_char_p, _I, _P, _P, _P, _I])
+_TEXT_BATCH = (_L, [_P, _P, _P, _L, _P, _L, _P])                     # handle, text, offsets, ndocs, text out, its capacity, offsets out
+_TEXT_BATCH_DEVICE = (_I, [_P, _P, _P, _L, _L, _P, _L, _P, _P])
+
+_SIGNATURES = {
+    "GetBlingFireTokVersion": (_I, []),
+    "LoadModel": (_P, [c_char_p]),
+    "SetModel": (_P, [c_char_p, _I]),
+    "FreeModel": (_I, [_P]),
+    "SetNoDummyPrefix": (_I, [_P, c_bool]),
+    "TextToIds": _TEXT_TO_IDS, "TextToIds_wp": _TEXT_TO_IDS, "TextToIds_sp": _TEXT_TO_IDS,
+    "TextToIdsWithOffsets": _TEXT_TO_IDS_OFFSETS, "TextToIdsWithOffsets_wp": _TEXT_TO_IDS_OFFSETS, "TextToIdsWithOffsets_sp": _TEXT_TO_IDS_OFFSETS,
+    "TextToIdsBatch": (_L, [_P, _P, _P, _L, _P, _L, _P, _I, _I]),
+    "TextToIdsBatchDevice": (_I, [_P, _P, _P, _L, _L, _P, _L, _P, _I, _I, _P]),
+    "TextToIdsWithOffsetsBatch": (_L, [_P, _P, _P, _L, _P, _P, _P, _L, _P, _I, _I]),
+    "TextToIdsWithOffsetsBatchDevice": (_I, [_P, _P, _P, _L, _L, _P, _P, _P, _L, _P, _I, _I, _P]),
+    "TextToWords": _STRING, "TextToSentences": _STRING,
+    "TextToWordsWithModel": (_I, _STRING[1] + [_P]), "TextToSentencesWithModel": (_I, _STRING[1] + [_P]),
+    "TextToWordsWithOffsets": _STRING_OFFSETS, "TextToSentencesWithOffsets": _STRING_OFFSETS,
+    "TextToWordsWithOffsetsWithModel": (_I, _STRING_OFFSETS[1] + [_P]), "TextToSentencesWithOffsetsWithModel": (_I, _STRING_OFFSETS[1] + [_P]),
+    "TextToWordsBatch": _TEXT_BATCH, "TextToSentencesBatch": _TEXT_BATCH,
+    "TextToWordsBatchDevice": _TEXT_BATCH_DEVICE, "TextToSentencesBatchDevice": _TEXT_BATCH_DEVICE,
+    "NormalizeSpaces": (_I, _STRING[1] + [_I]),
+    "NormalizeSpacesBatch": (_L, [_P, _P, _L, _P, _L, _P, _I]),
+    "TextToHashes": (_I, _STRING[1] + [_I, _I]),
+    "TextToHashesBatch": (_L, [_P, _P, _L, _P, _L, _P, _I, _I]),
+    "WordHyphenationWithModel": (_I, _STRING[1] + [_P, _I]),
+    "WordHyphenationBatch": (_L, _TEXT_BATCH[1] + [_I]),
+    "WordHyphenationBatchDevice": (_I, _TEXT_BATCH_DEVICE[1][:-1] + [_I, _P]),
+    "IdsToText": (_I, [_P, _P, _I, _P, _I, c_bool]),
+    "IdsToTextBatch": (_L, _TEXT_BATCH[1] + [_I]),
+    "IdsToTextBatchDevice": (_I, _TEXT_BATCH[1] + [_I, _P]),
+    "DictGetInfoBatch": (_L, [_P, _P, _P, _L, _P, _P, _P, _L, _P]),
+    "DictGetInfoBatchDevice": (_I, [_P, _P, _P, _L, _P, _P, _P, _L, _P, _P]),
+    # the row stage: ragged ids (the Device forms also take their length), the row parameters, the outputs, their capacity, the size answers
+    "IdsToRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 7 + [_P] * 4 + [_L, _P]),
+    "IdsToRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 7 + [_P] * 4 + [_L, _P, _P]),
+    "IdsToPairRowsBatch": (_L, [_P, _P, _P, _P, _P, _L] + [_I] * 9 + [_P] * 5 + [_L, _P]),
+    "IdsToPairRowsBatchDevice": (_I, [_P, _P, _L, _P, _P, _L, _P, _L] + [_I] * 9 + [_P] * 5 + [_L, _P, _P]),
+    "IdsToPackedRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 5 + [_P] * 4 + [_L, _P, _P]),
+    "IdsToPackedRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 5 + [_P] * 4 + [_L] + [_P] * 4),
+    "IdsToStreamRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 6 + [_P] * 6 + [_L, _P, _P]),
+    "IdsToStreamRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 6 + [_P] * 6 + [_L] + [_P] * 4),
+    "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
+    "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
+    "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
+    "BfLastKernelMs": (_I, [_P, POINTER(c_float), _I]),
+    "BfLastStatus": (_I, [_P]),
+    "BfLastError": (c_char_p, []),
+    "BfBpeFallbackDocs": (c_longlong, [_P]),
+    "BfModelKind": (_I, [_P]),
+    "BfReserve": (_I, [_P, _L, _L, _I]),
+    "BfSetBpePoolBytes": (_L, [_P, _L]),
+    "BfSetDevices": (_I, [_P, _P, _I]),
+    "BfShardHandle": (_P, [_P, _I]),
+    "BfShardRanges": (_I, [_P, _L, _I, _P]),
+    # declared in csrc/bf_internal.h: diagnostics the tests and tools drive
+    "BfSetVariant": (_I, [_P, _I]),
+    "BfSetLexStats": (_I, [_P, _I]),
+    "BfWorkspaceGrows": (_I, [_P]),
+}
+# a ...Planes... call is its base call plus (nplanes, one source array per side, fill, planes out), in front of the stream of a Device form
+for _base in ("IdsToRowsBatch", "IdsToPairRowsBatch", "IdsToPackedRowsBatch"):
+    _tail = [_I] + [_P] * (4 if "Pair" in _base else 3)
+    for _dev in ("", "Device"):
+        _res, _args = _SIGNATURES[_base + _dev]
+        _SIGNATURES[_base.replace("RowsBatch", "RowsPlanesBatch") + _dev] = (_res, _args[:-1] + _tail + _args[-1:] if _dev else _args + _tail)
+_SIGNATURES["RowsMlmPredictionsBatchDevice"] = (_I, _SIGNATURES["RowsMlmMaskBatchDevice"][1][:-1] + [_I, _P, _P, _P, _P])
+
+
+def _bind(L):
+    """applies _SIGNATURES to a loaded library (or to what stands in for one in a test) and returns it"""
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
+    return L
 
 
 def lib():
@@ -28,146 +119,262 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("%s is missing: run `python -m blingfire_amd.build` (hipcc, gfx950) first; "
                                "there is no CPU fallback" % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        L.LoadModel.restype = c_void_p
-        L.LoadModel.argtypes = [c_char_p]
-        L.SetModel.restype = c_void_p
-        L.SetModel.argtypes = [c_char_p, c_int]
-        L.FreeModel.restype = c_int
-        L.FreeModel.argtypes = [c_void_p]
-        for name in ("TextToIds", "TextToIds_wp", "TextToIds_sp"):
-            f = getattr(L, name)
-            f.restype = c_int
-            f.argtypes = [c_void_p, c_char_p, c_int, c_void_p, c_int, c_int]
-        for name in ("TextToIdsWithOffsets", "TextToIdsWithOffsets_wp", "TextToIdsWithOffsets_sp"):
-            f = getattr(L, name)
-            f.restype = c_int
-            f.argtypes = [c_void_p, c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int]
-        L.TextToIdsWithOffsetsBatch.restype = c_int64
-        L.TextToIdsWithOffsetsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int]
-        L.TextToIdsWithOffsetsBatchDevice.restype = c_int
-        L.TextToIdsWithOffsetsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                                      c_void_p, c_int, c_int, c_void_p]
-        L.SetNoDummyPrefix.restype = c_int
-        L.SetNoDummyPrefix.argtypes = [c_void_p, ctypes.c_bool]
-        L.GetBlingFireTokVersion.restype = c_int
-        L.TextToIdsBatch.restype = c_int64
-        L.TextToIdsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int]
-        L.TextToIdsBatchDevice.restype = c_int
-        L.TextToIdsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p,
-                                           c_int, c_int, c_void_p]
-        L.TextToWords.restype = c_int
-        L.TextToWords.argtypes = [c_char_p, c_int, c_void_p, c_int]
-        L.TextToWordsWithModel.restype = c_int
-        L.TextToWordsWithModel.argtypes = [c_char_p, c_int, c_void_p, c_int, c_void_p]
-        L.TextToWordsWithOffsets.restype = c_int
-        L.TextToWordsWithOffsets.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_int]
-        L.TextToWordsWithOffsetsWithModel.restype = c_int
-        L.TextToWordsWithOffsetsWithModel.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-        L.TextToSentences.restype = c_int
-        L.TextToSentences.argtypes = [c_char_p, c_int, c_void_p, c_int]
-        L.TextToSentencesWithModel.restype = c_int
-        L.TextToSentencesWithModel.argtypes = [c_char_p, c_int, c_void_p, c_int, c_void_p]
-        L.TextToSentencesWithOffsets.restype = c_int
-        L.TextToSentencesWithOffsets.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_int]
-        L.TextToSentencesWithOffsetsWithModel.restype = c_int
-        L.TextToSentencesWithOffsetsWithModel.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]
-        L.TextToWordsBatch.restype = c_int64
-        L.TextToWordsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-        L.TextToWordsBatchDevice.restype = c_int
-        L.TextToWordsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
-        L.TextToSentencesBatch.restype = c_int64
-        L.TextToSentencesBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]
-        L.TextToSentencesBatchDevice.restype = c_int
-        L.TextToSentencesBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]
-        L.IdsToText.restype = c_int
-        L.IdsToText.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_bool]
-        L.IdsToTextBatch.restype = c_int64
-        L.IdsToTextBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int]
-        L.IdsToTextBatchDevice.restype = c_int
-        L.IdsToTextBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]
-        L.IdsToRowsBatch.restype = c_int64
-        L.IdsToRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-        L.IdsToRowsBatchDevice.restype = c_int
-        L.IdsToRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-        L.IdsToPairRowsBatch.restype = c_int64
-        L.IdsToPairRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [c_int64, c_void_p]
-        L.IdsToPairRowsBatchDevice.restype = c_int
-        L.IdsToPairRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 9 + [c_void_p] * 5 + [
-            c_int64, c_void_p, c_void_p]
-        L.IdsToRowsPlanesBatch.restype = c_int64
-        L.IdsToRowsPlanesBatch.argtypes = L.IdsToRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p]
-        L.IdsToRowsPlanesBatchDevice.restype = c_int
-        L.IdsToRowsPlanesBatchDevice.argtypes = L.IdsToRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.IdsToPairRowsPlanesBatch.restype = c_int64
-        L.IdsToPairRowsPlanesBatch.argtypes = L.IdsToPairRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.IdsToPairRowsPlanesBatchDevice.restype = c_int
-        L.IdsToPairRowsPlanesBatchDevice.argtypes = L.IdsToPairRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.RowsSpanCellsBatchDevice.restype = c_int
-        L.RowsSpanCellsBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
-                                               c_void_p, c_void_p, c_void_p]
-        L.RowsMlmMaskBatchDevice.restype = c_int
-        L.RowsMlmMaskBatchDevice.argtypes = [c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 5 + [c_int, c_void_p] + [c_double] * 3 + [c_int] * 4 + [
-            c_uint64, c_uint32, c_void_p, c_void_p, c_void_p]
-        L.RowsMlmPredictionsBatchDevice.restype = c_int
-        L.RowsMlmPredictionsBatchDevice.argtypes = L.RowsMlmMaskBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.RowsDenoiseBatchDevice.restype = c_int
-        L.RowsDenoiseBatchDevice.argtypes = [c_void_p, c_void_p, c_int, c_int64] + [c_void_p] * 3 + [c_int, c_void_p, c_double] + [c_int] * 8 + [c_uint64, c_uint32] + [
-            c_int, c_void_p, c_void_p, c_void_p] * 2 + [c_void_p, c_void_p]
-        L.IdsToPackedRowsBatch.restype = c_int64
-        L.IdsToPackedRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p]
-        L.IdsToPackedRowsBatchDevice.restype = c_int
-        L.IdsToPackedRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int64] + [c_void_p] * 4
-        L.IdsToPackedRowsPlanesBatch.restype = c_int64
-        L.IdsToPackedRowsPlanesBatch.argtypes = L.IdsToPackedRowsBatch.argtypes + [c_int, c_void_p, c_void_p, c_void_p]
-        L.IdsToPackedRowsPlanesBatchDevice.restype = c_int
-        L.IdsToPackedRowsPlanesBatchDevice.argtypes = L.IdsToPackedRowsBatchDevice.argtypes[:-1] + [c_int, c_void_p, c_void_p, c_void_p, c_void_p]
-        L.IdsToStreamRowsBatch.restype = c_int64
-        L.IdsToStreamRowsBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64] + [c_int] * 6 + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p]
-        L.IdsToStreamRowsBatchDevice.restype = c_int
-        L.IdsToStreamRowsBatchDevice.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64] + [c_int] * 6 + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4
-        L.BfLastKernelMs.restype = c_int
-        L.BfLastKernelMs.argtypes = [c_void_p, POINTER(c_float), c_int]
-        L.BfLastStatus.restype = c_int
-        L.BfLastStatus.argtypes = [c_void_p]
-        L.BfLastError.restype = c_char_p
-        L.BfModelKind.restype = c_int
-        L.BfModelKind.argtypes = [c_void_p]
-        L.BfSetVariant.restype = c_int
-        L.BfSetVariant.argtypes = [c_void_p, c_int]
-        L.DictGetInfoBatch.restype = c_int64
-        L.DictGetInfoBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-        L.DictGetInfoBatchDevice.restype = c_int
-        L.DictGetInfoBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
-        L.BfSetDevices.restype = c_int
-        L.BfSetDevices.argtypes = [c_void_p, c_void_p, c_int]
-        L.BfShardHandle.restype = c_void_p
-        L.BfShardHandle.argtypes = [c_void_p, c_int]
-        L.BfShardRanges.restype = c_int
-        L.BfShardRanges.argtypes = [c_void_p, c_int64, c_int, c_void_p]
-        L.BfSetLexStats.restype = c_int
-        L.BfSetLexStats.argtypes = [c_void_p, c_int]
-        L.BfSetBpePoolBytes.restype = c_int64
-        L.BfSetBpePoolBytes.argtypes = [c_void_p, c_int64]
-        L.BfWorkspaceGrows.restype = c_int
-        L.BfWorkspaceGrows.argtypes = [c_void_p]
-        L.BfReserve.restype = c_int
-        L.BfReserve.argtypes = [c_void_p, c_int64, c_int64, c_int]
-        L.NormalizeSpaces.restype = c_int
-        L.NormalizeSpaces.argtypes = [c_char_p, c_int, c_void_p, c_int, c_int]
-        L.TextToHashes.restype = c_int
-        L.TextToHashes.argtypes = [c_char_p, c_int, c_void_p, c_int, c_int, c_int]
-        L.WordHyphenationWithModel.restype = c_int
-        L.WordHyphenationWithModel.argtypes = [c_char_p, c_int, c_void_p, c_int, c_void_p, c_int]
-        L.WordHyphenationBatch.restype = c_int64
-        L.WordHyphenationBatch.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int]
-        L.WordHyphenationBatchDevice.restype = c_int
-        L.WordHyphenationBatchDevice.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p]
-        _lib = L
+        _lib = _bind(ctypes.CDLL(LIB_PATH))
     return _lib
 
+
+# ---------------------------------------------------------------------------------------------
+# shared helpers
+# ---------------------------------------------------------------------------------------------
+_COUNT = "%s failed: %d (%s)"                   # the message of the host calls that answer a count; the Device and control calls use _check's default
+
+
+def _last_error():
+    return lib().BfLastError().decode("utf-8", "replace")
+
+
+def _check(name, r, ok, layout="%s failed (%d): %s"):
+    if not ok:
+        raise RuntimeError(layout % (name, r, _last_error()))
+
+
+def _special(i):
+    return -1 if i is None else int(i)
+
+
+def _nspecial(*ids):
+    """how many of the special ids there are (None or negative = none)"""
+    return sum(1 for i in ids if _special(i) >= 0)
+
+
+def _default_special_ids(*ids):
+    return [i for i in map(_special, ids) if i >= 0]
+
+
+def _seed_args(seed, epoch):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF
+
+
+def _ids_cap(total, ndocs, max_len):
+    """the ids `ndocs` documents of `total` bytes can give: every id covers >= 1 element of <= 2*(n+1) per document"""
+    return min(2 * (total + ndocs), ndocs * max(max_len, 0))
+
+
+def pack_docs(docs):
+    """list of str/bytes -> (uint8 array, int64 offsets[ndocs+1])"""
+    bs = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs]
+    off = np.zeros(len(bs) + 1, dtype=np.int64)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=off[1:])
+    text = np.frombuffer(b"".join(bs), dtype=np.uint8) if bs else np.zeros(0, dtype=np.uint8)
+    return text, off
+
+
+def _host_ragged(items, off, dtype=np.int32):
+    """-> (items, offsets, n): contiguous arrays of `dtype` and int64, and the number of ranges"""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    return np.ascontiguousarray(items, dtype=dtype), off, len(off) - 1
+
+
+def _host_docs(docs):
+    """list of str / bytes, or a (uint8 array, int64 offsets) pair -> _host_ragged of the text"""
+    return _host_ragged(*(docs if isinstance(docs, tuple) else pack_docs(docs)), dtype=np.uint8)
+
+
+def _upload_docs(docs):
+    """_host_docs, uploaded with torch to the current device -> (text, offsets) tensors"""
+    import torch
+    text, off, _ = _host_docs(docs)
+    return torch.from_numpy(text.copy()).cuda(), torch.from_numpy(off.copy()).cuda()
+
+
+def _stream_arg(stream, dev):
+    """the caller's raw stream handle, or torch's current stream on `dev`"""
+    import torch
+    return c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _dev_addr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _np_i32(x):
+    return None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+
+
+def _dev_i32(t, dev, what):
+    """a device array a kernel reads as int32 through its address: None, or a contiguous torch.int32 tensor on `dev` (anything else would be read
+    as garbage -- an int64 labels tensor as pairs of int32 -- so it is refused, not converted behind the caller's back)"""
+    import torch
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
+        raise ValueError("%s must be a contiguous torch.int32 tensor on %s (got %s)" % (
+            what, dev, "%s, %s, %s" % (t.dtype, t.device, "contiguous" if t.is_contiguous() else "not contiguous") if isinstance(t, torch.Tensor) else type(t).__name__))
+    return t
+
+
+def _string_call(name, s, mul, add, *post):
+    """the reference's single-string calls: `s` into a buffer of mul * bytes + add -> the string the library wrote, '' on error or if it does not fit"""
+    s_bytes = s.encode("utf-8")
+    o = ctypes.create_string_buffer(len(s_bytes) * mul + add)
+    n = getattr(lib(), name)(s_bytes, len(s_bytes), o, len(o), *post)
+    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+
+
+def _spans_call(name, s, h, mul, count):
+    """the reference's ...WithOffsets calls: (string, [(begin, end) per unit]) with the library's byte offsets (end inclusive) turned into character
+    offsets into `s` (end exclusive); count(string) = the units there are"""
+    s_bytes = s.encode("utf-8")
+    cap = len(s_bytes) * mul
+    o = ctypes.create_string_buffer(max(cap, 1))
+    st = (c_int32 * max(cap, 1))()
+    en = (c_int32 * max(cap, 1))()
+    n = getattr(lib(), name)(s_bytes, len(s_bytes), o, byref(st), byref(en), cap, c_void_p(h) if h else None)
+    if n == -1 or n > cap:
+        return "", []
+    text = o.value.decode("utf-8")
+    lead = np.frombuffer(s_bytes, dtype=np.uint8) & 0xC0 != 0x80
+    char_at = np.concatenate([[0], np.cumsum(lead)])          # byte offset -> number of characters that start before it
+    return text, [(int(char_at[st[i]]), int(char_at[en[i] + 1])) for i in range(count(text) if text else 0)]
+
+
+def _capacity_retry(name, pre, post, dtype, n):
+    """the host calls that size their own output: fn(*pre, out, capacity, offsets, *post) with no output first; on BF_E_CAPACITY (-3) the offsets
+    tell the size and the call is made again.  -> (out, offsets int64[n + 1])"""
+    fn = getattr(lib(), name)
+    out, off = np.empty(0, dtype=dtype), np.zeros(n + 1, dtype=np.int64)
+    r = fn(*pre, None, 0, off.ctypes.data, *post)
+    if r == -3:
+        out = np.empty(int(off[-1]), dtype=dtype)
+        r = fn(*pre, out.ctypes.data, len(out), off.ctypes.data, *post)
+    _check(name, r, r >= 0, _COUNT)
+    return out, off
+
+
+# The outputs a row call has in front of its capacity: (dtype, an [R, L] plane or an [R] vector, entries beyond R).
+_PLANE, _MASK, _VEC = ("int32", True, 0), ("uint8", True, 0), ("int32", False, 0)
+_ROWS_OUTS = (_PLANE, _MASK, _VEC, _VEC)                              # rows, mask, row item, row first id
+_PAIR_OUTS = (_PLANE, _MASK, _MASK, _VEC, _VEC)                       # rows, mask, type, row pair, row first B id
+_PACKED_OUTS = (_PLANE,) * 3 + (("int32", False, 1),)                 # rows, seg, pos, row_first_seq[R + 1]
+_STREAM_OUTS = (_PLANE,) * 4 + (_VEC,) * 2                            # rows, seg, pos, labels, row first seq, row first pos
+
+
+def _outs(spec, n, L, dev=None):
+    """the outputs of `spec` for n rows: numpy arrays, or torch tensors on `dev`"""
+    shapes = [((n + more, L) if plane else (n + more,), t) for t, plane, more in spec]
+    if dev is None:
+        return [np.empty(shape, dtype=t) for shape, t in shapes]
+    import torch
+    return [torch.empty(shape, dtype=getattr(torch, t), device=dev) for shape, t in shapes]
+
+
+def _plane_tail(srcs, fill, addr):
+    """the companion-plane arguments of the ...Planes calls: `srcs` = one list of arrays / tensors (None entries allowed) per side, `fill` = one int per
+    plane, addr(x) = the address of an array.  -> (nplanes, tail) with tail(outs) = the arguments for the plane outputs `outs` (None: every
+    plane NULL); the ctypes arrays live as long as `tail` does"""
+    n = len(fill)
+    if n > 4 or any(len(side) != n for side in srcs):
+        raise ValueError("companion planes: at most 4, and one source (or None) per fill value and side")
+    c_src = [(c_void_p * max(n, 1))(*[None if x is None else addr(x) for x in side]) for side in srcs]
+    c_fill = (c_int32 * max(n, 1))(*[int(f) for f in fill])
+
+    def tail(outs):
+        c_out = (c_void_p * max(n, 1))(*([None] * n if outs is None else [addr(o) for o in outs]))
+        return (n, *c_src, c_fill, c_out)
+    return n, tail
+
+
+def _planes_host(sides, fill):
+    return _plane_tail([[_np_i32(x) for x in side] for side in sides], fill, lambda a: a.ctypes.data)
+
+
+def _planes_device(sides, fill, dev, what):
+    """what: one "function: argument[%d]" per side, for the message that refuses a source"""
+    return _plane_tail([[_dev_i32(t, dev, w % k) for k, t in enumerate(side)] for w, side in zip(what, sides)], fill, lambda t: t.data_ptr())
+
+
+def _pair_sides(src_a, src_b, n):
+    return [list(src_a) if src_a is not None else [None] * n, list(src_b) if src_b is not None else [None] * n]
+
+
+def _planes_name(name, extra):
+    return name.replace("RowsBatch", "RowsPlanesBatch") if extra else name
+
+
+def _count_fill_host(name, pre, spec, L, answers, fill_empty, extra=None):
+    """the host forms of the row stage (count_fill_host of bf_capi.cpp, seen from outside): fn(*pre, outputs of `spec`, capacity, *answers[, planes])
+    with every output NULL at capacity 0 answers the row count R -- `answers` (sized by the items, not by the rows) are filled by that call already
+    -- then the outputs are allocated and the call is made again; with R = 0 only if `fill_empty`.  extra = (nplanes, tail) of _plane_tail: the
+    ...Planes symbol, whose int32 [R, L] planes are appended to the result as a list.  -> (*outputs, *answers[, planes])"""
+    name = _planes_name(name, extra)
+    fn = getattr(lib(), name)
+    nextra, tail = extra if extra else (0, lambda outs: ())
+    after = [a.ctypes.data for a in answers]
+    n = fn(*pre, *[None] * len(spec), 0, *after, *tail(None))
+    _check(name, n, n >= 0, _COUNT)
+    outs = _outs(spec, n, L)
+    more = _outs((_PLANE,) * nextra, n, L)
+    if n > 0 or fill_empty:
+        r = fn(*pre, *[o.ctypes.data for o in outs], n, *after, *tail(more))
+        _check(name, r, r == n, _COUNT)
+    return (*outs, *answers, more) if extra else (*outs, *answers)
+
+
+def _count_fill_device(name, pre, spec, L, seq, total, rows_cap, dev, stream, extra=None):
+    """the Device forms of the row stage that may have to ask for their size: fn(*pre, outputs of `spec`, capacity, *seq, total[, planes], stream);
+    `seq` = the outputs sized by the items, `total` = the int64 tensor whose last element is the row count.  rows_cap None: a size query (every
+    output NULL at capacity 0) whose total is read back.  extra: as in _count_fill_host.  -> (outputs, planes)"""
+    import torch
+    name = _planes_name(name, extra)
+    fn = getattr(lib(), name)
+    nextra, tail = extra if extra else (0, lambda outs: ())
+    s = _stream_arg(stream, dev)
+
+    def call(outs, cap, seq_outs, more=None):
+        r = fn(*pre, *outs, cap, *seq_outs, total.data_ptr(), *tail(more), s)
+        _check(name, r, r == 0)
+    if rows_cap is None:
+        call([None] * len(spec), 0, [None] * len(seq))
+        if stream is not None:
+            torch.cuda.synchronize(dev)                   # (a raw stream handle: nothing finer to wait on)
+        rows_cap = int(total[-1].item())
+    outs = _outs(spec, rows_cap, L, dev)
+    more = _outs((_PLANE,) * nextra, rows_cap, L, dev)
+    call([o.data_ptr() for o in outs], rows_cap, [t.data_ptr() for t in seq], more)
+    return outs, more
+
+
+def _head(h, nseq, *ragged):
+    """the leading arguments of a call over ragged ids: the handle, (ids, offsets) of every side -- numpy arrays, or torch tensors for the Device
+    forms, which also take the length of the ids -- and the number of sequences"""
+    args = [c_void_p(h)]
+    for ids, off in ragged:
+        args += [ids.ctypes.data, off.ctypes.data] if isinstance(ids, np.ndarray) else [ids.data_ptr(), ids.numel(), off.data_ptr()]
+    return (*args, nseq)
+
+
+def _rows_args(L, cls_id, sep_id, pad_id, stride, max_rows_per_seq, pad_left):
+    return (int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride), int(max_rows_per_seq), int(bool(pad_left)))
+
+
+def _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep):
+    return (int(L), _special(cls_id), _special(sep_id), int(pad_id), int(mode), int(max_a), int(stride), int(max_rows_per_pair),
+            (1 if pad_left else 0) | (2 if double_sep else 0))
+
+
+def _packed_args(L, cls_id, sep_id, pad_id):
+    return (int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
+
+
+def _stream_args(L, bos_id, eos_id, pad_id, ignore_label, drop_last, pos_from_row, labels_within_doc):
+    return (int(L), _special(bos_id), _special(eos_id), int(pad_id), int(ignore_label),
+            (1 if drop_last else 0) | (2 if pos_from_row else 0) | (4 if labels_within_doc else 0))
+
+
+# ---------------------------------------------------------------------------------------------
+# the mirror of the reference wrapper
+# ---------------------------------------------------------------------------------------------
 
 def get_blingfiretok_version():
     return lib().GetBlingFireTokVersion()
@@ -177,7 +384,7 @@ def load_model(file_name):
     """reference __init__.py:229-234; raises instead of returning a NULL handle."""
     h = lib().LoadModel(file_name.encode("utf-8"))
     if not h:
-        raise RuntimeError("LoadModel(%r) failed: %s" % (file_name, lib().BfLastError().decode("utf-8", "replace")))
+        raise RuntimeError("LoadModel(%r) failed: %s" % (file_name, _last_error()))
     return h
 
 
@@ -207,10 +414,7 @@ def utf8text_to_ids_with_offsets(h, s_bytes, max_len, unk=0, no_padding=False):
 
 def normalize_spaces(s, uSpace=0x20):
     """reference __init__.py:65-82: runs of white space -> one uSpace, leading / trailing dropped; '' on error."""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 2 + 4)
-    n = lib().NormalizeSpaces(s_bytes, len(s_bytes), o, len(o), uSpace)
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("NormalizeSpaces", s, 2, 4, uSpace)
 
 
 def text_to_hashes(s, word_n_grams, bucketSize):
@@ -227,94 +431,45 @@ def text_to_hashes(s, word_n_grams, bucketSize):
 def word_hyphenation_with_model(h, s, uHy=0x2D):
     """reference __init__.py:125-142: the word with uHy behind every hyphenation point of the model's [w2h] patterns (h: a handle of
     syllab.bin or of another model with that section); '' on error or for a handle without one."""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 4 + 1)
-    n = lib().WordHyphenationWithModel(s_bytes, len(s_bytes), o, len(o), c_void_p(h) if h else None, uHy)
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("WordHyphenationWithModel", s, 4, 1, c_void_p(h) if h else None, uHy)
 
 
 def word_hyphenation_batch(h, words, uHy=0x2D):
     """additive: word_hyphenation_with_model over many words (str or bytes) in one call -> list of str; '' where the single call fails."""
-    text, off = pack_docs([w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in words])
-    nw = len(off) - 1
-    t_off = np.zeros(nw + 1, dtype=np.int64)
-    args = (c_void_p(h), c_void_p(text.ctypes.data), c_void_p(off.ctypes.data), nw)
-    fn = lib().WordHyphenationBatch
-    n = fn(*args, None, 0, c_void_p(t_off.ctypes.data), uHy)
-    out = np.empty(0, dtype=np.uint8)
-    if n == -3:                                           # BF_E_CAPACITY: the offsets tell the size
-        out = np.empty(int(t_off[-1]), dtype=np.uint8)
-        n = fn(*args, c_void_p(out.ctypes.data), len(out), c_void_p(t_off.ctypes.data), uHy)
-    if n < 0:
-        raise RuntimeError("WordHyphenationBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
+    text, off, nw = _host_ragged(*pack_docs(words), dtype=np.uint8)
+    out, t_off = _capacity_retry("WordHyphenationBatch", (c_void_p(h), text.ctypes.data, off.ctypes.data, nw), (uHy,), np.uint8, nw)
     raw = out.tobytes()
     return [raw[t_off[i]:t_off[i + 1]].decode("utf-8") for i in range(nw)]
 
 
 def text_to_words(s):
     """reference __init__.py:85-102: space-joined words by the built-in wbd.bin; '' on error."""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 3)
-    n = lib().TextToWords(s_bytes, len(s_bytes), o, len(o))
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("TextToWords", s, 3, 0)
 
 
 def text_to_words_with_model(h, s):
     """reference __init__.py:105-122"""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 3)
-    n = lib().TextToWordsWithModel(s_bytes, len(s_bytes), o, len(o), c_void_p(h))
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("TextToWordsWithModel", s, 3, 0, c_void_p(h))
 
 
 def text_to_words_with_offsets(s, h=None):
     """reference __init__.py:161-223: (string, [(begin, end) per word]) as character offsets into `s`, end exclusive."""
-    s_bytes = s.encode("utf-8")
-    cap = len(s_bytes) * 3
-    o = ctypes.create_string_buffer(max(cap, 1))
-    st = (c_int32 * max(cap, 1))()
-    en = (c_int32 * max(cap, 1))()
-    n = lib().TextToWordsWithOffsetsWithModel(s_bytes, len(s_bytes), o, byref(st), byref(en), cap, c_void_p(h) if h else None)
-    if n == -1 or n > cap:
-        return "", []
-    words = o.value.decode("utf-8")
-    k = len(words.split(" ")) if words else 0
-    lead = np.frombuffer(s_bytes, dtype=np.uint8) & 0xC0 != 0x80
-    char_at = np.concatenate([[0], np.cumsum(lead)])          # byte offset -> number of characters that start before it
-    return words, [(int(char_at[st[i]]), int(char_at[en[i] + 1])) for i in range(k)]
+    return _spans_call("TextToWordsWithOffsetsWithModel", s, h, 3, lambda words: len(words.split(" ")))
 
 
 def text_to_sentences(s):
     """reference __init__.py:45-62: one sentence per line by the built-in sbd.bin; '' on error."""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 2)
-    n = lib().TextToSentences(s_bytes, len(s_bytes), o, len(o))
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("TextToSentences", s, 2, 0)
 
 
 def text_to_sentences_with_model(h, s):
     """reference __init__.py:65-82"""
-    s_bytes = s.encode("utf-8")
-    o = ctypes.create_string_buffer(len(s_bytes) * 2)
-    n = lib().TextToSentencesWithModel(s_bytes, len(s_bytes), o, len(o), c_void_p(h))
-    return "" if n == -1 or n > len(o) else o.value.decode("utf-8")
+    return _string_call("TextToSentencesWithModel", s, 2, 0, c_void_p(h))
 
 
 def text_to_sentences_and_offsets(s, h=None):
     """reference __init__.py:225-226: (string, [(begin, end) per sentence]) as character offsets into `s`, end exclusive."""
-    s_bytes = s.encode("utf-8")
-    cap = len(s_bytes) * 2
-    o = ctypes.create_string_buffer(max(cap, 1))
-    st = (c_int32 * max(cap, 1))()
-    en = (c_int32 * max(cap, 1))()
-    n = lib().TextToSentencesWithOffsetsWithModel(s_bytes, len(s_bytes), o, byref(st), byref(en), cap, c_void_p(h) if h else None)
-    if n == -1 or n > cap:
-        return "", []
-    sents = o.value.decode("utf-8")
-    k = sents.count("\n") + 1 if sents else 0
-    lead = np.frombuffer(s_bytes, dtype=np.uint8) & 0xC0 != 0x80
-    char_at = np.concatenate([[0], np.cumsum(lead)])
-    return sents, [(int(char_at[st[i]]), int(char_at[en[i] + 1])) for i in range(k)]
+    return _spans_call("TextToSentencesWithOffsetsWithModel", s, h, 2, lambda sents: sents.count("\n") + 1)
 
 
 def text_to_sentences_batch(docs, h=None):
@@ -325,20 +480,8 @@ def text_to_sentences_batch(docs, h=None):
 def text_to_words_batch(docs, h=None, _fn="TextToWordsBatch"):
     """additive: TextToWords over many documents (list of bytes, or a (text uint8, offsets int64) pair) -> (text uint8, offsets int64[ndocs+1]);
     h None = the built-in wbd.bin."""
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    text = np.ascontiguousarray(text, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.int64)
-    nd = len(off) - 1
-    t_off = np.zeros(nd + 1, dtype=np.int64)
-    hp = c_void_p(h) if h else None
-    fn = getattr(lib(), _fn)
-    n = fn(hp, c_void_p(text.ctypes.data), c_void_p(off.ctypes.data), nd, None, 0, c_void_p(t_off.ctypes.data))
-    out = np.empty(0, dtype=np.uint8)
-    if n == -3:                                           # BF_E_CAPACITY: the offsets tell the size
-        out = np.empty(int(t_off[-1]), dtype=np.uint8)
-        n = fn(hp, c_void_p(text.ctypes.data), c_void_p(off.ctypes.data), nd, c_void_p(out.ctypes.data), len(out), c_void_p(t_off.ctypes.data))
-    if n < 0:
-        raise RuntimeError("%s failed: %d (%s)" % (_fn, n, lib().BfLastError().decode("utf-8", "replace")))
-    return out, t_off
+    text, off, nd = _host_docs(docs)
+    return _capacity_retry(_fn, (c_void_p(h) if h else None, text.ctypes.data, off.ctypes.data, nd), (), np.uint8, nd)
 
 
 def ids_to_text(h, ids, skip_special_tokens=True, output_buffer_size=None):
@@ -355,21 +498,8 @@ def ids_to_text(h, ids, skip_special_tokens=True, output_buffer_size=None):
 
 def ids_to_text_batch(h, ids, id_off, skip_special_tokens=True):
     """additive: (text bytes as uint8 array, text offsets int64[nseq+1]) for many id sequences at once (IdsToTextBatch)."""
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
-    nseq = len(id_off) - 1
-    t_off = np.zeros(nseq + 1, dtype=np.int64)
-    n = lib().IdsToTextBatch(c_void_p(h), c_void_p(ids.ctypes.data), c_void_p(id_off.ctypes.data), nseq, None, 0, c_void_p(t_off.ctypes.data),
-                             int(bool(skip_special_tokens)))
-    if n == -3:                                           # BF_E_CAPACITY: the offsets tell the size
-        text = np.empty(int(t_off[-1]), dtype=np.uint8)
-        n = lib().IdsToTextBatch(c_void_p(h), c_void_p(ids.ctypes.data), c_void_p(id_off.ctypes.data), nseq, c_void_p(text.ctypes.data), len(text),
-                                 c_void_p(t_off.ctypes.data), int(bool(skip_special_tokens)))
-    else:
-        text = np.empty(0, dtype=np.uint8)
-    if n < 0:
-        raise RuntimeError("IdsToTextBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
-    return text, t_off
+    ids, id_off, nseq = _host_ragged(ids, id_off)
+    return _capacity_retry("IdsToTextBatch", (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq), (int(bool(skip_special_tokens)),), np.uint8, nseq)
 
 
 def change_settings_dummy_prefix(h, add_prefix):
@@ -380,23 +510,12 @@ def change_settings_dummy_prefix(h, add_prefix):
 # additive batch API
 # ---------------------------------------------------------------------------------------------
 
-def pack_docs(docs):
-    """list of str/bytes -> (uint8 array, int64 offsets[ndocs+1])"""
-    bs = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs]
-    off = np.zeros(len(bs) + 1, dtype=np.int64)
-    if bs:
-        np.cumsum([len(b) for b in bs], out=off[1:])
-    text = np.frombuffer(b"".join(bs), dtype=np.uint8) if bs else np.zeros(0, dtype=np.uint8)
-    return text, off
-
-
 def set_devices(h, device_ids):
     """Range-shards the host-buffer batch calls of h over the listed devices of this node (BfSetDevices: tables replicated, contiguous
     byte-balanced document ranges, one host thread per device, no collective).  A device may be listed more than once."""
     arr = (c_int * len(device_ids))(*[int(d) for d in device_ids])
     r = lib().BfSetDevices(c_void_p(h), arr, len(device_ids))
-    if r != 0:
-        raise RuntimeError("BfSetDevices failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    _check("BfSetDevices", r, r == 0)
 
 
 def shard_handle(h, g):
@@ -419,37 +538,25 @@ def text_to_ids_batch(h, docs, max_len, unk=0):
 
     docs: list of str/bytes, or a (uint8 ndarray, int64 offsets) pair.  Returns (ids int32[total], offsets int64[ndocs+1]).
     """
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    text = np.ascontiguousarray(text, dtype=np.uint8)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    ndocs = len(off) - 1
-    total = int(off[-1] - off[0]) if ndocs > 0 else 0
-    cap = min(2 * (total + ndocs), ndocs * max(max_len, 0)) + 1      # every id covers >= 1 element of <= 2*(n+1) per document
+    text, off, ndocs = _host_docs(docs)
+    cap = _ids_cap(int(off[-1] - off[0]) if ndocs > 0 else 0, ndocs, max_len) + 1
     ids = np.empty(cap, dtype=np.int32)
     id_off = np.zeros(ndocs + 1, dtype=np.int64)
     r = lib().TextToIdsBatch(c_void_p(h), text.ctypes.data, off.ctypes.data, ndocs, ids.ctypes.data, cap, id_off.ctypes.data,
                              max_len, unk)
-    if r < 0:
-        raise RuntimeError("TextToIdsBatch failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    _check("TextToIdsBatch", r, r >= 0)
     return ids[:r], id_off
 
 
 def text_to_ids_with_offsets_batch(h, docs, max_len, unk=0):
     """Batch form of TextToIdsWithOffsets: (ids, starts, ends, id_offsets); starts/ends are byte offsets inside each document."""
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    text = np.ascontiguousarray(text, dtype=np.uint8)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    ndocs = len(off) - 1
-    total = int(off[-1] - off[0]) if ndocs > 0 else 0
-    cap = min(2 * (total + ndocs), ndocs * max(max_len, 0)) + 1
-    ids = np.empty(cap, dtype=np.int32)
-    starts = np.empty(cap, dtype=np.int32)
-    ends = np.empty(cap, dtype=np.int32)
+    text, off, ndocs = _host_docs(docs)
+    cap = _ids_cap(int(off[-1] - off[0]) if ndocs > 0 else 0, ndocs, max_len) + 1
+    ids, starts, ends = (np.empty(cap, dtype=np.int32) for _ in range(3))
     id_off = np.zeros(ndocs + 1, dtype=np.int64)
     r = lib().TextToIdsWithOffsetsBatch(c_void_p(h), text.ctypes.data, off.ctypes.data, ndocs, ids.ctypes.data, starts.ctypes.data,
                                         ends.ctypes.data, cap, id_off.ctypes.data, max_len, unk)
-    if r < 0:
-        raise RuntimeError("TextToIdsWithOffsetsBatch failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    _check("TextToIdsWithOffsetsBatch", r, r >= 0)
     return ids[:r], starts[:r], ends[:r], id_off
 
 
@@ -462,16 +569,13 @@ def text_to_ids_batch_device(h, d_text, d_doc_off, max_len, unk=0, out_ids=None,
     import torch
     ndocs = d_doc_off.numel() - 1
     total = d_text.numel()
-    cap = max(1, min(2 * (total + ndocs), ndocs * max(max_len, 0)))
     if out_ids is None:
-        out_ids = torch.empty(cap, dtype=torch.int32, device=d_text.device)
+        out_ids = torch.empty(max(1, _ids_cap(total, ndocs, max_len)), dtype=torch.int32, device=d_text.device)
     if out_off is None:
         out_off = torch.empty(ndocs + 1, dtype=torch.int64, device=d_text.device)
-    s = stream if stream is not None else torch.cuda.current_stream(d_text.device).cuda_stream
     r = lib().TextToIdsBatchDevice(c_void_p(h), d_text.data_ptr(), d_doc_off.data_ptr(), ndocs, total, out_ids.data_ptr(),
-                                   out_ids.numel(), out_off.data_ptr(), max_len, unk, c_void_p(s))
-    if r != 0:
-        raise RuntimeError("TextToIdsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+                                   out_ids.numel(), out_off.data_ptr(), max_len, unk, _stream_arg(stream, d_text.device))
+    _check("TextToIdsBatchDevice", r, r == 0)
     return out_ids, out_off
 
 
@@ -482,14 +586,12 @@ def text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, max_len, unk=0, 
     import torch
     ndocs = d_doc_off.numel() - 1
     total = d_text.numel()
-    cap = max(1, min(2 * (total + ndocs), ndocs * max(max_len, 0)))
+    cap = max(1, _ids_cap(total, ndocs, max_len))
     ids, starts, ends = (torch.empty(cap, dtype=torch.int32, device=d_text.device) for _ in range(3))
     out_off = torch.empty(ndocs + 1, dtype=torch.int64, device=d_text.device)
-    s = stream if stream is not None else torch.cuda.current_stream(d_text.device).cuda_stream
     r = lib().TextToIdsWithOffsetsBatchDevice(c_void_p(h), d_text.data_ptr(), d_doc_off.data_ptr(), ndocs, total, ids.data_ptr(), starts.data_ptr(),
-                                              ends.data_ptr(), cap, out_off.data_ptr(), max_len, unk, c_void_p(s))
-    if r != 0:
-        raise RuntimeError("TextToIdsWithOffsetsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+                                              ends.data_ptr(), cap, out_off.data_ptr(), max_len, unk, _stream_arg(stream, d_text.device))
+    _check("TextToIdsWithOffsetsBatchDevice", r, r == 0)
     return ids, starts, ends, out_off
 
 
@@ -502,77 +604,39 @@ def ids_to_text_batch_device(h, d_ids, d_id_off, out_text=None, out_off=None, sk
         out_text = torch.empty(max(16 * d_ids.numel(), 1), dtype=torch.uint8, device=d_ids.device)
     if out_off is None:
         out_off = torch.empty(nseq + 1, dtype=torch.int64, device=d_ids.device)
-    s = stream if stream is not None else torch.cuda.current_stream(d_ids.device).cuda_stream
     r = lib().IdsToTextBatchDevice(c_void_p(h), d_ids.data_ptr(), d_id_off.data_ptr(), nseq, out_text.data_ptr(), out_text.numel(),
-                                   out_off.data_ptr(), int(bool(skip_special_tokens)), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("IdsToTextBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+                                   out_off.data_ptr(), int(bool(skip_special_tokens)), _stream_arg(stream, d_ids.device))
+    _check("IdsToTextBatchDevice", r, r == 0)
     return out_text, out_off
 
 
-def _special(i):
-    return -1 if i is None else int(i)
-
-
-def _plane_tail(srcs, fill, addr):
-    """the companion-plane arguments of the ...Planes calls: `srcs` = one list of arrays / tensors (None entries allowed) per side, `fill` = one int per
-    plane, addr(x) = the address of an array.  -> (nplanes, tail) with tail(outs) = the arguments for the plane outputs `outs` (None: every
-    plane NULL); the ctypes arrays live as long as `tail` does"""
-    n = len(fill)
-    if n > 4 or any(len(side) != n for side in srcs):
-        raise ValueError("companion planes: at most 4, and one source (or None) per fill value and side")
-    c_src = [(c_void_p * max(n, 1))(*[None if x is None else addr(x) for x in side]) for side in srcs]
-    c_fill = (c_int32 * max(n, 1))(*[int(f) for f in fill])
-
-    def tail(outs):
-        c_out = (c_void_p * max(n, 1))(*([None] * n if outs is None else [addr(o) for o in outs]))
-        return (n, *c_src, c_fill, c_out)
-    return n, tail
-
-
-def _rows_host(name, pre, nseq, L, planes, extra=None):
-    """the host forms of the row stage: the size query, then every output (one `planes` dtype per [R, L] plane, row item, row first id).
-    extra = (nplanes, tail) of _plane_tail: the ...Planes calls, whose int32 [R, L] planes are appended to the result as a list"""
-    fn = getattr(lib(), name)
-    nextra, tail = extra if extra else (0, lambda outs: ())
+def _rows_host(name, pre, nseq, L, spec, planes):
+    """the host forms of rows and pair rows; planes = None (the base symbol) or (sources per side, fill)"""
     r_off = np.zeros(nseq + 1, dtype=np.int64)
-    n = fn(*pre, *[None] * (len(planes) + 2), 0, r_off.ctypes.data, *tail(None))
-    if n < 0:
-        raise RuntimeError("%s failed: %d (%s)" % (name, n, lib().BfLastError().decode("utf-8", "replace")))
-    outs = [np.empty((n, L), dtype=t) for t in planes] + [np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)]
-    more = [np.empty((n, L), dtype=np.int32) for _ in range(nextra)]
-    if n > 0:
-        r = fn(*pre, *[o.ctypes.data for o in outs], n, r_off.ctypes.data, *tail(more))
-        if r != n:
-            raise RuntimeError("%s failed: %d (%s)" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
-    return (*outs, r_off, more) if extra else (*outs, r_off)
+    return _count_fill_host(name, pre, spec, L, [r_off], False, planes and _planes_host(*planes))
 
 
-def _rows_device(name, pre, nseq, L, planes, one_row, rows_cap, dev, stream, extra=None):
-    """the device forms of the row stage.  rows_cap None: nseq rows where one row per item is certain (`one_row`), else a size query whose
-    total is read back.  extra: as in _rows_host"""
+def _rows_device(name, pre, nseq, L, spec, one_row, rows_cap, dev, stream, planes, what=()):
+    """the Device forms of rows and pair rows.  rows_cap None: nseq rows where one row per item is certain (`one_row`), else a size query whose
+    total is read back.  planes, what: as in _rows_host and _planes_device"""
     import torch
-    fn = getattr(lib(), name)
-    nextra, tail = extra if extra else (0, lambda outs: ())
-    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+    extra = planes and _planes_device(*planes, dev, what)
     r_off = torch.empty(nseq + 1, dtype=torch.int64, device=dev)
-
-    def call(outs, cap, more=None):
-        r = fn(*pre, *outs, cap, r_off.data_ptr(), *tail(more), s)
-        if r != 0:
-            raise RuntimeError("%s failed (%d): %s" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
-    if rows_cap is None:
-        if one_row:
-            rows_cap = nseq
-        else:
-            call([None] * (len(planes) + 2), 0)
-            if stream is not None:
-                torch.cuda.synchronize(dev)               # (a raw stream handle: nothing finer to wait on)
-            rows_cap = int(r_off[-1].item())
-    outs = [torch.empty((rows_cap, L), dtype=t, device=dev) for t in planes] + [torch.empty(rows_cap, dtype=torch.int32, device=dev) for _ in range(2)]
-    more = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(nextra)]
-    call([o.data_ptr() for o in outs], rows_cap, more)
+    if rows_cap is None and one_row:
+        rows_cap = nseq
+    outs, more = _count_fill_device(name, pre, spec, L, [], r_off, rows_cap, dev, stream, extra)
     return (*outs, r_off, more) if extra else (*outs, r_off)
+
+
+def _ids_to_rows(h, ids, id_off, L, args, planes=None):
+    ids, id_off, nseq = _host_ragged(ids, id_off)
+    return _rows_host("IdsToRowsBatch", _head(h, nseq, (ids, id_off)) + args, nseq, L, _ROWS_OUTS, planes)
+
+
+def _ids_to_rows_device(h, d_ids, d_id_off, L, args, one_row, rows_cap, stream, planes=None):
+    nseq = d_id_off.numel() - 1
+    return _rows_device("IdsToRowsBatchDevice", _head(h, nseq, (d_ids, d_id_off)) + args, nseq, L, _ROWS_OUTS, one_row, rows_cap, d_ids.device, stream,
+                              planes, ["ids_to_rows_planes_batch_device: src[%d]"])
 
 
 def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False):
@@ -580,12 +644,7 @@ def ids_to_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, str
     the row is cut into windows that share `stride` ids (max_rows_per_seq: 1 = truncate, 0 = every window); cls_id / sep_id None = no
     such special.  Returns (rows int32[R, L], mask uint8[R, L], row_seq int32[R], row_first int32[R], row_offsets int64[nseq+1]):
     the rows of sequence q are [row_offsets[q], row_offsets[q+1]), row_first is the index within its sequence of a row's first id."""
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
-    nseq = len(id_off) - 1
-    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride),
-           int(max_rows_per_seq), int(bool(pad_left)))
-    return _rows_host("IdsToRowsBatch", pre, nseq, L, (np.int32, np.uint8))
+    return _ids_to_rows(h, ids, id_off, L, _rows_args(L, cls_id, sep_id, pad_id, stride, max_rows_per_seq, pad_left))
 
 
 def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False,
@@ -594,52 +653,23 @@ def ids_to_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pa
     the same five results as tensors on that device, enqueued on torch's current stream (or `stream`).  rows_cap None: nseq rows when
     max_rows_per_seq is 1 (nothing is read back); otherwise a size query whose total is read back (one synchronisation).  With a
     rows_cap of the caller's the tensors have rows_cap rows, row_offsets[-1] of them valid; rows beyond it are dropped (BfLastStatus bit 0)."""
-    import torch
-    nseq = d_id_off.numel() - 1
-    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id),
-           int(stride), int(max_rows_per_seq), int(bool(pad_left)))
-    return _rows_device("IdsToRowsBatchDevice", pre, nseq, L, (torch.int32, torch.uint8), max_rows_per_seq == 1, rows_cap, d_ids.device, stream)
-
-
-def _np_i32(x):
-    return None if x is None else np.ascontiguousarray(x, dtype=np.int32)
-
-
-def _dev_i32(t, dev, what):
-    """a device array a kernel reads as int32 through its address: None, or a contiguous torch.int32 tensor on `dev` (anything else would be read
-    as garbage -- an int64 labels tensor as pairs of int32 -- so it is refused, not converted behind the caller's back)"""
-    import torch
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev:
-        raise ValueError("%s must be a contiguous torch.int32 tensor on %s (got %s)" % (
-            what, dev, "%s, %s, %s" % (t.dtype, t.device, "contiguous" if t.is_contiguous() else "not contiguous") if isinstance(t, torch.Tensor) else type(t).__name__))
-    return t
+    return _ids_to_rows_device(h, d_ids, d_id_off, L, _rows_args(L, cls_id, sep_id, pad_id, stride, max_rows_per_seq, pad_left), max_rows_per_seq == 1,
+                               rows_cap, stream)
 
 
 def ids_to_rows_planes_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False, src=(), fill=()):
     """ids_to_rows_batch with companion planes (IdsToRowsPlanesBatch): src = up to 4 int32 arrays parallel to ids (token offsets, labels, ...),
     fill = one int per array.  Returns ids_to_rows_batch's five results and the list of planes, int32[R, L] each: a cell that holds an id holds
     that id's element of the array, every other cell the array's fill."""
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
-    src = [_np_i32(x) for x in src]
-    nseq = len(id_off) - 1
-    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), int(stride),
-           int(max_rows_per_seq), int(bool(pad_left)))
-    return _rows_host("IdsToRowsPlanesBatch", pre, nseq, L, (np.int32, np.uint8), _plane_tail([src], fill, lambda a: a.ctypes.data))
+    return _ids_to_rows(h, ids, id_off, L, _rows_args(L, cls_id, sep_id, pad_id, stride, max_rows_per_seq, pad_left), ([src], fill))
 
 
 def ids_to_rows_planes_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, stride=0, max_rows_per_seq=1, pad_left=False,
                                     rows_cap=None, stream=None, src=(), fill=()):
     """Device-resident ids_to_rows_planes_batch: src = int32 tensors on the device of d_ids, parallel to it (the starts / ends of
     text_to_ids_with_offsets_batch_device as they are).  Returns ids_to_rows_batch_device's five results and the list of plane tensors."""
-    import torch
-    nseq = d_id_off.numel() - 1
-    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id),
-           int(stride), int(max_rows_per_seq), int(bool(pad_left)))
-    return _rows_device("IdsToRowsPlanesBatchDevice", pre, nseq, L, (torch.int32, torch.uint8), max_rows_per_seq == 1, rows_cap, d_ids.device, stream,
-                        _plane_tail([[_dev_i32(t, d_ids.device, "ids_to_rows_planes_batch_device: src[%d]" % k) for k, t in enumerate(src)]], fill, lambda t: t.data_ptr()))
+    return _ids_to_rows_device(h, d_ids, d_id_off, L, _rows_args(L, cls_id, sep_id, pad_id, stride, max_rows_per_seq, pad_left), max_rows_per_seq == 1,
+                               rows_cap, stream, ([src], fill))
 
 
 def rows_span_cells_device(h, starts, ends, row_seq, row_offsets, span_first, span_last, none_cell=0, stream=None):
@@ -663,12 +693,10 @@ def rows_span_cells_device(h, starts, ends, row_seq, row_offsets, span_first, sp
     if span_first.numel() != span_last.numel() or span_first.numel() < nseq:
         raise ValueError("rows_span_cells_device: span_first / span_last need one entry per item (%d)" % nseq)
     out = [torch.full((R,), int(none_cell), dtype=torch.int32, device=starts.device) for _ in range(2)]
-    s = stream if stream is not None else torch.cuda.current_stream(starts.device).cuda_stream
     r = lib().RowsSpanCellsBatchDevice(c_void_p(h), starts.data_ptr(), ends.data_ptr(), L, R,
-                                       None if row_offsets is None else row_offsets.data_ptr() + 8 * nseq, None if row_seq is None else row_seq.data_ptr(),
-                                       nseq, span_first.data_ptr(), span_last.data_ptr(), int(none_cell), out[0].data_ptr(), out[1].data_ptr(), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("RowsSpanCellsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+                                       None if row_offsets is None else row_offsets.data_ptr() + 8 * nseq, _dev_addr(row_seq),
+                                       nseq, span_first.data_ptr(), span_last.data_ptr(), int(none_cell), out[0].data_ptr(), out[1].data_ptr(), _stream_arg(stream, dev))
+    _check("RowsSpanCellsBatchDevice", r, r == 0)
     return out[0], out[1]
 
 
@@ -677,7 +705,7 @@ def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, 
     Every document is tokenised up to the ids its rows can hold (all of them when max_rows_per_doc is 0).
     Returns (rows int32[R, L], mask uint8[R, L], row_doc int32[R], row_offsets int64[ndocs+1]); with return_offsets also
     (starts int32[R, L], ends int32[R, L]): every token's first and last byte in its document, -1 in cells without a token."""
-    body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
+    body = int(L) - _nspecial(cls_id, sep_id)
     step = body - int(stride)
     if body < 1 or stride < 0 or step < 1 or max_rows_per_doc < 0:
         raise ValueError("encode_batch_device: L leaves no room for ids, or stride / max_rows_per_doc are out of range")
@@ -695,16 +723,23 @@ def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, 
 def encode_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False):
     """encode_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed, uploaded with torch to the current
     device, encoded there."""
-    import torch
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
-    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
-    return encode_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, stride, max_rows_per_doc, pad_left)
+    return encode_batch_device(h, *_upload_docs(docs), L, cls_id, sep_id, pad_id, unk, stride, max_rows_per_doc, pad_left)
 
 
-def _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep):
-    return (int(L), _special(cls_id), _special(sep_id), int(pad_id), int(mode), int(max_a), int(stride), int(max_rows_per_pair),
-            (1 if pad_left else 0) | (2 if double_sep else 0))
+def _ids_to_pair_rows(fn_name, h, ids_a, off_a, ids_b, off_b, L, args, planes=None):
+    ids_a, off_a, nseq = _host_ragged(ids_a, off_a)
+    ids_b, off_b, nseq_b = _host_ragged(ids_b, off_b)
+    if nseq_b != nseq:
+        raise ValueError("%s: off_a and off_b name different numbers of sequences" % fn_name)
+    return _rows_host("IdsToPairRowsBatch", _head(h, nseq, (ids_a, off_a), (ids_b, off_b)) + args, nseq, L, _PAIR_OUTS, planes)
+
+
+def _ids_to_pair_rows_device(fn_name, h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, args, one_row, rows_cap, stream, planes=None):
+    nseq = d_off_a.numel() - 1
+    if d_off_b.numel() != nseq + 1:
+        raise ValueError("%s: d_off_a and d_off_b name different numbers of sequences" % fn_name)
+    return _rows_device("IdsToPairRowsBatchDevice", _head(h, nseq, (d_ids_a, d_off_a), (d_ids_b, d_off_b)) + args, nseq, L, _PAIR_OUTS, one_row, rows_cap,
+                              d_ids_a.device, stream, planes, [fn_name + ": src_a[%d]", fn_name + ": src_b[%d]"])
 
 
 def ids_to_pair_rows_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
@@ -715,14 +750,8 @@ def ids_to_pair_rows_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id
     (max_rows_per_pair: 1 = truncate B, 0 = every window).  double_sep: two separators between A and B.  Returns (rows int32[R, L],
     mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[nseq+1]): the rows of pair q are
     [row_offsets[q], row_offsets[q+1]), row_first_b is the index within B of a row's first B id."""
-    ids_a = np.ascontiguousarray(ids_a, dtype=np.int32); off_a = np.ascontiguousarray(off_a, dtype=np.int64)
-    ids_b = np.ascontiguousarray(ids_b, dtype=np.int32); off_b = np.ascontiguousarray(off_b, dtype=np.int64)
-    nseq = len(off_a) - 1
-    if len(off_b) != nseq + 1:
-        raise ValueError("ids_to_pair_rows_batch: off_a and off_b name different numbers of sequences")
-    pre = (c_void_p(h), ids_a.ctypes.data, off_a.ctypes.data, ids_b.ctypes.data, off_b.ctypes.data, nseq) + _pair_args(
-        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    return _rows_host("IdsToPairRowsBatch", pre, nseq, L, (np.int32, np.uint8, np.uint8))
+    return _ids_to_pair_rows("ids_to_pair_rows_batch", h, ids_a, off_a, ids_b, off_b, L,
+                             _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep))
 
 
 def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0,
@@ -732,18 +761,9 @@ def ids_to_pair_rows_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_
     enqueued on torch's current stream (or `stream`).  rows_cap None: nseq rows when one row per pair is certain (mode 1, or
     max_rows_per_pair 1: nothing is read back); otherwise a size query whose total is read back (one synchronisation).  With a rows_cap of
     the caller's the tensors have rows_cap rows, row_offsets[-1] of them valid; rows beyond it are dropped (BfLastStatus bit 0)."""
-    import torch
-    nseq = d_off_a.numel() - 1
-    if d_off_b.numel() != nseq + 1:
-        raise ValueError("ids_to_pair_rows_batch_device: d_off_a and d_off_b name different numbers of sequences")
-    pre = (c_void_p(h), d_ids_a.data_ptr(), d_ids_a.numel(), d_off_a.data_ptr(), d_ids_b.data_ptr(), d_ids_b.numel(), d_off_b.data_ptr(), nseq) + _pair_args(
-        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    return _rows_device("IdsToPairRowsBatchDevice", pre, nseq, L, (torch.int32, torch.uint8, torch.uint8), mode == 1 or max_rows_per_pair == 1, rows_cap,
-                        d_ids_a.device, stream)
-
-
-def _pair_sides(src_a, src_b, n):
-    return [list(src_a) if src_a is not None else [None] * n, list(src_b) if src_b is not None else [None] * n]
+    return _ids_to_pair_rows_device("ids_to_pair_rows_batch_device", h, d_ids_a, d_off_a, d_ids_b, d_off_b, L,
+                                    _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep),
+                                    mode == 1 or max_rows_per_pair == 1, rows_cap, stream)
 
 
 def ids_to_pair_rows_planes_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
@@ -751,31 +771,18 @@ def ids_to_pair_rows_planes_batch(h, ids_a, off_a, ids_b, off_b, L, cls_id=None,
     """ids_to_pair_rows_batch with companion planes (IdsToPairRowsPlanesBatch): src_a / src_b = lists of int32 arrays parallel to ids_a / ids_b,
     one entry per fill value; a list that is None, or an entry that is, leaves that side's cells at the fill.  Returns ids_to_pair_rows_batch's
     six results and the list of planes, int32[R, L] each."""
-    ids_a = np.ascontiguousarray(ids_a, dtype=np.int32); off_a = np.ascontiguousarray(off_a, dtype=np.int64)
-    ids_b = np.ascontiguousarray(ids_b, dtype=np.int32); off_b = np.ascontiguousarray(off_b, dtype=np.int64)
-    nseq = len(off_a) - 1
-    if len(off_b) != nseq + 1:
-        raise ValueError("ids_to_pair_rows_planes_batch: off_a and off_b name different numbers of sequences")
-    sides = [[_np_i32(x) for x in side] for side in _pair_sides(src_a, src_b, len(fill))]
-    pre = (c_void_p(h), ids_a.ctypes.data, off_a.ctypes.data, ids_b.ctypes.data, off_b.ctypes.data, nseq) + _pair_args(
-        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    return _rows_host("IdsToPairRowsPlanesBatch", pre, nseq, L, (np.int32, np.uint8, np.uint8), _plane_tail(sides, fill, lambda a: a.ctypes.data))
+    return _ids_to_pair_rows("ids_to_pair_rows_planes_batch", h, ids_a, off_a, ids_b, off_b, L,
+                             _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep),
+                             (_pair_sides(src_a, src_b, len(fill)), fill))
 
 
 def ids_to_pair_rows_planes_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, L, cls_id=None, sep_id=None, pad_id=0, mode=1, max_a=0, stride=0,
                                          max_rows_per_pair=1, pad_left=False, double_sep=False, rows_cap=None, stream=None, src_a=None, src_b=None, fill=()):
     """Device-resident ids_to_pair_rows_planes_batch: src_a / src_b = lists of int32 tensors parallel to d_ids_a / d_ids_b (None entries and
     None lists allowed).  Returns ids_to_pair_rows_batch_device's six results and the list of plane tensors."""
-    import torch
-    nseq = d_off_a.numel() - 1
-    if d_off_b.numel() != nseq + 1:
-        raise ValueError("ids_to_pair_rows_planes_batch_device: d_off_a and d_off_b name different numbers of sequences")
-    pre = (c_void_p(h), d_ids_a.data_ptr(), d_ids_a.numel(), d_off_a.data_ptr(), d_ids_b.data_ptr(), d_ids_b.numel(), d_off_b.data_ptr(), nseq) + _pair_args(
-        L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
-    return _rows_device("IdsToPairRowsPlanesBatchDevice", pre, nseq, L, (torch.int32, torch.uint8, torch.uint8), mode == 1 or max_rows_per_pair == 1, rows_cap,
-                        d_ids_a.device, stream, _plane_tail([[_dev_i32(t, d_ids_a.device, "ids_to_pair_rows_planes_batch_device: src_%s[%d]" % (ab, k))
-                                                              for k, t in enumerate(side)] for ab, side in zip("ab", _pair_sides(src_a, src_b, len(fill)))],
-                                                            fill, lambda t: t.data_ptr()))
+    return _ids_to_pair_rows_device("ids_to_pair_rows_planes_batch_device", h, d_ids_a, d_off_a, d_ids_b, d_off_b, L,
+                                    _pair_args(L, cls_id, sep_id, pad_id, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep),
+                                    mode == 1 or max_rows_per_pair == 1, rows_cap, stream, (_pair_sides(src_a, src_b, len(fill)), fill))
 
 
 def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
@@ -788,7 +795,7 @@ def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id
     return_offsets also (starts int32[R, L], ends int32[R, L]): first and last byte of every token of B in its text (with offsets_a, of A in
     its own text too), -1 in every other cell."""
     nsep = 0 if _special(sep_id) < 0 else 3 if double_sep else 2
-    T = int(L) - (1 if _special(cls_id) >= 0 else 0) - nsep
+    T = int(L) - _nspecial(cls_id) - nsep
     if T < 1 or mode not in (0, 1) or (mode == 0 and not (0 <= max_a <= T - 1 and 0 <= stride < T - max_a and max_rows_per_pair >= 0)):
         raise ValueError("encode_pairs_batch_device: L leaves no room for ids, or mode / max_a / stride / max_rows_per_pair are out of range")
     if mode == 1:
@@ -834,13 +841,16 @@ def encode_qa_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, s
 def encode_pairs_batch(h, docs_a, docs_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1, pad_left=False, double_sep=False):
     """encode_pairs_batch_device for two lists of str / bytes (or two (uint8 array, int64 offsets) pairs): packed, uploaded with torch to the
     current device, encoded there."""
-    import torch
-    d = []
-    for docs in (docs_a, docs_b):
-        text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-        d.append(torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda())
-        d.append(torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda())
-    return encode_pairs_batch_device(h, d[0], d[1], d[2], d[3], L, cls_id, sep_id, pad_id, unk, mode, max_a, stride, max_rows_per_pair, pad_left, double_sep)
+    return encode_pairs_batch_device(h, *_upload_docs(docs_a), *_upload_docs(docs_b), L, cls_id, sep_id, pad_id, unk, mode, max_a, stride, max_rows_per_pair,
+                                     pad_left, double_sep)
+
+
+def _ids_to_packed_rows(h, ids, id_off, L, cls_id, sep_id, pad_id, planes=None):
+    """the host forms of the packed call; unlike _rows_host the second call is made for R = 0 too: row_first_seq has R + 1 entries"""
+    ids, id_off, nseq = _host_ragged(ids, id_off)
+    seq = [np.empty(nseq, dtype=np.int32) for _ in range(2)]
+    return _count_fill_host("IdsToPackedRowsBatch", _head(h, nseq, (ids, id_off)) + _packed_args(L, cls_id, sep_id, pad_id), _PACKED_OUTS, L, seq, True,
+                            planes and _planes_host(*planes))
 
 
 def ids_to_packed_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0):
@@ -849,38 +859,14 @@ def ids_to_packed_rows_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id
     Returns (rows int32[R, L], seg int32[R, L], pos int32[R, L], row_first_seq int32[R + 1], seq_row int32[nseq], seq_col int32[nseq]):
     seg numbers the sequences of a row from 1 (0 = padding), pos restarts at every sequence, row r holds the sequences
     [row_first_seq[r], row_first_seq[r + 1]), and sequence q begins at cell seq_col[q] of row seq_row[q]."""
-    return _packed_host("IdsToPackedRowsBatch", h, ids, id_off, L, cls_id, sep_id, pad_id)
-
-
-def _packed_host(name, h, ids, id_off, L, cls_id, sep_id, pad_id, extra=None):
-    """the host forms of the packed call: the size query, then every output.  extra = (nplanes, tail) of _plane_tail: the ...Planes call, whose
-    int32 [R, L] planes are appended to the result as a list"""
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
-    nseq = len(id_off) - 1
-    fn = getattr(lib(), name)
-    nextra, tail = extra if extra else (0, lambda outs: ())
-    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
-    seq_row = np.empty(nseq, dtype=np.int32)
-    seq_col = np.empty(nseq, dtype=np.int32)
-    n = fn(*pre, None, None, None, None, 0, seq_row.ctypes.data, seq_col.ctypes.data, *tail(None))
-    if n < 0:
-        raise RuntimeError("%s failed: %d (%s)" % (name, n, lib().BfLastError().decode("utf-8", "replace")))
-    planes = [np.empty((n, L), dtype=np.int32) for _ in range(3)]
-    more = [np.empty((n, L), dtype=np.int32) for _ in range(nextra)]
-    first = np.empty(n + 1, dtype=np.int32)
-    r = fn(*pre, *[p.ctypes.data for p in planes], first.ctypes.data, n, seq_row.ctypes.data, seq_col.ctypes.data, *tail(more))
-    if r != n:
-        raise RuntimeError("%s failed: %d (%s)" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
-    return (*planes, first, seq_row, seq_col, more) if extra else (*planes, first, seq_row, seq_col)
+    return _ids_to_packed_rows(h, ids, id_off, L, cls_id, sep_id, pad_id)
 
 
 def ids_to_packed_rows_planes_batch(h, ids, id_off, L, cls_id=None, sep_id=None, pad_id=0, src=(), fill=()):
     """ids_to_packed_rows_batch with companion planes (IdsToPackedRowsPlanesBatch): src = up to 4 int32 arrays parallel to ids (token offsets,
     labels, ...), fill = one int per array.  Returns ids_to_packed_rows_batch's six results and the list of planes, int32[R, L] each: a cell
     that holds an id holds that id's element of the array, every other cell (cls_id, sep_id, padding) the array's fill."""
-    src = [_np_i32(x) for x in src]
-    return _packed_host("IdsToPackedRowsPlanesBatch", h, ids, id_off, L, cls_id, sep_id, pad_id, _plane_tail([src], fill, lambda a: a.ctypes.data))
+    return _ids_to_packed_rows(h, ids, id_off, L, cls_id, sep_id, pad_id, ([src], fill))
 
 
 def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=None, pad_id=0, rows_cap=None, stream=None, planes=None, fill=None):
@@ -897,31 +883,12 @@ def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=N
     nseq = d_id_off.numel() - 1
     if planes is None and fill:
         raise ValueError("ids_to_packed_rows_batch_device: fill without planes")
-    nextra, tail = 0, lambda outs: ()
-    if planes is not None:
-        nextra, tail = _plane_tail([[_dev_i32(t, dev, "ids_to_packed_rows_batch_device: planes[%d]" % k) for k, t in enumerate(planes)]],
-                                   () if fill is None else fill, lambda t: t.data_ptr())
-    name = "IdsToPackedRowsBatchDevice" if planes is None else "IdsToPackedRowsPlanesBatchDevice"
-    fn = getattr(lib(), name)
-    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-    pre = (c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, int(L), _special(cls_id), _special(sep_id), int(pad_id), 0)
+    extra = None if planes is None else _planes_device([planes], () if fill is None else fill, dev, ["ids_to_packed_rows_batch_device: planes[%d]"])
     nrows = torch.empty(1, dtype=torch.int64, device=dev)
-
-    def call(outs, cap, seq, more=None):
-        r = fn(*pre, *outs, cap, *seq, nrows.data_ptr(), *tail(more), s)
-        if r != 0:
-            raise RuntimeError("%s failed (%d): %s" % (name, r, lib().BfLastError().decode("utf-8", "replace")))
-    if rows_cap is None:
-        call([None] * 4, 0, [None] * 2)
-        if stream is not None:
-            torch.cuda.synchronize(dev)                   # (a raw stream handle: nothing finer to wait on)
-        rows_cap = int(nrows.item())
-    base = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(3)]
-    more = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(nextra)]
-    first = torch.empty(rows_cap + 1, dtype=torch.int32, device=dev)
     seq = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(2)]
-    call([t.data_ptr() for t in base] + [first.data_ptr()], rows_cap, [t.data_ptr() for t in seq], more)
-    return (*base, first, *seq, nrows, *more)
+    outs, more = _count_fill_device("IdsToPackedRowsBatchDevice", _head(h, nseq, (d_ids, d_id_off)) + _packed_args(L, cls_id, sep_id, pad_id), _PACKED_OUTS, L, seq,
+                                    nrows, rows_cap, dev, stream, extra)
+    return (*outs, *seq, nrows, *more)
 
 
 def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None, return_offsets=False):
@@ -929,7 +896,7 @@ def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, 
     a row can hold) and ids_to_packed_rows_batch_device on one stream.  Returns what ids_to_packed_rows_batch_device returns; with a
     rows_cap of the caller's nothing is read back.  With return_offsets also (starts int32[R, L], ends int32[R, L]) behind nrows: every
     token's first and last byte in its document, -1 in cells without a token."""
-    body = int(L) - (1 if _special(cls_id) >= 0 else 0) - (1 if _special(sep_id) >= 0 else 0)
+    body = int(L) - _nspecial(cls_id, sep_id)
     if body < 1:
         raise ValueError("encode_packed_batch_device: L leaves no room for ids")
     if return_offsets:
@@ -942,15 +909,7 @@ def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, 
 def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None):
     """encode_packed_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed into one buffer, uploaded with
     torch to the current device, encoded there."""
-    import torch
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
-    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
-    return encode_packed_batch_device(h, d_text, d_off, L, cls_id, sep_id, pad_id, unk, rows_cap)
-
-
-def _stream_flags(drop_last, pos_from_row, labels_within_doc):
-    return (1 if drop_last else 0) | (2 if pos_from_row else 0) | (4 if labels_within_doc else 0)
+    return encode_packed_batch_device(h, *_upload_docs(docs), L, cls_id, sep_id, pad_id, unk, rows_cap)
 
 
 def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,
@@ -963,21 +922,10 @@ def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id
     seg numbers the sequences of a row from 1 (0 = padding); pos is the place in the sequence, continuing across rows (pos_from_row: counted
     from the row's edge for a sequence that continues from the row before); row r begins at place row_first_pos[r] of sequence
     row_first_seq[r]; sequence q begins at cell seq_col[q] of row seq_row[q].  drop_last drops the last row when it is incomplete."""
-    ids = np.ascontiguousarray(ids, dtype=np.int32)
-    id_off = np.ascontiguousarray(id_off, dtype=np.int64)
-    nseq = len(id_off) - 1
-    fn = lib().IdsToStreamRowsBatch
-    pre = (c_void_p(h), ids.ctypes.data, id_off.ctypes.data, nseq, int(L), _special(bos_id), _special(eos_id), int(pad_id), int(ignore_label),
-           _stream_flags(drop_last, pos_from_row, labels_within_doc))
+    ids, id_off, nseq = _host_ragged(ids, id_off)
     seq = [np.empty(nseq, dtype=np.int32) for _ in range(2)]
-    n = fn(*pre, *[None] * 6, 0, *[a.ctypes.data for a in seq])
-    if n < 0:
-        raise RuntimeError("IdsToStreamRowsBatch failed: %d (%s)" % (n, lib().BfLastError().decode("utf-8", "replace")))
-    outs = [np.empty((n, L), dtype=np.int32) for _ in range(4)] + [np.empty(n, dtype=np.int32) for _ in range(2)]
-    r = fn(*pre, *[a.ctypes.data for a in outs], n, *[a.ctypes.data for a in seq])
-    if r != n:
-        raise RuntimeError("IdsToStreamRowsBatch failed: %d (%s)" % (r, lib().BfLastError().decode("utf-8", "replace")))
-    return (*outs, *seq)
+    pre = _head(h, nseq, (ids, id_off)) + _stream_args(L, bos_id, eos_id, pad_id, ignore_label, drop_last, pos_from_row, labels_within_doc)
+    return _count_fill_host("IdsToStreamRowsBatch", pre, _STREAM_OUTS, L, seq, True)
 
 
 def ids_to_stream_rows_batch_device(h, d_ids, d_id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,
@@ -992,17 +940,13 @@ def ids_to_stream_rows_batch_device(h, d_ids, d_id_off, L, bos_id=None, eos_id=N
     nseq = d_id_off.numel() - 1
     L = int(L)
     if rows_cap is None:
-        specials = (1 if _special(bos_id) >= 0 else 0) + (1 if _special(eos_id) >= 0 else 0)
-        rows_cap = -(-(d_ids.numel() + specials * nseq) // L) if L > 0 else 0
-    s = c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
-    outs = [torch.empty((rows_cap, L), dtype=torch.int32, device=dev) for _ in range(4)] + [torch.empty(rows_cap, dtype=torch.int32, device=dev) for _ in range(2)]
+        rows_cap = -(-(d_ids.numel() + _nspecial(bos_id, eos_id) * nseq) // L) if L > 0 else 0
+    outs = _outs(_STREAM_OUTS, rows_cap, L, dev)
     seq = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(2)]
     nrows = torch.empty(2, dtype=torch.int64, device=dev)
-    r = lib().IdsToStreamRowsBatchDevice(c_void_p(h), d_ids.data_ptr(), d_ids.numel(), d_id_off.data_ptr(), nseq, L, _special(bos_id), _special(eos_id), int(pad_id),
-                                         int(ignore_label), _stream_flags(drop_last, pos_from_row, labels_within_doc), *[t.data_ptr() for t in outs], rows_cap,
-                                         *[t.data_ptr() for t in seq], nrows.data_ptr(), s)
-    if r != 0:
-        raise RuntimeError("IdsToStreamRowsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    pre = _head(h, nseq, (d_ids, d_id_off)) + _stream_args(L, bos_id, eos_id, pad_id, ignore_label, drop_last, pos_from_row, labels_within_doc)
+    r = lib().IdsToStreamRowsBatchDevice(*pre, *[t.data_ptr() for t in outs], rows_cap, *[t.data_ptr() for t in seq], nrows.data_ptr(), _stream_arg(stream, dev))
+    _check("IdsToStreamRowsBatchDevice", r, r == 0)
     return (*outs, *seq, nrows)
 
 
@@ -1021,11 +965,28 @@ def encode_clm_batch(h, docs, L, bos_id, eos_id, pad_id, unk=0, ignore_label=-10
                      rows_cap=None, max_ids_per_doc=0x7fffffff):
     """encode_clm_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed into one buffer, uploaded with
     torch to the current device, encoded there."""
+    return encode_clm_batch_device(h, *_upload_docs(docs), L, bos_id, eos_id, pad_id, unk, ignore_label, drop_last, pos_from_row, labels_within_doc, rows_cap,
+                                   max_ids_per_doc)
+
+
+def _row_inputs(fn_name, rows, mask, seg, nrows, special_ids, **int32_planes):
+    """what the per-row objectives check of their inputs: `rows`, `seg` and the further planes int32 on one device, `mask` uint8, all of one [R, L]
+    shape, `nrows` one int64 on the device, at most 8 special ids.  -> (device, R, L, the special ids as (count, int32 array))"""
     import torch
-    text, off = docs if isinstance(docs, tuple) else pack_docs(docs)
-    d_text = torch.from_numpy(np.ascontiguousarray(text, dtype=np.uint8).copy()).cuda()
-    d_off = torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64).copy()).cuda()
-    return encode_clm_batch_device(h, d_text, d_off, L, bos_id, eos_id, pad_id, unk, ignore_label, drop_last, pos_from_row, labels_within_doc, rows_cap, max_ids_per_doc)
+    dev = rows.device
+    for what, t in (("rows", rows), ("seg", seg), *int32_planes.items()):
+        _dev_i32(t, dev, "%s: %s" % (fn_name, what))
+    if rows.dim() != 2 or any(t is not None and t.shape != rows.shape for t in (mask, seg, *int32_planes.values())):
+        names = ["mask", "seg", *int32_planes]
+        raise ValueError("%s: rows is an [R, L] plane; %s and %s have its shape" % (fn_name, ", ".join(names[:-1]), names[-1]))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev):
+        raise ValueError("%s: mask must be a contiguous torch.uint8 tensor on %s" % (fn_name, dev))
+    if nrows is not None and (not isinstance(nrows, torch.Tensor) or nrows.dtype != torch.int64 or nrows.numel() != 1 or nrows.device != dev):
+        raise ValueError("%s: nrows must be a torch.int64 tensor of one element on %s" % (fn_name, dev))
+    special_ids = [int(x) for x in special_ids]
+    if len(special_ids) > 8:
+        raise ValueError("%s: at most 8 special ids" % fn_name)
+    return dev, *rows.shape, (len(special_ids), (c_int32 * max(len(special_ids), 1))(*special_ids))
 
 
 def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None, nrows=None, special_ids=(), select_prob=0.15, mask_prob=0.8, random_prob=0.1,
@@ -1045,21 +1006,9 @@ def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None
     inplace: ids is `rows` itself, overwritten.  Rows at or past nrows of a fresh ids tensor are copies of `rows`, of labels ignore_label.
     Like every batch call it clears the handle's status word first."""
     import torch
-    dev = rows.device
-    for what, t in (("rows", rows), ("seg", seg), ("starts", starts), ("ends", ends)):
-        _dev_i32(t, dev, "rows_mlm_mask_device: " + what)
-    if rows.dim() != 2 or any(t is not None and t.shape != rows.shape for t in (mask, seg, starts, ends)):
-        raise ValueError("rows_mlm_mask_device: rows is an [R, L] plane; mask, seg, starts and ends have its shape")
-    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev):
-        raise ValueError("rows_mlm_mask_device: mask must be a contiguous torch.uint8 tensor on %s" % dev)
+    dev, R, L, special = _row_inputs("rows_mlm_mask_device", rows, mask, seg, nrows, special_ids, starts=starts, ends=ends)
     if (starts is None) != (ends is None):
         raise ValueError("rows_mlm_mask_device: starts and ends come together")
-    if nrows is not None and (not isinstance(nrows, torch.Tensor) or nrows.dtype != torch.int64 or nrows.numel() != 1 or nrows.device != dev):
-        raise ValueError("rows_mlm_mask_device: nrows must be a torch.int64 tensor of one element on %s" % dev)
-    special_ids = [int(x) for x in special_ids]
-    if len(special_ids) > 8:
-        raise ValueError("rows_mlm_mask_device: at most 8 special ids")
-    R, L = rows.shape
     if isinstance(max_predictions, bool) or not isinstance(max_predictions, (int, np.integer)) or max_predictions < 0:
         raise ValueError("rows_mlm_mask_device: max_predictions is an integer >= 0")
     P = int(max_predictions)
@@ -1067,27 +1016,19 @@ def rows_mlm_mask_device(h, rows, *, mask=None, seg=None, starts=None, ends=None
         raise ValueError("rows_mlm_mask_device: max_predictions needs rows of at most 4096 cells and is at most 1 << 20")
     ids = rows if inplace else rows.clone()
     labels = torch.full((R, L), int(ignore_label), dtype=torch.int32, device=dev)
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    c_special = (c_int32 * max(len(special_ids), 1))(*special_ids)
-
-    def addr(t):
-        return None if t is None else t.data_ptr()
+    s = _stream_arg(stream, dev)
+    common = (c_void_p(h), rows.data_ptr(), L, R, _dev_addr(nrows), _dev_addr(mask), _dev_addr(seg), _dev_addr(starts), _dev_addr(ends), *special,
+              float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]), int(rand_range[1]), int(ignore_label),
+              *_seed_args(seed, epoch), ids.data_ptr(), labels.data_ptr())
     if P > 0:
         cells = torch.zeros((R, P), dtype=torch.int32, device=dev)
         plabels = torch.full((R, P), int(ignore_label), dtype=torch.int32, device=dev)
         count = torch.zeros((R,), dtype=torch.int32, device=dev)
-        r = lib().RowsMlmPredictionsBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), addr(starts), addr(ends), len(special_ids),
-                                                c_special, float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]),
-                                                int(rand_range[1]), int(ignore_label), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, ids.data_ptr(),
-                                                labels.data_ptr(), P, cells.data_ptr(), plabels.data_ptr(), count.data_ptr(), c_void_p(s))
-        if r != 0:
-            raise RuntimeError("RowsMlmPredictionsBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+        r = lib().RowsMlmPredictionsBatchDevice(*common, P, cells.data_ptr(), plabels.data_ptr(), count.data_ptr(), s)
+        _check("RowsMlmPredictionsBatchDevice", r, r == 0)
         return ids, labels, cells, plabels, count
-    r = lib().RowsMlmMaskBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), addr(starts), addr(ends), len(special_ids), c_special,
-                                     float(select_prob), float(mask_prob), float(random_prob), int(mask_id), int(rand_range[0]), int(rand_range[1]), int(ignore_label),
-                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, ids.data_ptr(), labels.data_ptr(), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("RowsMlmMaskBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    r = lib().RowsMlmMaskBatchDevice(*common, s)
+    _check("RowsMlmMaskBatchDevice", r, r == 0)
     return ids, labels
 
 
@@ -1105,7 +1046,7 @@ def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mas
     if packed and whole_word:
         raise ValueError("encode_mlm_batch_device: packed rows have no offset planes, so no whole-word masking")
     if special_ids is None:
-        special_ids = [i for i in (_special(cls_id), _special(sep_id), _special(pad_id)) if i >= 0]
+        special_ids = _default_special_ids(cls_id, sep_id, pad_id)
     kw = dict(special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id, rand_range=rand_range,
               ignore_label=ignore_label, seed=seed, epoch=epoch, inplace=True, max_predictions=max_predictions)
     if packed:
@@ -1128,10 +1069,10 @@ def encode_packed_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_
     whole_word=False masks token by token (the planes are returned all the same).  With whole_word=True a row needs cls_id or sep_id: the
     special between two sequences is what keeps a unit from joining the last token of one sequence to the first token of the next when their
     byte offsets happen to be adjacent; without either, ValueError."""
-    if whole_word and _special(cls_id) < 0 and _special(sep_id) < 0:
+    if whole_word and _nspecial(cls_id, sep_id) == 0:
         raise ValueError("encode_packed_mlm_batch_device: whole-word masking over packed rows needs cls_id or sep_id (units could join across sequences)")
     if special_ids is None:
-        special_ids = [i for i in (_special(cls_id), _special(sep_id), _special(pad_id)) if i >= 0]
+        special_ids = _default_special_ids(cls_id, sep_id, pad_id)
     out = encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk, rows_cap, return_offsets=True)
     ids, *tail = rows_mlm_mask_device(h, out[0], seg=out[1], starts=out[7] if whole_word else None, ends=out[8] if whole_word else None, nrows=out[6],
                                       special_ids=special_ids, select_prob=select_prob, mask_prob=mask_prob, random_prob=random_prob, mask_id=mask_id,
@@ -1185,19 +1126,7 @@ def rows_denoise_device(h, rows, *, mask=None, seg=None, nrows=None, special_ids
     longer than a smaller value is cut there and sets BfLastStatus bit 0.  Rows at or past nrows hold pad_id / ignore_label / -1 and counts of 0.
     The result is a function of (seed, epoch, row) and the row alone.  Like every batch call it clears the handle's status word first."""
     import torch
-    dev = rows.device
-    _dev_i32(rows, dev, "rows_denoise_device: rows")
-    _dev_i32(seg, dev, "rows_denoise_device: seg")
-    if rows.dim() != 2 or any(t is not None and t.shape != rows.shape for t in (mask, seg)):
-        raise ValueError("rows_denoise_device: rows is an [R, L] plane; mask and seg have its shape")
-    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.device != dev):
-        raise ValueError("rows_denoise_device: mask must be a contiguous torch.uint8 tensor on %s" % dev)
-    if nrows is not None and (not isinstance(nrows, torch.Tensor) or nrows.dtype != torch.int64 or nrows.numel() != 1 or nrows.device != dev):
-        raise ValueError("rows_denoise_device: nrows must be a torch.int64 tensor of one element on %s" % dev)
-    special_ids = [int(x) for x in special_ids]
-    if len(special_ids) > 8:
-        raise ValueError("rows_denoise_device: at most 8 special ids")
-    R, L = rows.shape
+    dev, R, L, special = _row_inputs("rows_denoise_device", rows, mask, seg, nrows, special_ids)
     enc_len = L if enc_len is None else int(enc_len)
     dec_len = L + 2 if dec_len is None else int(dec_len)
     if enc_len < 1 or dec_len < 1:
@@ -1206,17 +1135,11 @@ def rows_denoise_device(h, rows, *, mask=None, seg=None, nrows=None, special_ids
     dec = torch.full((R, dec_len), int(ignore_label), dtype=torch.int32, device=dev)
     counts = [torch.zeros((R,), dtype=torch.int32, device=dev) for _ in range(3)]
     cells = [torch.full((R, n), -1, dtype=torch.int32, device=dev) for n in (enc_len, dec_len)] if return_cells else [None, None]
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    c_special = (c_int32 * max(len(special_ids), 1))(*special_ids)
-
-    def addr(t):
-        return None if t is None else t.data_ptr()
-    r = lib().RowsDenoiseBatchDevice(c_void_p(h), rows.data_ptr(), L, R, addr(nrows), addr(mask), addr(seg), len(special_ids), c_special, float(start_prob), int(len_lo),
+    r = lib().RowsDenoiseBatchDevice(c_void_p(h), rows.data_ptr(), L, R, _dev_addr(nrows), _dev_addr(mask), _dev_addr(seg), *special, float(start_prob), int(len_lo),
                                      int(len_hi), int(sentinel_first), int(sentinel_step), int(max_sentinels), _special(eos_id), int(pad_id), int(ignore_label),
-                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, enc_len, enc.data_ptr(), addr(cells[0]), counts[0].data_ptr(), dec_len,
-                                     dec.data_ptr(), addr(cells[1]), counts[1].data_ptr(), counts[2].data_ptr(), c_void_p(s))
-    if r != 0:
-        raise RuntimeError("RowsDenoiseBatchDevice failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+                                     *_seed_args(seed, epoch), enc_len, enc.data_ptr(), _dev_addr(cells[0]), counts[0].data_ptr(), dec_len,
+                                     dec.data_ptr(), _dev_addr(cells[1]), counts[1].data_ptr(), counts[2].data_ptr(), _stream_arg(stream, dev))
+    _check("RowsDenoiseBatchDevice", r, r == 0)
     out = dict(input_ids=enc, labels=dec, enc_count=counts[0], dec_count=counts[1], span_count=counts[2])
     if return_cells:
         out.update(enc_cells=cells[0], dec_cells=cells[1])
@@ -1268,35 +1191,24 @@ def dict_get_info_batch(h, keys):
         if seqs:
             np.cumsum([len(q) for q in seqs], out=off[1:])
         flat = np.array([c for q in seqs for c in q], dtype=np.int32)
-    flat = np.ascontiguousarray(flat, dtype=np.int32)
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    nk = len(off) - 1
-    ret = np.zeros(nk, dtype=np.int32)
+    flat, off, nk = _host_ragged(flat, off)
+    ret = np.zeros(nk, dtype=np.int32)                    # the two per-key outputs: the size pass fills them already
     ids = np.zeros(nk, dtype=np.int32)
-    v_off = np.zeros(nk + 1, dtype=np.int64)
-    L = lib()
-    n = L.DictGetInfoBatch(c_void_p(h), flat.ctypes.data, off.ctypes.data, nk, ret.ctypes.data, ids.ctypes.data, None, 0, v_off.ctypes.data)
-    vals = np.empty(0, dtype=np.int32)
-    if n == -3:                                           # BF_E_CAPACITY: the offsets tell the size
-        vals = np.empty(int(v_off[-1]), dtype=np.int32)
-        n = L.DictGetInfoBatch(c_void_p(h), flat.ctypes.data, off.ctypes.data, nk, ret.ctypes.data, ids.ctypes.data, vals.ctypes.data, len(vals), v_off.ctypes.data)
-    if n < 0:
-        raise RuntimeError("DictGetInfoBatch failed: %d (%s)" % (n, L.BfLastError().decode("utf-8", "replace")))
+    vals, v_off = _capacity_retry("DictGetInfoBatch", (c_void_p(h), flat.ctypes.data, off.ctypes.data, nk, ret.ctypes.data, ids.ctypes.data), (), np.int32, nk)
     return ret, ids, vals, v_off
 
 
 def reserve(h, max_docs, max_bytes, want_offsets=False):
     """additive: size the handle's workspaces once (BfReserve) so that later device-resident batches of that size allocate nothing."""
     r = lib().BfReserve(c_void_p(h), int(max_docs), int(max_bytes), int(bool(want_offsets)))
-    if r != 0:
-        raise RuntimeError("BfReserve failed (%d): %s" % (r, lib().BfLastError().decode("utf-8", "replace")))
+    _check("BfReserve", r, r == 0)
 
 
 def workspace_grows():
     """diagnostic (BfWorkspaceGrows): (device allocations the library's workspaces and tables have made in this process, those of them for the
     long-document workspace of the words modes, which reserve() leaves out).  A device-resident call on a reserved handle moves neither,
     or only the second."""
-    out = (ctypes.c_longlong * 2)()
+    out = (c_longlong * 2)()
     r = lib().BfWorkspaceGrows(out)
     if r != 0:
         raise RuntimeError("BfWorkspaceGrows failed (%d)" % r)
