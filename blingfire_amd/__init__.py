@@ -37,6 +37,7 @@ _STRING = (_I, [c_char_p, _I, _P, _I])                                # text, it
 _STRING_OFFSETS = (_I, [c_char_p, _I, _P, _P, _P, _I])
 _TEXT_BATCH = (_L, [_P, _P, _P, _L, _P, _L, _P])                     # handle, text, offsets, ndocs, text out, its capacity, offsets out
 _TEXT_BATCH_DEVICE = (_I, [_P, _P, _P, _L, _L, _P, _L, _P, _P])
+_CHARPOS = (_I, [_P, _P, _P, _L, _L, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P])
 
 _SIGNATURES = {
     "GetBlingFireTokVersion": (_I, []),
@@ -80,6 +81,8 @@ _SIGNATURES = {
     "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
     "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
     "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
+    # offsets in characters: handle, text, doc offsets, ndocs, total bytes, item offsets, items cap, starts, ends, unit, flags, the three outputs, stream
+    "ByteToCharOffsetsBatchDevice": _CHARPOS, "CharToByteOffsetsBatchDevice": _CHARPOS,
     "BfLastKernelMs": (_I, [_P, POINTER(c_float), _I]),
     "BfLastStatus": (_I, [_P]),
     "BfLastError": (c_char_p, []),
@@ -700,18 +703,100 @@ def rows_span_cells_device(h, starts, ends, row_seq, row_offsets, span_first, sp
     return out[0], out[1]
 
 
-def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False, return_offsets=False):
+_OFFSET_UNITS = {"char": 0, "utf16": 1}
+
+
+def _charpos_device(name, h, d_text, d_doc_off, starts, ends, item_off, unit, ends_in_exclusive, ends_out_exclusive, items_cap, stream, return_doc_units, in_place):
+    """the two offset conversions: one argument list, one result layout"""
+    import torch
+    if unit not in _OFFSET_UNITS:
+        raise ValueError("%s: unit is 'char' (code points) or 'utf16' (UTF-16 code units), not %r" % (name, unit))
+    dev = d_text.device
+    ndocs = d_doc_off.numel() - 1
+    what = name + ": %s"
+    starts, ends = _dev_i32(starts, dev, what % "starts"), _dev_i32(ends, dev, what % "ends")
+    if item_off is not None and (item_off.dtype != torch.int64 or not item_off.is_contiguous() or item_off.device != dev or item_off.numel() != ndocs + 1):
+        raise ValueError("%s: item_off must be a contiguous torch.int64 tensor of ndocs + 1 entries on %s" % (name, dev))
+    if starts is not None and ends is not None and starts.numel() != ends.numel():
+        raise ValueError("%s: starts and ends name different numbers of items" % name)
+    given = starts if starts is not None else ends
+    if items_cap is None:
+        items_cap = 0 if given is None else given.numel()
+    elif given is not None and items_cap > given.numel():
+        raise ValueError("%s: items_cap is beyond the arrays" % name)
+    outs = [None if t is None else t if in_place else torch.empty_like(t) for t in (starts, ends)]
+    units = torch.empty(ndocs, dtype=torch.int32, device=dev) if return_doc_units else None
+    fn = "ByteToCharOffsetsBatchDevice" if name.startswith("byte") else "CharToByteOffsetsBatchDevice"
+    r = getattr(lib(), fn)(c_void_p(h), d_text.data_ptr(), d_doc_off.data_ptr(), ndocs, d_text.numel(), _dev_addr(item_off), int(items_cap), _dev_addr(starts), _dev_addr(ends),
+                           _OFFSET_UNITS[unit], (1 if ends_in_exclusive else 0) | (2 if ends_out_exclusive else 0), _dev_addr(outs[0]), _dev_addr(outs[1]), _dev_addr(units),
+                           _stream_arg(stream, dev))
+    _check(fn, r, r == 0)
+    return (*outs, units) if return_doc_units else tuple(outs)
+
+
+def byte_to_char_offsets_device(h, d_text, d_doc_off, starts=None, ends=None, item_off=None, unit="char", ends_in_exclusive=False, ends_out_exclusive=False, items_cap=None,
+                                stream=None, return_doc_units=False, in_place=False):
+    """Byte offsets inside documents that are in HBM -> offsets in code points (unit "char": what a Python str indexes by) or in UTF-16 code units
+    ("utf16": C#, JS), on the device (ByteToCharOffsetsBatchDevice).  starts / ends: int32 tensors of one entry per item, either may be None;
+    item_off: the int64[ndocs+1] offsets that say which document an item belongs to (text_to_ids_with_offsets_batch_device's id offsets as they
+    are; the items at or past its last entry are left alone), or None: item d belongs to document d.  Ends are inclusive on both sides unless
+    ends_in_exclusive / ends_out_exclusive say otherwise.  A negative entry (a dummy prefix, a plane's fill) gives -1; a position beyond its document
+    gives -1 and BfLastStatus bit 3.  Returns (starts, ends) -- None where none was given; new tensors, or the inputs with in_place -- and with
+    return_doc_units also doc_units int32[ndocs], every document's length in the unit.  Enqueued on torch's current stream (or `stream`); nothing
+    is read back.  Any loaded handle serves; the model is not consulted."""
+    return _charpos_device("byte_to_char_offsets_device", h, d_text, d_doc_off, starts, ends, item_off, unit, ends_in_exclusive, ends_out_exclusive, items_cap, stream,
+                           return_doc_units, in_place)
+
+
+def char_to_byte_offsets_device(h, d_text, d_doc_off, starts=None, ends=None, item_off=None, unit="char", ends_in_exclusive=False, ends_out_exclusive=False, items_cap=None,
+                                stream=None, return_doc_units=False, in_place=False):
+    """The inverse of byte_to_char_offsets_device (CharToByteOffsetsBatchDevice): offsets in code points or UTF-16 code units -> byte offsets, the
+    first byte of the character that holds the unit (an index on a low surrogate gives its character's first byte); an exclusive end one past
+    the document's last unit gives the document's length.  Same arguments and results; doc_units is again the length in the unit."""
+    return _charpos_device("char_to_byte_offsets_device", h, d_text, d_doc_off, starts, ends, item_off, unit, ends_in_exclusive, ends_out_exclusive, items_cap, stream,
+                           return_doc_units, in_place)
+
+
+def _offset_keywords(fn_name, offset_unit, offset_end, return_offsets=True):
+    """checks the offset_unit / offset_end keywords of an encode_* call -> True when the offsets are to be converted"""
+    if offset_unit not in ("byte", "char", "utf16") or offset_end not in ("inclusive", "exclusive"):
+        raise ValueError("%s: offset_unit is 'byte', 'char' or 'utf16' and offset_end 'inclusive' or 'exclusive'" % fn_name)
+    if offset_unit == "byte":
+        if offset_end != "inclusive":
+            raise ValueError("%s: offset_end='exclusive' needs offset_unit 'char' or 'utf16' (byte offsets stay as the tokenizer gives them)" % fn_name)
+        return False
+    if not return_offsets:
+        raise ValueError("%s: offset_unit=%r without return_offsets" % (fn_name, offset_unit))
+    return True
+
+
+def _ragged_offsets_in_units(h, d_text, d_doc_off, d_st, d_en, d_id_off, offset_unit, offset_end):
+    """the tokenizer's ragged starts / ends, converted where they lie: once per token, before the planes are gathered from them"""
+    byte_to_char_offsets_device(h, d_text, d_doc_off, d_st, d_en, d_id_off, unit=offset_unit, ends_out_exclusive=offset_end == "exclusive", in_place=True)
+
+
+def encode_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, stride=0, max_rows_per_doc=1, pad_left=False, return_offsets=False,
+                        offset_unit="byte", offset_end="inclusive"):
     """Text in HBM -> tensors a model takes, nothing on the host: text_to_ids_batch_device and ids_to_rows_batch_device on one stream.
     Every document is tokenised up to the ids its rows can hold (all of them when max_rows_per_doc is 0).
     Returns (rows int32[R, L], mask uint8[R, L], row_doc int32[R], row_offsets int64[ndocs+1]); with return_offsets also
-    (starts int32[R, L], ends int32[R, L]): every token's first and last byte in its document, -1 in cells without a token."""
+    (starts int32[R, L], ends int32[R, L]): every token's first and last byte in its document, -1 in cells without a token.
+    offset_unit "char" / "utf16": the planes count code points / UTF-16 code units instead of bytes (byte_to_char_offsets_device on the ragged
+    offsets, between the tokenizer call and the planes call; the default "byte" is today's call sequence unchanged); offset_end "exclusive": the
+    ends are one past the token's last unit, so that text[s:e] is the token.  "exclusive" needs offset_unit "char" or "utf16": with "byte" it is
+    refused (ValueError) -- byte offsets stay exactly as the tokenizer gives them -- and so is a unit other than "byte" without return_offsets.
+    BfLastStatus afterwards is that of the last call on the handle, the planes call, as before; the conversion's own word (it has nothing to report
+    on the tokenizer's offsets) is cleared by it."""
     body = int(L) - _nspecial(cls_id, sep_id)
     step = body - int(stride)
     if body < 1 or stride < 0 or step < 1 or max_rows_per_doc < 0:
         raise ValueError("encode_batch_device: L leaves no room for ids, or stride / max_rows_per_doc are out of range")
+    convert = _offset_keywords("encode_batch_device", offset_unit, offset_end, return_offsets)
     max_len = min(body + (max_rows_per_doc - 1) * step, 2 ** 31 - 1) if max_rows_per_doc > 0 else 2 ** 31 - 1
     if return_offsets:
         d_ids, d_st, d_en, d_id_off = text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, max_len, unk)
+        if convert:
+            _ragged_offsets_in_units(h, d_text, d_doc_off, d_st, d_en, d_id_off, offset_unit, offset_end)
         rows, mask, seq, _, r_off, (st, en) = ids_to_rows_planes_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, stride, max_rows_per_doc, pad_left,
                                                                                src=[d_st, d_en], fill=[-1, -1])
         return rows, mask, seq, r_off, st, en
@@ -786,18 +871,20 @@ def ids_to_pair_rows_planes_batch_device(h, d_ids_a, d_off_a, d_ids_b, d_off_b, 
 
 
 def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1,
-                              pad_left=False, double_sep=False, return_offsets=False, offsets_a=False):
+                              pad_left=False, double_sep=False, return_offsets=False, offsets_a=False, offset_unit="byte", offset_end="inclusive"):
     """Two texts in HBM -> the tensors a pair model takes, nothing on the host: two text_to_ids_batch_device calls and
     ids_to_pair_rows_batch_device on one stream.  Each side is tokenised up to the ids its rows can hold: T = L - specials for both in mode 1
     (cutting both to T first does not change what longest-first keeps); in mode 0 max_a for A and T + (max_rows_per_pair - 1) * (T - stride)
     for B (all of B when max_rows_per_pair is 0).
     Returns (rows int32[R, L], mask uint8[R, L], type uint8[R, L], row_pair int32[R], row_first_b int32[R], row_offsets int64[npairs+1]); with
     return_offsets also (starts int32[R, L], ends int32[R, L]): first and last byte of every token of B in its text (with offsets_a, of A in
-    its own text too), -1 in every other cell."""
+    its own text too), -1 in every other cell.  offset_unit / offset_end: as in encode_batch_device, every side against its own text
+    (offset_end="exclusive" with offset_unit="byte" is refused there and here)."""
     nsep = 0 if _special(sep_id) < 0 else 3 if double_sep else 2
     T = int(L) - _nspecial(cls_id) - nsep
     if T < 1 or mode not in (0, 1) or (mode == 0 and not (0 <= max_a <= T - 1 and 0 <= stride < T - max_a and max_rows_per_pair >= 0)):
         raise ValueError("encode_pairs_batch_device: L leaves no room for ids, or mode / max_a / stride / max_rows_per_pair are out of range")
+    convert = _offset_keywords("encode_pairs_batch_device", offset_unit, offset_end, return_offsets)
     if mode == 1:
         len_a = len_b = T
     else:
@@ -808,9 +895,13 @@ def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id
         if offsets_a:
             d_ids_a, d_st_a, d_en_a, d_idoff_a = text_to_ids_with_offsets_batch_device(h, d_text_a, d_off_a, len_a, unk)
             src_a = [d_st_a, d_en_a]
+            if convert:
+                _ragged_offsets_in_units(h, d_text_a, d_off_a, d_st_a, d_en_a, d_idoff_a, offset_unit, offset_end)
         else:
             d_ids_a, d_idoff_a = text_to_ids_batch_device(h, d_text_a, d_off_a, len_a, unk)
         d_ids_b, d_st_b, d_en_b, d_idoff_b = text_to_ids_with_offsets_batch_device(h, d_text_b, d_off_b, len_b, unk)
+        if convert:
+            _ragged_offsets_in_units(h, d_text_b, d_off_b, d_st_b, d_en_b, d_idoff_b, offset_unit, offset_end)
         *base, (st, en) = ids_to_pair_rows_planes_batch_device(h, d_ids_a, d_idoff_a, d_ids_b, d_idoff_b, L, cls_id, sep_id, pad_id, mode, max_a, stride,
                                                               max_rows_per_pair, pad_left, double_sep, src_a=src_a, src_b=[d_st_b, d_en_b], fill=[-1, -1])
         return (*base, st, en)
@@ -821,7 +912,7 @@ def encode_pairs_batch_device(h, d_text_a, d_off_a, d_text_b, d_off_b, L, cls_id
 
 
 def encode_qa_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, sep_id, pad_id, max_q, stride, unk=0, double_sep=False, d_ans_first=None,
-                           d_ans_last=None):
+                           d_ans_last=None, offset_unit="byte", offset_end="inclusive", answer_unit="byte"):
     """Questions and contexts in HBM -> extractive-QA inputs, one stream end to end: [cls] question [sep] context window [sep] rows (mode 0,
     the first max_q question ids in every row, every window of the context, `stride` ids shared by neighbours) with the context's byte
     offsets as planes.  Returns (rows, mask, type, row_pair, row_first_b, row_offsets, starts, ends) -- starts / ends int32[R, L]: first and
@@ -830,12 +921,31 @@ def encode_qa_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, s
     row, the [cls] cell (0) in both where the answer is not inside the row's window.  The only read-back is the size query of
     ids_to_pair_rows_batch_device.  BfLastStatus afterwards is that of the LAST call on the handle alone, as always: with answers that is the span
     call, which cleared what the tokenizer and row calls reported (ids or rows dropped, bad ranges); a caller who needs those runs
-    encode_pairs_batch_device(..., return_offsets=True) and rows_span_cells_device itself and reads the status between them."""
+    encode_pairs_batch_device(..., return_offsets=True) and rows_span_cells_device itself and reads the status between them.
+    answer_unit "char" / "utf16": the answers are the first and the last character (code point / UTF-16 code unit), inclusive, of each answer in
+    its context -- a SQuAD answer_start as it stands; they go through char_to_byte_offsets_device (one item per context) in front of the span
+    call, which compares them with byte planes.  offset_unit / offset_end: the planes returned count characters, as in encode_batch_device;
+    with answers they are converted behind the span call (the cells of a context's rows as its items), without answers on the ragged offsets.
+    With answers AND offset_unit "char" / "utf16" the last call on the handle is that conversion of the planes: BfLastStatus afterwards is its own
+    word, and what the span call reported (bit 3) is cleared like everything before it.  offset_end="exclusive" needs offset_unit "char" or
+    "utf16": with "byte" it is refused (ValueError), byte offsets stay as the tokenizer gives them."""
+    convert = _offset_keywords("encode_qa_batch_device", offset_unit, offset_end)
+    if answer_unit not in ("byte", "char", "utf16"):
+        raise ValueError("encode_qa_batch_device: answer_unit is 'byte', 'char' or 'utf16'")
+    if d_ans_first is None or d_ans_last is None:
+        return encode_pairs_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, sep_id, pad_id, unk, 0, max_q, stride, 0, False, double_sep,
+                                         return_offsets=True, offset_unit=offset_unit, offset_end=offset_end)
     out = encode_pairs_batch_device(h, d_text_q, d_off_q, d_text_c, d_off_c, L, cls_id, sep_id, pad_id, unk, 0, max_q, stride, 0, False, double_sep,
                                     return_offsets=True)
-    if d_ans_first is None or d_ans_last is None:
-        return out
-    return (*out, *rows_span_cells_device(h, out[6], out[7], out[3], out[5], d_ans_first, d_ans_last, 0))
+    if answer_unit != "byte":
+        import torch
+        first, last = (t.to(device=d_text_c.device, dtype=torch.int32).contiguous() for t in (d_ans_first, d_ans_last))
+        d_ans_first, d_ans_last = char_to_byte_offsets_device(h, d_text_c, d_off_c, first, last, unit=answer_unit)
+    cells = rows_span_cells_device(h, out[6], out[7], out[3], out[5], d_ans_first, d_ans_last, 0)
+    if convert:
+        byte_to_char_offsets_device(h, d_text_c, d_off_c, out[6].view(-1), out[7].view(-1), out[5] * int(L), unit=offset_unit,
+                                    ends_out_exclusive=offset_end == "exclusive", in_place=True)
+    return (*out, *cells)
 
 
 def encode_pairs_batch(h, docs_a, docs_b, L, cls_id, sep_id, pad_id, unk=0, mode=1, max_a=0, stride=0, max_rows_per_pair=1, pad_left=False, double_sep=False):
@@ -891,16 +1001,21 @@ def ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id=None, sep_id=N
     return (*outs, *seq, nrows, *more)
 
 
-def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None, return_offsets=False):
+def encode_packed_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None, return_offsets=False, offset_unit="byte",
+                               offset_end="inclusive"):
     """Text in HBM -> packed tensors a model takes, nothing on the host: text_to_ids_batch_device (every document tokenised up to the ids
     a row can hold) and ids_to_packed_rows_batch_device on one stream.  Returns what ids_to_packed_rows_batch_device returns; with a
     rows_cap of the caller's nothing is read back.  With return_offsets also (starts int32[R, L], ends int32[R, L]) behind nrows: every
-    token's first and last byte in its document, -1 in cells without a token."""
+    token's first and last byte in its document, -1 in cells without a token.  offset_unit / offset_end: as in encode_batch_device
+    (offset_end="exclusive" with offset_unit="byte" is refused there and here)."""
     body = int(L) - _nspecial(cls_id, sep_id)
     if body < 1:
         raise ValueError("encode_packed_batch_device: L leaves no room for ids")
+    convert = _offset_keywords("encode_packed_batch_device", offset_unit, offset_end, return_offsets)
     if return_offsets:
         d_ids, d_st, d_en, d_id_off = text_to_ids_with_offsets_batch_device(h, d_text, d_doc_off, body, unk)
+        if convert:
+            _ragged_offsets_in_units(h, d_text, d_doc_off, d_st, d_en, d_id_off, offset_unit, offset_end)
         return ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, rows_cap, planes=[d_st, d_en], fill=[-1, -1])
     d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, body, unk)
     return ids_to_packed_rows_batch_device(h, d_ids, d_id_off, L, cls_id, sep_id, pad_id, rows_cap)
@@ -1042,7 +1157,7 @@ def encode_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_id, mas
     planes, so packed=True with whole_word=True raises ValueError: whole-word masking over packed rows is encode_packed_mlm_batch_device.
     rows_cap is the packed call's (None: its one read-back).  max_predictions = P > 0
     caps the predictions of a row and appends (pred_cells int32[R, P], pred_labels int32[R, P], pred_count int32[R]) behind labels, in all
-    three forms (rows_mlm_mask_device)."""
+    three forms (rows_mlm_mask_device).  The offset planes stay in bytes (there is no offset_unit here): the whole-word rule is byte adjacency."""
     if packed and whole_word:
         raise ValueError("encode_mlm_batch_device: packed rows have no offset planes, so no whole-word masking")
     if special_ids is None:
@@ -1068,7 +1183,7 @@ def encode_packed_mlm_batch_device(h, d_text, d_doc_off, L, cls_id, sep_id, pad_
     is predicted); the last three with max_predictions = P > 0 (rows_mlm_mask_device).  The remaining keywords are encode_mlm_batch_device's.
     whole_word=False masks token by token (the planes are returned all the same).  With whole_word=True a row needs cls_id or sep_id: the
     special between two sequences is what keeps a unit from joining the last token of one sequence to the first token of the next when their
-    byte offsets happen to be adjacent; without either, ValueError."""
+    byte offsets happen to be adjacent; without either, ValueError.  The planes stay in bytes (no offset_unit): the whole-word rule is byte adjacency."""
     if whole_word and _nspecial(cls_id, sep_id) == 0:
         raise ValueError("encode_packed_mlm_batch_device: whole-word masking over packed rows needs cls_id or sep_id (units could join across sequences)")
     if special_ids is None:

@@ -41,9 +41,9 @@ def hipcc():
 
 
 def build_product(force=False):
-    """the product: eleven translation units compiled side by side (the two large kernel files are most of the time), then linked"""
+    """the product: twelve translation units compiled side by side (the two large kernel files are most of the time), then linked"""
     names = ("bf_kernels.hip", "bf_kernels_sp.hip", "bf_kernels_w2h.hip", "bf_kernels_rows.hip", "bf_kernels_pairs.hip", "bf_kernels_packed.hip", "bf_kernels_stream.hip",
-             "bf_kernels_mlm.hip", "bf_kernels_denoise.hip", "bf_capi.cpp", "bf_model.cpp")
+             "bf_kernels_mlm.hip", "bf_kernels_denoise.hip", "bf_kernels_charpos.hip", "bf_capi.cpp", "bf_model.cpp")
     srcs = [os.path.join(CSRC, f) for f in names]
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [
         os.path.join(ROOT, "include", "blingfiretokdll_amd.h"), os.path.join(CSRC, "exports.map"), os.path.join(ROOT, "models", "wbd.bin"), os.path.join(ROOT, "models", "sbd.bin")]

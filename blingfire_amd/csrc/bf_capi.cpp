@@ -115,8 +115,9 @@ struct PinBuf {
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
 //                            calls on one handle).  Nobody keeps a list of entry points here: begin_launch() is called by the drivers they all go
 //                            through -- run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, run_packed_device, run_stream_device, run_i2t_host and IdsToTextBatchDevice -- and by rows_call(), the
-//                            prologue of every Rows...BatchDevice entry point (span cells, MLM mask, MLM predictions, denoise).  The host forms reach
+//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_i2t_host and
+//                            IdsToTextBatchDevice -- and by rows_call(), the prologue of every Rows...BatchDevice entry point (span cells, MLM mask,
+//                            MLM predictions, denoise).  The host forms reach
 //                            it through the Device drivers they call.  The fill passes of the two-pass calls keep the size pass's words.
 //                            NormalizeSpacesBatch and TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for
 //                            its status, and their kernels use none of the words: they clear nothing.
@@ -216,6 +217,7 @@ struct Handle {
     DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch / IdsToPairRowsBatch: sequence (pair) and first id of every row, where the caller takes neither
     DevBuf w_plsrc[2][ROWS_MAX_PLANES], w_plout[ROWS_MAX_PLANES]; // IdsToRowsPlanesBatch / IdsToPairRowsPlanesBatch, host forms: the staged companion arrays of each side, the planes
     DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
+    DevBuf w_cplead, w_cpfour, w_cpcnt, w_cpP;                   // Byte / CharToByteOffsetsBatchDevice (bf_kernels.h CharposParams): the two masks, the weights, P -- 28 bytes per 64 bytes of text
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -1704,6 +1706,53 @@ int run_stream_device(Handle *h, const StreamSpec &spec, const int32_t *d_ids, i
     return hip_ok(hipGetLastError(), "IdsToStreamRows kernels") ? 0 : BF_E_DEVICE;
 }
 
+// The index of the offset conversions for a text of total_bytes bytes: two masks, the weight and P per 64-byte chunk, and the scan's block sums
+// (w_bsums is otherwise sized by documents: here by chunks)
+bool reserve_charpos_workspaces(Handle *h, int64_t total_bytes)
+{
+    const size_t n = (size_t)charpos_nchunks(total_bytes) + 2;
+    return h->w_cplead.reserve(n * 8) && h->w_cpfour.reserve(n * 8) && h->w_cpcnt.reserve(n * 4) && h->w_cpP.reserve(n * 8) &&
+           h->w_bsums.reserve((size_t)(scan_nblocks((int64_t)n) + 1) * 8);
+}
+
+// ByteToCharOffsetsBatchDevice (dir = CHARPOS_FWD) and CharToByteOffsetsBatchDevice (CHARPOS_INV) on device buffers (bf_kernels_charpos.hip): the
+// index pass over the text, the scan of the chunk weights, the per-document kernel (bad ranges, U_d), the per-item kernel.  The launches depend
+// on the sizes and on which outputs are taken, never on the data.  A refused argument touches neither the device nor the status word.
+int run_charpos_device(Handle *h, int dir, const char *d_text, const int64_t *d_doc_off, int64_t ndocs, int64_t total_bytes, const int64_t *d_item_off, int64_t items_cap,
+                       const int32_t *d_starts, const int32_t *d_ends, int unit, int flags, int32_t *d_starts_out, int32_t *d_ends_out, int32_t *d_doc_units, hipStream_t s)
+{
+    if ((unit != CHARPOS_UNIT_CHAR && unit != CHARPOS_UNIT_UTF16) || (flags & ~CHARPOS_FLAGS) != 0 || ndocs < 0 || total_bytes < 0 || items_cap < 0) return BF_E_ARG;
+    if ((d_starts != nullptr) != (d_starts_out != nullptr) || (d_ends != nullptr) != (d_ends_out != nullptr)) return BF_E_ARG;
+    if (!d_doc_off || (total_bytes > 0 && !d_text)) return BF_E_ARG;
+    const int64_t items_bound = ndocs == 0 ? 0 : d_item_off ? items_cap : (items_cap < ndocs ? items_cap : ndocs);
+    const bool want_items = d_starts_out || d_ends_out;
+    if (items_bound > 0 && !want_items && !d_doc_units) return BF_E_ARG;
+    if (!reserve_charpos_workspaces(h, total_bytes)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    CharposParams p;
+    p.text = (const uint8_t *)d_text; p.total_bytes = total_bytes; p.nchunks = charpos_nchunks(total_bytes);
+    p.lead = h->w_cplead.as<uint64_t>(); p.four = unit == CHARPOS_UNIT_UTF16 ? h->w_cpfour.as<uint64_t>() : nullptr;
+    p.counts = h->w_cpcnt.as<int32_t>(); p.P = h->w_cpP.as<int64_t>();
+    p.doc_off = d_doc_off; p.ndocs = ndocs; p.item_off = d_item_off; p.items_cap = items_cap;
+    p.starts = d_starts; p.ends = d_ends; p.starts_out = d_starts_out; p.ends_out = d_ends_out; p.doc_units = d_doc_units;
+    p.dir = dir; p.flags = flags; p.status = &h->misc()->status;
+    const bool index = ndocs > 0 && (d_doc_units || (want_items && items_bound > 0));
+    // the events BfLastKernelMs reads: [0] the index pass, [1] and [5] nothing, [2] the scan, [3] the per-document and the per-item kernel
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (index) launch_char_index(p, s);
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    if (index) launch_scan(ScanParams{p.counts, p.nchunks, p.P, h->w_bsums.as<int64_t>(), scan_nblocks(p.nchunks)}, s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    launch_char_docs(p, s);
+    if (want_items) launch_char_items(p, items_bound, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), dir == CHARPOS_FWD ? "ByteToCharOffsets kernels" : "CharToByteOffsets kernels") ? 0 : BF_E_DEVICE;
+}
+
 // IdsToStreamRowsBatch on host buffers: the ids through stage_ragged, then count_fill_host, whose size pass also answers the per-sequence outputs
 int64_t run_stream_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const StreamSpec &spec, int32_t *rows_out, int32_t *seg_out, int32_t *pos_out,
                         int32_t *labels_out, int32_t *first_seq_out, int32_t *first_pos_out, int64_t rows_cap, int32_t *seq_row_out, int32_t *seq_col_out)
@@ -2606,6 +2655,31 @@ int64_t IdsToStreamRowsBatch(void *p, const int32_t *ids, const int64_t *id_offs
     return run_stream_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, labels_out, row_first_seq_out, row_first_pos_out, rows_cap, seq_row_out, seq_col_out);
 }
 
+/* ---- additive: byte offsets <-> code points / UTF-16 code units of text that is on the device (bf_charpos.h; any live handle: the model is not consulted) */
+int ByteToCharOffsetsBatchDevice(void *p, const char *d_text, const int64_t *d_doc_offsets, int64_t ndocs, int64_t total_bytes, const int64_t *d_item_offsets,
+                                 int64_t items_cap, const int32_t *d_starts, const int32_t *d_ends, int unit, int flags, int32_t *d_starts_out, int32_t *d_ends_out,
+                                 int32_t *d_doc_units_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_charpos_device(h, CHARPOS_FWD, d_text, d_doc_offsets, ndocs, total_bytes, d_item_offsets, items_cap, d_starts, d_ends, unit, flags, d_starts_out, d_ends_out,
+                              d_doc_units_out, (hipStream_t)stream);
+}
+
+int CharToByteOffsetsBatchDevice(void *p, const char *d_text, const int64_t *d_doc_offsets, int64_t ndocs, int64_t total_bytes, const int64_t *d_item_offsets,
+                                 int64_t items_cap, const int32_t *d_starts, const int32_t *d_ends, int unit, int flags, int32_t *d_starts_out, int32_t *d_ends_out,
+                                 int32_t *d_doc_units_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_charpos_device(h, CHARPOS_INV, d_text, d_doc_offsets, ndocs, total_bytes, d_item_offsets, items_cap, d_starts, d_ends, unit, flags, d_starts_out, d_ends_out,
+                              d_doc_units_out, (hipStream_t)stream);
+}
+
 /* ---- additive: FADictInterpreter_t<int>::GetInfo for many keys at once over the model's [pos-dict] */
 int DictGetInfoBatchDevice(void *p, const int32_t *d_keys, const int64_t *d_key_offsets, int64_t nkeys, int32_t *d_ret_out, int32_t *d_info_ids_out,
                            int32_t *d_values_out, int64_t values_cap, int64_t *d_value_offsets_out, void *stream)
@@ -2704,7 +2778,8 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     if (!reserve_rows_workspaces(h, max_docs)) return BF_E_DEVICE;                                   // IdsToRowsBatchDevice, any handle: documents = sequences
     if (!reserve_packed_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToPackedRowsBatchDevice, any handle
-    if (h->m.kind == KIND_I2W) return 0;                                                             // (nothing else of such a handle takes batches of documents)
+    if (!reserve_charpos_workspaces(h, max_bytes)) return BF_E_DEVICE;                               // Byte / CharToByteOffsetsBatchDevice, any handle: sized by the text alone
+    if (h->m.kind == KIND_I2W) return 0;                                                            // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words
     if (h->m.kind == KIND_W2H) return 0;
     // both forms of the WordPiece path: the wave program's workspaces and (words = 1 skips use_wave()'s early return) the class stream and flags of

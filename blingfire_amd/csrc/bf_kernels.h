@@ -15,6 +15,7 @@
 #include "bf_stream.h"
 #include "bf_mlm.h"
 #include "bf_denoise.h"
+#include "bf_charpos.h"
 #include "bf_variant.h"
 
 namespace bfa {
@@ -384,6 +385,24 @@ struct StreamParams {
 void launch_stream_widths(const StreamParams &p, hipStream_t s);                // lane per sequence: widths, status bit 3
 void launch_stream_seq(const StreamParams &p, hipStream_t s);                   // behind the scan: seq_row, seq_col, nrows, status bit 0
 void launch_stream_fill(const StreamParams &p, int64_t rows_bound, hipStream_t s);      // the four planes and the row-first pair, tile by tile
+// ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice (additive; bf_charpos.h has the lane code, bf_kernels_charpos.hip the kernels): the
+// index over 64-byte chunks of the text (masks, weights, their scan P) and the per-item conversion.  unit 0: `four` is NULL.
+struct CharposParams {
+    const uint8_t *text; int64_t total_bytes, nchunks;
+    uint64_t *lead, *four;       // [nchunks] each: the bytes with a weight; the bytes >= 0xF0 (UTF-16 alone)
+    int32_t *counts;             // [nchunks] weight of a chunk, scanned into P
+    int64_t *P;                  // [nchunks + 1]
+    const int64_t *doc_off; int64_t ndocs;
+    const int64_t *item_off;     // [ndocs + 1], or NULL: item d belongs to document d
+    int64_t items_cap;
+    const int32_t *starts, *ends; int32_t *starts_out, *ends_out;      // either pair may be NULL
+    int32_t *doc_units;          // [ndocs] U_d, may be NULL
+    int dir, flags;              // CHARPOS_FWD / CHARPOS_INV; CHARPOS_ENDS_*
+    int *status;
+};
+void launch_char_index(const CharposParams &p, hipStream_t s);                  // the pass over the text: masks and weights
+void launch_char_docs(const CharposParams &p, hipStream_t s);                   // behind the scan: status bit 3 of a bad range, U_d
+void launch_char_items(const CharposParams &p, int64_t items_bound, hipStream_t s);     // k_char_fwd / k_char_inv, a lane per item
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

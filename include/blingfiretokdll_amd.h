@@ -639,6 +639,45 @@ BF_API int TextToIdsWithOffsetsBatchDevice(void *ModelPtr, const char *d_text, c
                                     int64_t total_bytes, int32_t *d_ids_out, int32_t *d_starts_out, int32_t *d_ends_out,
                                     int64_t cap, int64_t *d_id_offsets_out, int max_ids_per_doc, int unk, void *stream);
 
+/* additive: the byte offsets this library produces and takes (the starts / ends above, the offset planes of the row calls, the spans of
+ * RowsSpanCellsBatchDevice) <-> offsets in code points (what a Python str indexes by) or UTF-16 code units (C#, JS), on the device.
+ *
+ * Definitions.  Document d is text[doc_off[d] .. doc_off[d+1]) and has n_d bytes; a range outside [0, total_bytes] or with decreasing offsets
+ * reads as empty and sets BfLastStatus bit 3, as in every Device call.  The weight of a byte value b:
+ *   unit = 0 (code points):        0 if (b & 0xC0) == 0x80, else 1;
+ *   unit = 1 (UTF-16 code units):  0 if (b & 0xC0) == 0x80; 2 if b >= 0xF0; else 1.
+ * The rule is on bytes alone, so it is defined for byte-level models (gpt2.bin) whose documents need not be valid UTF-8; for valid UTF-8 it
+ * equals what len(doc[:i].decode()), or the UTF-16 length of the same prefix, gives.
+ *   C_d(i), 0 <= i <= n_d:  the sum of the weights of the first i bytes of the document.  U_d = C_d(n_d).
+ *   B_d(k), 0 <= k <= U_d:  n_d if k == U_d, else min { i : C_d(i+1) > k } -- the first byte of the character that holds unit k (an index
+ *                           that points at a low surrogate maps to its character's first byte).
+ * Items.  d_item_offsets is int64[ndocs+1], non-decreasing from 0 (the tokenizer's d_id_offsets_out as it stands): item i belongs to the document
+ * d with off[d] <= i < off[d+1].  NULL: item d belongs to document d (one span per document, the QA form).  Items at or past
+ * min(items_cap, off[ndocs]) are neither read nor written, so chaining behind a tokenizer call that overflowed its ids_cap is safe.  (An item
+ * no document holds -- offsets that do not start at 0 -- gives -1 and bit 3.)
+ * Ends.  flags bit 0: the input ends are exclusive (default inclusive, like the tokenizer's); flags bit 1: the output ends are exclusive (the
+ * offset_mapping convention of other tokenizer libraries).  With x = e + 1 for an inclusive input end and x = e otherwise, out = F(x), minus 1
+ * when the output is inclusive.  Starts: out = F(s).  F is C_d in ByteToCharOffsetsBatchDevice and B_d in CharToByteOffsetsBatchDevice.  A negative
+ * input (the dummy prefix's -1, a plane's fill, "no answer") gives -1 and sets no status bit.  A non-negative argument of F beyond n_d
+ * (respectively U_d) gives -1 and sets bit 3; so does an answer beyond INT32_MAX (a document of more than 2 GiB).
+ * Either input / output pair may be NULL; d_doc_units_out ([ndocs], U_d; saturates at INT32_MAX) may be NULL, and it alone is a legal call.
+ * d_starts_out == d_starts and d_ends_out == d_ends (in place) are allowed: a lane reads only its own element before it writes it.
+ * BF_E_ARG: a unit other than 0 or 1, a flag bit above 1, negative sizes, an input without its output or an output without its input, a NULL
+ * d_text with total_bytes > 0, a NULL d_doc_offsets, every output NULL with items to do, a NULL ModelPtr.  Any live handle serves: it lends its
+ * device, workspaces and status word; the model is not consulted.
+ * Like every batch call it clears the status word first, enqueues on `stream`, does not synchronise, reads nothing back and returns 0 or
+ * BF_E_*.  The kernels it launches depend on the sizes and on which outputs are taken, never on the data.  The workspace is 28 bytes per 64 bytes
+ * of text (an index over 64-byte chunks of the text buffer: two masks, a count and its 64-bit prefix sum; the one pass over the text); after
+ * BfReserve(h, ..., max_bytes >= total_bytes, ...) the calls allocate nothing.  Every pointer needs only the natural alignment of its type;
+ * nothing in front of d_text or at or behind d_text + total_bytes is looked at.
+ * Not here: host-buffer forms (on the host this is a cumulative sum), grapheme clusters, validation of the UTF-8. */
+BF_API int ByteToCharOffsetsBatchDevice(void *ModelPtr, const char *d_text, const int64_t *d_doc_offsets, int64_t ndocs, int64_t total_bytes,
+                                        const int64_t *d_item_offsets, int64_t items_cap, const int32_t *d_starts, const int32_t *d_ends, int unit, int flags,
+                                        int32_t *d_starts_out, int32_t *d_ends_out, int32_t *d_doc_units_out, void *stream);
+BF_API int CharToByteOffsetsBatchDevice(void *ModelPtr, const char *d_text, const int64_t *d_doc_offsets, int64_t ndocs, int64_t total_bytes,
+                                        const int64_t *d_item_offsets, int64_t items_cap, const int32_t *d_starts, const int32_t *d_ends, int unit, int flags,
+                                        int32_t *d_starts_out, int32_t *d_ends_out, int32_t *d_doc_units_out, void *stream);
+
 /* additive: the reference's dictionary interpreter, FADictInterpreter_t<int>::GetInfo
  * (blingfireclient.library/inc/FADictInterpreter_t.h:31-66,334-390; FAMphInterpretTools_t.h:97-122), for many keys at once over the
  * [pos-dict] of a tokenizer model (gpt2.bin, xlm_roberta_base.bin, ...) -- the same Mealy automaton / K2I / I2Info the segmenters use.
@@ -663,13 +702,14 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * tokenise segment alone.  After IdsToPackedRowsBatchDevice: [0] widths + scan, [1] next + the doubling rounds, [2] the scan of the marks and the
  * per-row / per-sequence outputs, [3] the fill of the planes, [4] total, [5] the doubling rounds alone.  After IdsToPackedRowsPlanesBatchDevice with a plane taken, [3] covers the
  * fill and the kernel of the companion planes behind it.  After IdsToStreamRowsBatchDevice: [0] widths + scan, [2] the per-sequence outputs and
- * the counts, [3] the fill, [4] total ([1] and [5] are 0).
+ * the counts, [3] the fill, [4] total ([1] and [5] are 0).  After ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice: [0] the index pass
+ * over the text, [2] the scan of the chunk counts, [3] the per-document and the per-item kernel, [4] total ([1] and [5] are 0).
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
- * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, span-cell, MLM and denoise calls, IdsToText, DictGetInfo and
- * WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
+ * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
+ * and CharToByteOffsetsBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
@@ -678,7 +718,7 @@ BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
  * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
  * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
- * [0, ids_len]; the span cells: a row whose item is out of range).  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
+ * [0, ids_len]; the span cells: a row whose item is out of range; the offset conversions: also a position beyond its document).  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
  * terminate (a skipped start position left without an arc, FATokenSegmentationTools_1best_bpe_t.h:299-313) got 0 ids; bit 6 (64) = a
  * BPE document's arcs did not fit the pool and it got 0 ids (only the ...BatchDevice forms: the host-buffer calls grow the pool and
  * run again; BfSetBpePoolBytes). */
@@ -701,6 +741,10 @@ BF_API int BfModelKind(void *ModelPtr);
  * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
  * bound).  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
  * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
+ * Every kind of handle also gets the index of ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice, sized from max_bytes alone (28 bytes per
+ * 64 bytes of text, and the scan's block sums for that many chunks): after that the two calls allocate nothing, the first one included.
+ * That is 0.44 bytes of HBM per byte of max_bytes on EVERY reserved handle, whether it ever converts an offset or not (about 2.2 GB for a
+ * reserve of 5.1 GB of text): count it when sizing HBM.  A handle that is not reserved allocates the index in its first conversion call.
  * A WordPiece handle also gets the buffers of TextToWordsBatchDevice / TextToSentencesBatchDevice (12 bytes per byte of text and 8 per
  * document); a handle with a [pos-dict] gets its lookup tables uploaded and the workspaces of DictGetInfoBatchDevice for max_docs keys; a
  * handle with [w2h] those of WordHyphenationBatchDevice for max_docs words.
