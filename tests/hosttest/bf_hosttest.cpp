@@ -85,6 +85,17 @@ void bft_lookup_hist(unsigned long long *out, int n, int reset) { for (int i = 0
 long bft_table_len(void *hv) { return (long)((Handle *)hv)->m.wbd_t2.size(); }
 int bft_trie_depth(void *hv) { return ((Handle *)hv)->m.trie_max_depth; }
 int bft_kind(void *hv) { return ((Handle *)hv)->m.kind; }
+// what bf_capi.cpp's reserve_* formulas take from the model (tests/big_offset_cases.py states them per model): out[0] = stream elements per byte of
+// the _sp slots (2 with a charmap), [1] = bytes of a Unigram record (4 where the lane program applies: bf_capi.cpp uni_lane_ok), [2] = the BPE wave
+// program applies, [3] = the flat program applies
+void bft_reserve_facts(void *hv, int *out)
+{
+    const Model &m = ((Handle *)hv)->m;
+    out[0] = m.dict_has_charmap ? 2 : 1;
+    out[1] = (m.trie_max_depth > 0 && m.trie_max_depth <= 32 && m.seg_info.size() <= (size_t)UNI_MAX_ID && m.max_info_id < 0x7fffffff) ? 4 : 16;
+    out[2] = m.bpe_wave_ok ? 1 : 0;
+    out[3] = (m.wave_ok && m.flat_ok) ? 1 : 0;
+}
 
 // sizes for reports: out[0]=wbd states, [1]=wbd transitions, [2]=wbd table entries, [3]=wbd classes,
 // [4..7] same for dict, [8]=trie depth
