@@ -120,6 +120,27 @@ def build_test_infra(force=False):
         _run(["make", "-C", odir, "ref", "REF=" + REF_DIR])
 
 
+def build_unioffs_san(out_dir):
+    """tests/hosttest/bf_unioffstest.cpp as a stand-alone program under the address and undefined-behaviour sanitizers (the offsets instance of the
+    Unigram cut form in the host driver, against the oracle linked into it): `bf_unioffs MODEL...`, exit status 0 = no difference, no report"""
+    flags = ["-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan"]
+    ht = os.path.join(ROOT, "tests", "hosttest")
+    units = [(["g++", "-std=c++17", "-DBF_UNIOFFS_MAIN"], os.path.join(ht, "bf_unioffstest.cpp")), (["g++", "-std=c++17"], os.path.join(ht, "bf_hosttest.cpp")),
+             (["g++", "-std=c++17"], os.path.join(CSRC, "bf_model.cpp")), (["gcc", "-std=c99"], os.path.join(ROOT, "oracle", "bf_oracle.c"))]
+    objs, procs = [], []
+    for cc, src in units:
+        obj = os.path.join(out_dir, os.path.basename(src) + ".o")
+        cmd = cc + flags + ["-c", src, "-o", obj]
+        print("+", " ".join(cmd), flush=True)
+        objs.append(obj); procs.append((cmd, subprocess.Popen(cmd)))
+    for cmd, pr in procs:
+        if pr.wait() != 0:
+            raise subprocess.CalledProcessError(pr.returncode, cmd)
+    exe = os.path.join(out_dir, "bf_unioffs")
+    _run(["g++"] + flags + objs + ["-o", exe])
+    return exe
+
+
 def build_all(force=False):
     build_product(force)
     build_test_infra(force)

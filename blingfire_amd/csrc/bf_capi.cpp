@@ -758,9 +758,9 @@ StepTail enqueue_sp(const Step &st)
     const SegKnobs sk = seg_knobs(h->variant);
     sg.tune = sk.tune;
     sg.lane_ok = uni_lane_ok(m) ? 1 : 0;
-    // ids only: the cut form (bf_seg.h UniCut; cut_off: the forward / backward kernels of round 4, which the offsets API still takes)
+    // the cut form (bf_seg.h UniCut), ids and offsets alike; cut_off: the forward / backward kernels of round 4
     const bool uni_lane = m.kind == KIND_UNIGRAM && sg.lane_ok;
-    sg.uni_cut = (uni_lane && !want_off && !sk.cut_off) ? 1 : 0;
+    sg.uni_cut = (uni_lane && !sk.cut_off) ? 1 : 0;
     h->last_uni_cut = sg.uni_cut != 0;
     sg.perm = h->w_perm.as<int32_t>(); sg.hist = h->w_hist.as<unsigned int>();
     // the cut form leaves tokens, not ids (k_uni_ids is its compaction); the lane form writes its ids right-aligned (their first index: w_narcs)
@@ -787,6 +787,7 @@ int finish_step(const Step &st, const StepTail &t)
         // the ids of the cut form's tokens go straight to the caller's array
         UniIdsParams up{b, h->t_dict.as<uint64_t>(), m.dict.initial_base, h->t_segid.as<int32_t>(), h->w_cls.as<uint16_t>(), h->w_nchars.as<int32_t>(), t.slot_mul,
                         h->w_tmp.as<int32_t>(), h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, st.unk, m.id_offset, b.status};
+        if (st.want_off) { up.spans = h->w_span.as<int32_t>(); up.src_off = h->w_srcoff.as<int32_t>(); up.starts_out = st.starts; up.ends_out = st.ends; }
         if (b.ndocs > 0) launch_uni_ids(up, s);
     } else if (t.kind == StepTail::BPE_HOME) {
         BpeHomeParams hp{b, h->w_tmp.as<int32_t>(), h->w_nchars.as<int32_t>(), h->w_bwflags.as<int32_t>(), t.slot_mul, h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, st.max_ids, b.status};
@@ -3036,8 +3037,8 @@ const char *BfStepKernels(void *p)
         if (use_wave(h, false, 0)) return "prep: - | tokenise: k_wp_wave | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids (offsets: k_compact_text)";
         return "prep: k_prep_wp_flat, k_prep_wp_docs | tokenise: k_lex_wp_plain / k_lex_wp_flat | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids (offsets: k_compact)";
     case KIND_UNIGRAM:
-        if (h->last_uni_cut) return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_uni_cut | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_uni_ids";
-        return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_seg_unigram_lane, k_uni_back | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
+        if (h->last_uni_cut) return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_uni_cut | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_uni_ids (offsets: the spans instances of both)";
+        return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_seg_unigram_lane, k_uni_back | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids (offsets: k_compact)";
     case KIND_I2W: case KIND_W2H: return "";
     default:
         if (use_bpe_wave(h, false)) return bpe_wave_home(bpe_wave_knobs(h->variant).tune, EXPERIMENTS_BUILD) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather"

@@ -120,7 +120,7 @@ struct SpSegParams {
     int32_t *narcs;             // [ndocs] BPE arc count per document (-1 = capacity exceeded); Unigram: first id index within the slot
     int trie_depth;             // longest dictionary entry (bounds every arc length)
     int lane_ok;                // Unigram: the model fits the lane program (bf_seg.h UniLane: entries <= 32 symbols, ids < 2^20 - 2)
-    int uni_cut = 0;            // Unigram: the cut form (bf_seg.h UniCut; ids only): tokens leave as words (bf_seg.h: key / symbols to walk / unknown), left-aligned in the slot -> k_uni_ids
+    int uni_cut = 0;            // Unigram: the cut form (bf_seg.h UniCut): tokens leave as words (bf_seg.h: key / symbols to walk / unknown), left-aligned in the slot -> k_uni_ids; with span_tmp set, one span word per token beside them
     int64_t bm_words;           // BPE apply: words per bitmap (the two bitmaps live in the `tos` buffer)
     int32_t *fb_list; unsigned int *fb_count;   // BPE: documents k_bpe_fused hands to the full path (set by launch_seg_sp)
     uint8_t *big_pool; unsigned long long big_cap; unsigned long long *big_used, *big_need;   // BPE: pool of the documents whose arcs exceed the per-document reserve (k_bpe_seg); *big_need: bytes that did not fit
@@ -150,6 +150,8 @@ struct UniIdsParams {
     const uint16_t *stream; const int32_t *lens; int slot_mul;
     const int32_t *toks; const int32_t *counts; const int64_t *id_off;
     int32_t *ids_out; int64_t ids_cap; int unk, id_offset; int *status;
+    // the offsets call (all four or none): the span words of UniCut's offsets instance, k_prep_sp8's element -> source byte stream, the caller's arrays
+    const int32_t *spans = nullptr; const int32_t *src_off = nullptr; int32_t *starts_out = nullptr, *ends_out = nullptr;
 };
 void launch_uni_ids(const UniIdsParams &p, hipStream_t s);
 

@@ -1412,6 +1412,9 @@ __global__ __launch_bounds__(256) void k_uni_back(SpSegParams p)
 // per wave, sixteen waves per CU (the lane program above: 12 KB, thirteen) -- and the kernel's time is latency x waves (bf_seg.h).
 // Emission is a phase the whole wave enters together -- when a lane has finished its document or filled its ring, and every `period` trips --
 // so that its loops run with most lanes active instead of a few lanes every trip.
+// SPANS: the offsets instance -- UniCut's span words (one per token: its last stream position, bf_seg.h) go to the same index of the span
+// staging array as the token words go to in the id staging array; the two arrays are a wave-uniform byte distance apart, so the instance holds no
+// second pointer per lane.  Same launch shape, rings and waves per CU.
 struct RingCut {
     double *sc; uint8_t *rc; int smask, rmask, sn;
     __device__ __forceinline__ double score(int pos) const { return sc[(pos & smask) * 64]; }
@@ -1422,7 +1425,7 @@ struct RingCut {
     __device__ __forceinline__ void fill(double v) { for (int k = 0; k < sn; ++k) sc[k * 64] = v; }      // (a record slot is written before it is read: bf_seg.h)
 };
 
-template <int UNROLL>
+template <int UNROLL, bool SPANS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_uni_cut(SpSegParams p, int ring_n, int W, unsigned period_mask, int quick)
 {
     extern __shared__ double seg_ring[];            // [ring_n][64] scores, then [W][64] record bytes
@@ -1430,7 +1433,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const int lane = lane_id();
     RingCut ring{seg_ring + lane, (uint8_t *)(seg_ring + (size_t)ring_n * 64) + lane, ring_n - 1, W - 1, ring_n};
     ClsWinS cls_at; cls_at.init(p.stream, 0);
-    UniCut<ClsWinS, RingCut> uc(p.S, cls_at, ring);
+    UniCut<ClsWinS, RingCut, SPANS> uc(p.S, cls_at, ring);
     uc.L = 0; uc.depth = p.trie_depth; uc.W = W; uc.start = uc.i = uc.sum = 0; uc.state = 0; uc.unknown = true; uc.pend = false; uc.walking = false; uc.prev = 0; uc.pend_i = 0;
     uc.pend_score = 0; uc.unk_run = 0; uc.reach = -1; uc.rk = 0; uc.rs = 0; uc.ck = 0; uc.cs = -1; uc.cut0 = 0; uc.lastcut = -1; uc.ring_lo = 0; uc.nout = 0; uc.tok_align = 0;
     int mode = M_NEED;
@@ -1472,7 +1475,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 if (k + 3 < max_ids) *(uint4 *)(toks + k) = make_uint4(a, b, c, d);
                 else { (*this)(k, a); (*this)(k + 1, b); (*this)(k + 2, c); (*this)(k + 3, d); }
             }
-        } put{toks, p.max_ids};
+        };
+        struct TokSpanPut : TokPut {
+            intptr_t span_delta;      // bytes from the id staging array to the span staging array (both 256-byte aligned: a group of four is aligned in both)
+            __device__ __forceinline__ TokSpanPut(int32_t *t, int mx, intptr_t sd) : TokPut{t, mx}, span_delta(sd) {}
+            __device__ __forceinline__ uint32_t *sp(int k) const { return (uint32_t *)((char *)(this->toks + k) + span_delta); }
+            __device__ __forceinline__ void span(int k, uint32_t v) const { if (k < this->max_ids) *sp(k) = v; }
+            __device__ __forceinline__ void span_quad(int k, uint32_t a, uint32_t b, uint32_t c, uint32_t d) const
+            {
+                if (k + 3 < this->max_ids) *(uint4 *)sp(k) = make_uint4(a, b, c, d);
+                else { span(k, a); span(k + 1, b); span(k + 2, c); span(k + 3, d); }
+            }
+        };
+        auto make_put = [&]() { if constexpr (SPANS) return TokSpanPut(toks, p.max_ids, (intptr_t)((uintptr_t)p.span_tmp - (uintptr_t)p.ids_tmp)); else return TokPut{toks, p.max_ids}; };
+        auto put = make_put();
         // a trip: UNROLL transitions of the lane's walk (a walk that is over waits), then -- once, for all the lanes whose walk is over -- the
         // end of the start position; the short way out for the chunks that are complete
         const bool can = mode == M_WALK && uc.room(UNROLL);
@@ -1506,9 +1522,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 // A wave takes 64 consecutive documents (count, slot, place: one document per lane, handed round with readlane as in k_compact_ids) and their
 // tokens 64 per trip: keys and unknowns are answered at once (64 independent look-ups); the words to walk go to a list in LDS and are walked
 // 128 at a time, two per lane, whatever documents they come from -- every lane of a walk has tokens, and a walk's symbols are read eight per load.
+// OFFS: the offsets instance.  The first pass also turns every token's span word (and its neighbour's: bf_seg.h uni_token_span) into the byte
+// offsets of the caller's starts / ends arrays, exactly as k_compact does from the lane program's (from, to): the source-offset stream at both
+// stream positions, and the first byte of the last character for its UTF-8 size (the end is inclusive and covers that character whole).  Walked
+// words get theirs here too, so the list in LDS carries nothing more.  Nothing at or beyond ids_cap, like the ids.
 struct __attribute__((packed, aligned(2))) Sym8 { uint32_t x, y, z, w; };      // eight stream elements at a 2-byte aligned address: one 16-byte load
 constexpr int UNI_WM = 2;                         // words a lane walks at a time (independent chains: the dependent gathers of one hide behind the other's)
 constexpr int UNI_WL = 64 * UNI_WM * 2;           // the wave's list of words to walk (a ring: a batch waits while up to 64 more arrive)
+template <bool OFFS>
 __global__ __launch_bounds__(256) void k_uni_ids(UniIdsParams p)
 {
     __shared__ int64_t wl_src[4][UNI_WL], wl_out[4][UNI_WL];
@@ -1553,10 +1574,11 @@ __global__ __launch_bounds__(256) void k_uni_ids(UniIdsParams p)
     };
     for (int64_t base = wave0 * 64; base < p.b.ndocs; base += nwaves * 64) {
         const int64_t d = base + lane;
-        int c = 0; int64_t slot = 0, o = 0;
+        int c = 0; int64_t slot = 0, o = 0, tb = 0;
         if (d < p.b.ndocs) {
             c = p.counts[d];
             slot = sp_slot(p.b.doc_off[d], d, p.slot_mul);
+            if constexpr (OFFS) tb = p.b.doc_off[d];
             o = p.id_off[d];
             if (o + c > p.ids_cap) { over = true; c = o < p.ids_cap ? (int)(p.ids_cap - o) : 0; }
         }
@@ -1566,6 +1588,8 @@ __global__ __launch_bounds__(256) void k_uni_ids(UniIdsParams p)
             if (ck <= 0) continue;
             const int64_t sk = wv::bcast(slot, k), ok = wv::bcast(o, k);
             const uint32_t *tok = (const uint32_t *)p.toks + sk;
+            int64_t tbk = 0;
+            if constexpr (OFFS) tbk = wv::bcast(tb, k);
             for (int t0 = 0; t0 < ck; t0 += 64) {
                 const int t = t0 + lane;
                 const bool act = t < ck;
@@ -1574,6 +1598,18 @@ __global__ __launch_bounds__(256) void k_uni_ids(UniIdsParams p)
                 if (act && !walk) {
                     const int id = (v & UC_TOK_KEY) ? p.ids[v & 0xFFFFFu] : -1;
                     p.ids_out[ok + t] = (id != -1 ? id : p.unk) + p.id_offset;
+                }
+                if constexpr (OFFS) {
+                    if (act) {                      // t < ck <= the document's room below ids_cap
+                        int from, to;
+                        uni_token_span((const uint32_t *)p.spans + sk, t, from, to);
+                        const int32_t *so_doc = p.src_off + sk;
+                        const int so = from >= 0 ? so_doc[from] : -1;
+                        const int eo = so_doc[to];
+                        int sz = 0;
+                        if (eo >= 0) { const uint32_t ch = p.b.text[tbk + eo]; sz = (ch & 0x80) == 0 ? 1 : (ch & 0xE0) == 0xC0 ? 2 : (ch & 0xF0) == 0xE0 ? 3 : (ch & 0xF8) == 0xF0 ? 4 : 0; }
+                        p.starts_out[ok + t] = so; p.ends_out[ok + t] = eo + (sz > 0 ? sz - 1 : 0);
+                    }
                 }
                 const unsigned long long wm = __ballot(walk);
                 if (wm) {
@@ -1597,7 +1633,8 @@ void launch_uni_ids(const UniIdsParams &p, hipStream_t s)
     int64_t blocks = (p.b.ndocs + 255) / 256;
     if (blocks > device_cus() * 8) blocks = device_cus() * 8;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_uni_ids, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    if (p.starts_out) hipLaunchKernelGGL(k_uni_ids<true>, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_uni_ids<false>, dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
 // BPE, documents whose arcs exceed the per-document reserve (narcs == -1 on the fallback list; a long run of one character whose
@@ -1665,11 +1702,12 @@ void launch_seg_sp(const SpSegParams &p_in, const SegKnobs &k, hipStream_t s)
             int ring = 1; while (ring < p.trie_depth) ring <<= 1;
             const size_t lds = (size_t)ring * 64 * (sizeof(double) + sizeof(uint32_t));
             if (p.uni_cut) {
-                // the cut form (ids only): records in LDS, tokens out at the cuts, no backward kernel
+                // the cut form: records in LDS, tokens out at the cuts, no backward kernel; the offsets call takes the instance that also leaves span words
                 int W = 32; while (W < p.trie_depth + UC_SPILL + 4) W <<= 1;
                 const size_t lds_c = (size_t)ring * 64 * sizeof(double) + (size_t)W * 64;
                 int pc = 0;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, (const void *)k_uni_cut<3>, 64, lds_c) != hipSuccess || pc <= 0) pc = 8;
+                const bool spans = p.span_tmp != nullptr;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, spans ? (const void *)k_uni_cut<3, true> : (const void *)k_uni_cut<3, false>, 64, lds_c) != hipSuccess || pc <= 0) pc = 8;
                 (void)hipGetLastError();
                 if (k.per_cu_cap > 0 && k.per_cu_cap < pc) pc = k.per_cu_cap;
                 unsigned blocks = (unsigned)device_cus() * (unsigned)pc;
@@ -1678,8 +1716,8 @@ void launch_seg_sp(const SpSegParams &p_in, const SegKnobs &k, hipStream_t s)
                 if (k.tune > 0) { period_mask = 1u; while (period_mask + 1u < (unsigned)k.tune) period_mask = period_mask * 2u + 1u; if (k.tune == 1) period_mask = 0u; }
                 const int quick = k.quick_or_one_kernel ? 1 : 0;
                 if (p.ev_dom0) (void)hipEventRecord((hipEvent_t)p.ev_dom0, s);
-                if (k.cut_unroll2) hipLaunchKernelGGL(k_uni_cut<2>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, quick);
-                else hipLaunchKernelGGL(k_uni_cut<3>, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, quick);
+                void (*cut)(SpSegParams, int, int, unsigned, int) = k.cut_unroll2 ? (spans ? k_uni_cut<2, true> : k_uni_cut<2, false>) : (spans ? k_uni_cut<3, true> : k_uni_cut<3, false>);
+                hipLaunchKernelGGL(cut, dim3(blocks), dim3(64), lds_c, s, p, ring, W, period_mask, quick);
                 if (p.ev_dom1) (void)hipEventRecord((hipEvent_t)p.ev_dom1, s);
                 return;
             }

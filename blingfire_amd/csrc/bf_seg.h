@@ -293,17 +293,26 @@ struct UniLane {
 // "no incoming arc" by its score alone), so nothing is reserved ahead of the walk.  A lane whose pending region fills the ring with no cut to
 // emit (a word of more than ~24 symbols, a long unknown run) SPILLS its oldest final records to the document's record bytes in memory;
 // the hops read them back from there.  Rare: 0.1 % of the documents of running text.
+// The offsets instance (SPANS): every token that leaves the lane also leaves ONE span word, at the token's index of a second array --
+// the stream position of its last symbol (`to`).  `from` is not stored: the tokens the backward pass emits tile the stream (every hop goes to
+// begin - 1, ..._1best_t.h:237-265), so from(k) = to(k - 1) + 1 and from(0) = 0 -- except behind the restart, whose token is <UnkId, -1, end>
+// (..._1best_t.h:250-262): it always lands on index 0 and its word carries UC_SPAN_RESTART (from = -1); the tokens behind it tile again.
+// The span words are stored where the token words are (quick(), emit() -- which also covers what was spilled and the restart), never in the walk.
 // ---------------------------------------------------------------------------------------------------
 enum { UC_DONE = 0, UC_MORE = 1, UC_STALL = 2 };
 constexpr int UC_SPILL = 8;                           // records per spill
 constexpr uint32_t UC_NONE = 0u, UC_UNK = 0x80u, UC_RUN_MAX = 127u, UC_TOK_UNK = 0x80000000u, UC_TOK_KEY = 0x40000000u;
 constexpr int UC_BEGIN_BITS = 25;
+constexpr uint32_t UC_SPAN_RESTART = 0x80000000u;       // span word: the restart's token, from = -1 (stream positions are below 2^31)
 #ifndef BF_UC_STAT
 #define BF_UC_STAT(k)
 #endif
 BF_HD uint32_t uc_unk_rec(int run) { const uint32_t f = (uint32_t)(run - 1); return UC_UNK | (f < UC_RUN_MAX ? f : UC_RUN_MAX); }
 
-template <class ClsAt, class Ring>
+template <bool SPANS> struct UcSpanQueue { BF_HD void push(uint32_t) {} };      // the span words of emit()'s group of four; nothing in the ids instance
+template <> struct UcSpanQueue<true> { uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0; BF_HD void push(uint32_t v) { s3 = s2; s2 = s1; s1 = s0; s0 = v; } };
+
+template <class ClsAt, class Ring, bool SPANS = false>
 struct UniCut {
     const SegTables &S; ClsAt &cls_at; Ring &ring; uint8_t *recs;
     int L, depth, W, start, i, sum; uint32_t state; bool unknown, pend, walking; double prev; uint32_t pend_score; int pend_i;
@@ -443,6 +452,10 @@ struct UniCut {
         if (n == 0) return;
         put(nout, w0);
         if (n == 2) put(nout + 1, w1);
+        if constexpr (SPANS) {                                          // put.span(index, word): the token's last position
+            if (n == 2) { put.span(nout, (uint32_t)(b1 - 1)); put.span(nout + 1, (uint32_t)lastcut); }
+            else put.span(nout, (uint32_t)lastcut);
+        }
         BF_UC_STAT(cs == b1 ? 0 : 1); if (n == 2) BF_UC_STAT(1);
         nout += n; cut0 = lastcut + 1; ring_lo = ring_lo < cut0 ? cut0 : ring_lo;
     }
@@ -473,16 +486,21 @@ struct UniCut {
         // the words leave last to first, four at a time when they make an aligned group of the document's token array (put.quad: one 16-byte store;
         // a 4-byte store per token made the kernel write 22 GB for 4.6 GB of tokens -- every store its own sector, round 6 counters)
         uint32_t g0 = 0, g1 = 0, g2 = 0, g3 = 0; int gn = 0;            // g0: the word at the lowest index so far
+        UcSpanQueue<SPANS> sq;                                          // (SPANS) the span words of the same tokens
         int k = n - 1;
         for (int e = lastcut; k >= 0; --k) {
             const uint32_t r = rec_at(e);
             uint32_t w = UC_TOK_UNK; int len = 0;
             if (r != UC_NONE) { len = tok_len(e, r); if (!(r & UC_UNK)) w = walk_word(e - len + 1, len); BF_UC_STAT(2); }
             g3 = g2; g2 = g1; g1 = g0; g0 = w; ++gn;
+            if constexpr (SPANS) sq.push((uint32_t)e | (r == UC_NONE ? UC_SPAN_RESTART : 0u));
             const int idx = base + k;
             if (((idx + tok_align) & 3) == 0 || k == 0 || r == UC_NONE) {
-                if (gn == 4 && ((idx + tok_align) & 3) == 0) put.quad(idx, g0, g1, g2, g3);
-                else { put(idx, g0); if (gn > 1) put(idx + 1, g1); if (gn > 2) put(idx + 2, g2); if (gn > 3) put(idx + 3, g3); }
+                if (gn == 4 && ((idx + tok_align) & 3) == 0) { put.quad(idx, g0, g1, g2, g3); if constexpr (SPANS) put.span_quad(idx, sq.s0, sq.s1, sq.s2, sq.s3); }
+                else {
+                    put(idx, g0); if (gn > 1) put(idx + 1, g1); if (gn > 2) put(idx + 2, g2); if (gn > 3) put(idx + 3, g3);
+                    if constexpr (SPANS) { put.span(idx, sq.s0); if (gn > 1) put.span(idx + 1, sq.s1); if (gn > 2) put.span(idx + 2, sq.s2); if (gn > 3) put.span(idx + 3, sq.s3); }
+                }
                 gn = 0;
             }
             if (r == UC_NONE) break;
@@ -513,6 +531,15 @@ BF_HD int uni_token_id(const SegTables &S, const int32_t *ids, ClsAt &cls_at, ui
         id = ids[sum];
     }
     return (id != -1 ? id : unk) + S.id_offset;
+}
+
+// The stream positions (from, to) of token t from the span words the offsets instance of UniCut left (what k_uni_ids does per lane; the
+// values the lane program's bstep() hands to put()): sp = the document's span words, t < its token count.
+BF_HD void uni_token_span(const uint32_t *sp, int t, int &from, int &to)
+{
+    const uint32_t w = sp[t];
+    to = (int)(w & ~UC_SPAN_RESTART);
+    from = t > 0 ? (int)(sp[t - 1] & ~UC_SPAN_RESTART) + 1 : ((w & UC_SPAN_RESTART) ? -1 : 0);
 }
 
 // ---------------------------------------------------------------------------------------------------
