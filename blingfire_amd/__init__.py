@@ -78,6 +78,9 @@ _SIGNATURES = {
     "IdsToPackedRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 5 + [_P] * 4 + [_L] + [_P] * 4),
     "IdsToStreamRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 6 + [_P] * 6 + [_L, _P, _P]),
     "IdsToStreamRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 6 + [_P] * 6 + [_L] + [_P] * 4),
+    # the bucketed call: max_len, cls, sep, pad, multiple, max_cells, max_rows, flags; the planes and their cap, order, seq_pos, the per-batch arrays and their cap, counts
+    "IdsToBucketedRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 5 + [_L, _I, _I, _P, _P, _L] + [_P] * 5 + [_L, _P]),
+    "IdsToBucketedRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 5 + [_L, _I, _I, _P, _P, _L] + [_P] * 5 + [_L, _P, _P]),
     "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
     "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
     "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
@@ -1025,6 +1028,96 @@ def encode_packed_batch(h, docs, L, cls_id, sep_id, pad_id, unk=0, rows_cap=None
     """encode_packed_batch_device for a list of str / bytes (or a (uint8 array, int64 offsets) pair): packed into one buffer, uploaded with
     torch to the current device, encoded there."""
     return encode_packed_batch_device(h, *_upload_docs(docs), L, cls_id, sep_id, pad_id, unk, rows_cap)
+
+
+def _bucket_args(max_len, cls_id, sep_id, pad_id, multiple, max_cells, max_rows):
+    return (int(max_len), _special(cls_id), _special(sep_id), int(pad_id), int(multiple), int(max_cells), int(max_rows), 0)
+
+
+def _bucket_outs(nseq, cells, batches, new):
+    """rows, mask, order, seq_pos, batch_first, batch_len, batch_cell, counts: new(n, dtype) makes an array of n elements"""
+    return [new(cells, "int32"), new(cells, "uint8"), new(nseq, "int32"), new(nseq, "int32"), new(batches + 1, "int32"), new(batches + 1, "int32"),
+            new(batches + 1, "int64"), new(2, "int64")]
+
+
+def _bucket_call(name, pre, outs, cells_cap, batches_cap, addr, post=()):
+    """fn(*pre, rows, mask, cells_cap, order, seq_pos, batch_first, batch_len, batch_cell, batches_cap, counts, *post); None in outs = NULL"""
+    a = [None if o is None else addr(o) for o in outs]
+    return getattr(lib(), name)(*pre, a[0], a[1], cells_cap, a[2], a[3], a[4], a[5], a[6], batches_cap, a[7], *post)
+
+
+def ids_to_bucketed_rows_batch(h, ids, id_off, max_len, max_cells, cls_id=None, sep_id=None, pad_id=0, multiple=8, max_rows=0):
+    """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> LENGTH-BUCKETED model inputs (IdsToBucketedRowsBatch): the sequences sorted
+    by length (longest first, ties in input order), cut into batches of at most max_cells cells (and max_rows rows, 0 = no limit), every batch
+    padded to its own longest row rounded up to `multiple`; a sequence longer than max_len is truncated.  cls_id / sep_id None = no such special.
+    Returns (rows int32[C], mask uint8[C], order int32[nseq], seq_pos int32[nseq], batch_first int32[B + 1], batch_len int32[B + 1],
+    batch_cell int64[B + 1], counts int64[2] = (B, C)): batch b is rows[batch_cell[b] : batch_cell[b + 1]] seen as [n_b, batch_len[b]] and holds
+    the sequences order[batch_first[b] : batch_first[b + 1]]; seq_pos is the inverse of order.  bucketed_views cuts the planes up."""
+    name = "IdsToBucketedRowsBatch"
+    ids, id_off, nseq = _host_ragged(ids, id_off)
+    pre = _head(h, nseq, (ids, id_off)) + _bucket_args(max_len, cls_id, sep_id, pad_id, multiple, max_cells, max_rows)
+    new, addr = (lambda n, t: np.empty(n, dtype=t)), (lambda a: a.ctypes.data)
+    outs = _bucket_outs(nseq, 0, 0, new)
+    n = _bucket_call(name, pre, [None, None] + outs[2:4] + [None] * 3 + outs[7:], 0, 0, addr)      # the size query: order, seq_pos and the counts
+    _check(name, n, n >= 0, _COUNT)
+    B = int(outs[7][0])
+    full = _bucket_outs(nseq, n, B, new)
+    outs = full[:2] + outs[2:4] + full[4:7] + outs[7:]
+    r = _bucket_call(name, pre, outs, n, B, addr)
+    _check(name, r, r == n, _COUNT)
+    return tuple(outs)
+
+
+def ids_to_bucketed_rows_batch_device(h, d_ids, d_id_off, max_len, max_cells, cls_id=None, sep_id=None, pad_id=0, multiple=8, max_rows=0, cells_cap=None,
+                                      batches_cap=None, stream=None):
+    """Device-resident ids_to_bucketed_rows_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are)
+    -> the same eight results as tensors on that device, enqueued on torch's current stream (or `stream`).  With cells_cap and batches_cap
+    both given nothing is read back: the planes have cells_cap cells and the per-batch tensors batches_cap + 1 entries, of which C cells and
+    B + 1 entries are written; what does not fit is dropped (BfLastStatus bit 0).  With either None a size query runs first and counts is
+    read back (one synchronisation): the missing cap is the exact one."""
+    import torch
+    name = "IdsToBucketedRowsBatchDevice"
+    dev = d_ids.device
+    nseq = d_id_off.numel() - 1
+    pre = _head(h, nseq, (d_ids, d_id_off)) + _bucket_args(max_len, cls_id, sep_id, pad_id, multiple, max_cells, max_rows)
+    post = (_stream_arg(stream, dev),)
+    new, addr = (lambda n, t: torch.empty(n, dtype=getattr(torch, t), device=dev)), (lambda t: t.data_ptr())
+    if cells_cap is None or batches_cap is None:
+        counts = new(2, "int64")
+        r = _bucket_call(name, pre, [None] * 7 + [counts], 0, 0, addr, post)
+        _check(name, r, r == 0)
+        if stream is not None:
+            torch.cuda.synchronize(dev)                   # (a raw stream handle: nothing finer to wait on)
+        B, C = (int(x) for x in counts.tolist())
+        cells_cap, batches_cap = C if cells_cap is None else cells_cap, B if batches_cap is None else batches_cap
+    outs = _bucket_outs(nseq, int(cells_cap), int(batches_cap), new)
+    r = _bucket_call(name, pre, outs, int(cells_cap), int(batches_cap), addr, post)
+    _check(name, r, r == 0)
+    return tuple(outs)
+
+
+def encode_bucketed_batch_device(h, d_text, d_doc_off, max_len, cls_id, sep_id, pad_id, max_cells, multiple=8, max_rows=0, unk=0, cells_cap=None,
+                                 batches_cap=None):
+    """Text in HBM -> length-bucketed tensors a model takes, nothing on the host: text_to_ids_batch_device (every document tokenised up to the
+    ids a row of max_len can hold) and ids_to_bucketed_rows_batch_device on one stream.  Returns what ids_to_bucketed_rows_batch_device
+    returns; with cells_cap and batches_cap both given nothing is read back."""
+    body = int(max_len) - _nspecial(cls_id, sep_id)
+    if body < 1:
+        raise ValueError("encode_bucketed_batch_device: max_len leaves no room for ids")
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, body, unk)
+    return ids_to_bucketed_rows_batch_device(h, d_ids, d_id_off, max_len, max_cells, cls_id, sep_id, pad_id, multiple, max_rows, cells_cap, batches_cap)
+
+
+def bucketed_views(rows, mask, batch_first, batch_len, batch_cell, counts):
+    """The batches of a bucketed call, one after the other: (rows[n_b, L_b], mask[n_b, L_b], the slice of `order` the batch holds), views of the
+    flat planes (numpy arrays or torch tensors).  The per-batch arrays are copied to the host once -- the shapes must be there to launch a
+    model anyway.  Batches that a cap of the call cut off (BfLastStatus bit 0) are left out."""
+    first, blen, cell, counts = (np.asarray(t.cpu() if hasattr(t, "cpu") else t) for t in (batch_first, batch_len, batch_cell, counts))
+    for b in range(min(int(counts[0]), len(first) - 1)):
+        lo, hi, L = int(cell[b]), int(cell[b + 1]), int(blen[b])
+        if hi > len(rows):
+            break
+        yield rows[lo:hi].reshape(-1, L), mask[lo:hi].reshape(-1, L), slice(int(first[b]), int(first[b + 1]))
 
 
 def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,

@@ -217,7 +217,8 @@ struct Handle {
     DevBuf w_rowseq, w_rowfirst;                                 // IdsToRowsBatch / IdsToPairRowsBatch: sequence (pair) and first id of every row, where the caller takes neither
     DevBuf w_plsrc[2][ROWS_MAX_PLANES], w_plout[ROWS_MAX_PLANES]; // IdsToRowsPlanesBatch / IdsToPairRowsPlanesBatch, host forms: the staged companion arrays of each side, the planes
     DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
-    DevBuf w_cplead, w_cpfour, w_cpcnt, w_cpP;                   // Byte / CharToByteOffsetsBatchDevice (bf_kernels.h CharposParams): the two masks, the weights, P -- 28 bytes per 64 bytes of text
+    DevBuf w_bkkey[2], w_bkval[2], w_bkcnt, w_bkbase;            // IdsToBucketedRowsBatch (bf_kernels.h BucketParams): the sort's records, a pass's digit counts, their scan
+    DevBuf w_cplead, w_cpfour, w_cpcnt, w_cpP;                  // Byte / CharToByteOffsetsBatchDevice (bf_kernels.h CharposParams): the two masks, the weights, P -- 28 bytes per 64 bytes of text
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
     DevBuf t_wcp_l1, t_wcp_pages;                                // TextToWords: code point -> class without the charmap
@@ -1674,6 +1675,113 @@ int64_t run_packed_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
                                  PlaneArgs{planes.nplanes, d_src, nullptr, planes.fill, (int32_t *const *)(d + 4)}); });
 }
 
+// IdsToBucketedRowsBatch on device buffers (bf_kernels_bucket.hip).  Beside the packed stage's workspaces, which it borrows for the chain of batch
+// starts, the sort has its own: two key and two value arrays (16 bytes per sequence) and, per BUCKET_TILE sequences, the 256 digit counts of a
+// pass with their scan (12 bytes each: 1.5 bytes per sequence).  w_bsums also serves the scan of those counts.
+bool reserve_bucket_workspaces(Handle *h, int64_t nseq)
+{
+    const size_t n = (size_t)nseq + 2, bins = (size_t)bucket_blocks(nseq) * BUCKET_BINS;
+    return reserve_packed_workspaces(h, nseq) && h->w_bkkey[0].reserve(n * 4) && h->w_bkkey[1].reserve(n * 4) && h->w_bkval[0].reserve(n * 4) &&
+           h->w_bkval[1].reserve(n * 4) && h->w_bkcnt.reserve((bins + 1) * 4) && h->w_bkbase.reserve((bins + 1) * 8) &&
+           h->w_bsums.reserve((size_t)(scan_nblocks((int64_t)bins) + 1) * 8);
+}
+
+// keys, the sort passes (count, scan, scatter), next, the doubling rounds, the scan of the marks, first, lens, their scan, the per-batch outputs,
+// then -- when a plane is taken -- the fill.  The launches depend on nseq, max_len and on which outputs are taken, never on the data.
+int run_bucket_device(Handle *h, const BucketSpec &spec, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, int32_t *d_rows, uint8_t *d_mask,
+                      int64_t cells_cap, int32_t *d_order, int32_t *d_seq_pos, int32_t *d_batch_first, int32_t *d_batch_len, int64_t *d_batch_cell, int64_t batches_cap,
+                      int64_t *d_counts, hipStream_t s)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || cells_cap < 0 || batches_cap < 0 || ids_len < 0 || !d_id_off || !d_counts || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    if (!reserve_bucket_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    const int passes = bucket_passes(spec.max_len);
+    BucketParams p;
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
+    for (int k = 0; k < 2; ++k) { p.key[k] = h->w_bkkey[k].as<uint32_t>(); p.val[k] = h->w_bkval[k].as<int32_t>(); p.jmp[k] = h->w_pkjmp[k].as<int32_t>(); }
+    p.sorted = passes & 1; p.nblocks = bucket_blocks(nseq); p.counts = h->w_bkcnt.as<int32_t>(); p.bases = h->w_bkbase.as<int64_t>();
+    p.mark = h->w_pkmark.as<int32_t>(); p.mark_off = h->w_pkmoff.as<int64_t>(); p.first = h->w_pkf.as<int32_t>();
+    p.row_len = h->w_counts.as<int32_t>(); p.row_cell = h->w_pkW.as<int64_t>();
+    p.cells_cap = cells_cap; p.batches_cap = batches_cap; p.rows = d_rows; p.mask = d_mask; p.order = d_order; p.seq_pos = d_seq_pos;
+    p.batch_first = d_batch_first; p.batch_len = d_batch_len; p.batch_cell = d_batch_cell; p.counts_out = d_counts;
+    PackedParams chain;                                                         // what launch_packed_double reads: the jump arrays, the marks, nseq
+    chain.jmp[0] = p.jmp[0]; chain.jmp[1] = p.jmp[1]; chain.mark = p.mark; chain.nseq = nseq;
+    const int64_t bins = p.nblocks * BUCKET_BINS;
+    // the events BfLastKernelMs reads: [0] keys, [1] the sort passes, [5] the scatter kernel of the last pass, [2] the chain, the scans and the per-batch outputs, [3] fill
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (nseq > 0) launch_bucket_keys(p, s);
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    if (nseq == 0) { (void)hipEventRecord(h->ev[EV_DOM0], s); (void)hipEventRecord(h->ev[EV_DOM1], s); }
+    else for (int pass = 0; pass < passes; ++pass) {
+        launch_bucket_count(p, pass, s);
+        launch_scan(ScanParams{p.counts, bins, h->w_bkbase.as<int64_t>(), h->w_bsums.as<int64_t>(), scan_nblocks(bins)}, s);
+        if (pass == passes - 1) (void)hipEventRecord(h->ev[EV_DOM0], s);
+        launch_bucket_scatter(p, pass, s);
+        if (pass == passes - 1) (void)hipEventRecord(h->ev[EV_DOM1], s);
+    }
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    if (nseq > 0) {
+        launch_bucket_next(p, s);
+        for (int k = 0, rounds = packed_rounds(nseq); k < rounds; ++k) launch_packed_double(chain, k, s);
+    }
+    launch_scan(ScanParams{p.mark, nseq, p.mark_off, h->w_bsums.as<int64_t>(), scan_nblocks(nseq)}, s);
+    launch_bucket_first(p, s);
+    if (nseq > 0) launch_bucket_lens(p, s);
+    scan_counts(h, nseq, h->w_pkW.as<int64_t>(), s);
+    launch_bucket_batches(p, s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    if (nseq > 0 && cells_cap > 0 && (d_rows || d_mask)) launch_bucket_fill(p, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "IdsToBucketedRows kernels") ? 0 : BF_E_DEVICE;
+}
+
+// IdsToBucketedRowsBatch on host buffers: the ids through stage_ragged, then count_fill_host over the cell total, whose size pass also answers
+// order, seq_pos and the counts.  The per-batch arrays are sized by B, not by the cells: the fill pass checks B against batches_cap before it
+// queues anything, writes them into stagings of their own, and they are copied out behind the planes.
+int64_t run_bucket_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const BucketSpec &spec, int32_t *rows_out, uint8_t *mask_out, int64_t cells_cap,
+                        int32_t *order_out, int32_t *seq_pos_out, int32_t *batch_first_out, int32_t *batch_len_out, int64_t *batch_cell_out, int64_t batches_cap,
+                        int64_t *counts_out)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || cells_cap < 0 || batches_cap < 0 || !id_off || !counts_out) return BF_E_ARG;
+    const int64_t ids_len = host_side_len(id_off, nseq);
+    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    const size_t seq_bytes = (size_t)nseq * 4;
+    if (!h->w_idoff.reserve(16) || !h->w_starts.reserve(seq_bytes + 16) || !h->w_ends.reserve(seq_bytes + 16)) return BF_E_DEVICE;
+    Staged st;
+    int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    const RowOut outs[ROW_HOST_OUTS] = {{rows_out, &h->w_out, 4, "D2H rows"}, {mask_out, &h->w_text, 1, "D2H mask"}};
+    DevBuf *const d_batch[3] = {&h->w_outoff, &h->w_plout[0], &h->w_vals};       // first, len, cell
+    void *const batch_out[3] = {batch_first_out, batch_len_out, batch_cell_out};
+    const size_t batch_elem[3] = {4, 4, 8};
+    size_t nb = 0;                                                              // B + 1 once the fill pass has run
+    const int64_t total = count_fill_host(s, {{counts_out, &h->w_idoff, 16, "D2H counts"}, {order_out, &h->w_starts, seq_bytes, "D2H order"}, {seq_pos_out, &h->w_ends, seq_bytes, "D2H positions"}},
+                                          &counts_out[1], outs, cells_cap, true, [&](void *const d[ROW_HOST_OUTS], int64_t cap) {
+        const bool fill = d[0] || d[1];
+        void *db[3] = {};
+        if (fill) {
+            if (counts_out[0] > batches_cap) return BF_E_CAPACITY;
+            nb = (size_t)counts_out[0] + 1;
+            for (int k = 0; k < 3; ++k) {
+                if (!batch_out[k]) continue;
+                if (!d_batch[k]->reserve(nb * batch_elem[k] + 16)) return BF_E_DEVICE;
+                db[k] = d_batch[k]->p;
+            }
+        }
+        return run_bucket_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, (int32_t *)d[0], (uint8_t *)d[1], cap,
+                                 order_out ? h->w_starts.as<int32_t>() : nullptr, seq_pos_out ? h->w_ends.as<int32_t>() : nullptr, (int32_t *)db[0], (int32_t *)db[1],
+                                 (int64_t *)db[2], fill ? counts_out[0] : 0, h->w_idoff.as<int64_t>(), s); });
+    if (total < 0 || nb == 0) return total;
+    for (int k = 0; k < 3; ++k)
+        if (batch_out[k] && !hip_ok(hipMemcpyAsync(batch_out[k], d_batch[k]->p, nb * batch_elem[k], hipMemcpyDeviceToHost, s), "D2H batches")) { (void)hipStreamSynchronize(s); return BF_E_DEVICE; }
+    return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? total : BF_E_DEVICE;
+}
+
 // IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
 // outputs the caller takes -- the fill.  The launches depend on nseq and on which outputs are taken, never on the data; the workspaces are the
 // first three of the packed stage (reserve_packed_workspaces): nothing here is sized by the row count.
@@ -2604,6 +2712,32 @@ int64_t IdsToPackedRowsBatch(void *p, const int32_t *ids, const int64_t *id_offs
     return run_packed_host(h, ids, id_offsets, nseq, spec, rows_out, seg_out, pos_out, row_first_seq_out, rows_cap, seq_row_out, seq_col_out);
 }
 
+/* ---- additive: length-bucketed batches (bf_bucket.h): the units sorted by width, cut under a cell budget, every batch padded to its longest row */
+int IdsToBucketedRowsBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int max_len, int cls_id, int sep_id,
+                                 int pad_id, int multiple, int64_t max_cells, int max_rows, int flags, int32_t *d_rows_out, uint8_t *d_mask_out, int64_t cells_cap,
+                                 int32_t *d_order_out, int32_t *d_seq_pos_out, int32_t *d_batch_first_out, int32_t *d_batch_len_out, int64_t *d_batch_cell_out,
+                                 int64_t batches_cap, int64_t *d_counts_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    BucketSpec spec;
+    if (!h || !bucket_spec(max_len, cls_id, sep_id, pad_id, multiple, max_cells, max_rows, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_bucket_device(h, spec, d_ids, ids_len, d_id_offsets, nseq, d_rows_out, d_mask_out, cells_cap, d_order_out, d_seq_pos_out, d_batch_first_out, d_batch_len_out,
+                             d_batch_cell_out, batches_cap, d_counts_out, (hipStream_t)stream);
+}
+
+int64_t IdsToBucketedRowsBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int max_len, int cls_id, int sep_id, int pad_id, int multiple,
+                               int64_t max_cells, int max_rows, int flags, int32_t *rows_out, uint8_t *mask_out, int64_t cells_cap, int32_t *order_out, int32_t *seq_pos_out,
+                               int32_t *batch_first_out, int32_t *batch_len_out, int64_t *batch_cell_out, int64_t batches_cap, int64_t *counts_out)
+{
+    Handle *h = as_handle(p);
+    BucketSpec spec;
+    if (!h || !bucket_spec(max_len, cls_id, sep_id, pad_id, multiple, max_cells, max_rows, flags, &spec)) return BF_E_ARG;
+    return run_bucket_host(h, ids, id_offsets, nseq, spec, rows_out, mask_out, cells_cap, order_out, seq_pos_out, batch_first_out, batch_len_out, batch_cell_out, batches_cap,
+                           counts_out);
+}
+
 /* ---- additive: packed rows with companion planes (k_packed_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */
 int IdsToPackedRowsPlanesBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
                                      int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
@@ -2779,6 +2913,7 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     if (!reserve_rows_workspaces(h, max_docs)) return BF_E_DEVICE;                                   // IdsToRowsBatchDevice, any handle: documents = sequences
     if (!reserve_packed_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToPackedRowsBatchDevice, any handle
+    if (!reserve_bucket_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToBucketedRowsBatchDevice, any handle
     if (!reserve_charpos_workspaces(h, max_bytes)) return BF_E_DEVICE;                               // Byte / CharToByteOffsetsBatchDevice, any handle: sized by the text alone
     if (h->m.kind == KIND_I2W) return 0;                                                            // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words

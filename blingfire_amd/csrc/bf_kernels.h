@@ -12,6 +12,7 @@
 #include "bf_rows.h"
 #include "bf_pairs.h"
 #include "bf_packed.h"
+#include "bf_bucket.h"
 #include "bf_stream.h"
 #include "bf_mlm.h"
 #include "bf_denoise.h"
@@ -405,6 +406,33 @@ struct CharposParams {
 void launch_char_index(const CharposParams &p, hipStream_t s);                  // the pass over the text: masks and weights
 void launch_char_docs(const CharposParams &p, hipStream_t s);                   // behind the scan: status bit 3 of a bad range, U_d
 void launch_char_items(const CharposParams &p, int64_t items_bound, hipStream_t s);     // k_char_fwd / k_char_inv, a lane per item
+// IdsToBucketedRowsBatch (additive; bf_bucket.h has the lane code, bf_kernels_bucket.hip the kernels): the units sorted by width, cut into batches
+// under a cell budget, every batch padded to its own longest row.  The chain of batch starts runs through the packed stage's jump arrays, marks
+// and their scan; every per-position array has nseq + 1 entries (index nseq = the end of the chain) unless noted.
+struct BucketParams {
+    BucketSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    uint32_t *key[2]; int32_t *val[2];           // [nseq] each: the records of the radix sort, a pass reads buffer pass & 1 and writes the other
+    int sorted;                                  // the buffer the last pass wrote: passes & 1
+    int64_t nblocks;                             // bucket_blocks(nseq)
+    int32_t *counts; const int64_t *bases;       // [256 * nblocks] bin-major digit counts of a pass; their exclusive scan (+ 1 entry)
+    int32_t *jmp[2], *mark; int64_t *mark_off;   // the packed stage's: next(i) squared round by round, the batch starts, batches in front of a position
+    int32_t *first;                              // the sorted position every batch starts at, first[B] = nseq
+    int32_t *row_len; const int64_t *row_cell;   // [nseq] L of a position's batch; the exclusive scan of those: a row's first cell, row_cell[nseq] = the cell total
+    int64_t cells_cap, batches_cap;              // no cell >= cells_cap of a plane is written, no entry past min(B, batches_cap) of a per-batch array
+    int32_t *rows; uint8_t *mask;                // [cells_cap] each, either may be NULL
+    int32_t *order, *seq_pos;                    // [nseq] each, either may be NULL
+    int32_t *batch_first, *batch_len; int64_t *batch_cell;      // [batches_cap + 1] each, any may be NULL
+    int64_t *counts_out;                         // [2] = {B, the cell total}
+};
+void launch_bucket_keys(const BucketParams &p, hipStream_t s);                  // lane per sequence: key[0], status bit 3
+void launch_bucket_count(const BucketParams &p, int pass, hipStream_t s);       // a block per tile: its column of the digit counts
+void launch_bucket_scatter(const BucketParams &p, int pass, hipStream_t s);     // behind the scan of the counts: the records to their places, in order
+void launch_bucket_next(const BucketParams &p, hipStream_t s);                  // lane per sorted position: jmp[0] = next, mark = {0}; order, seq_pos
+void launch_bucket_first(const BucketParams &p, hipStream_t s);                 // behind the scan of the marks: first
+void launch_bucket_lens(const BucketParams &p, hipStream_t s);                  // row_len
+void launch_bucket_batches(const BucketParams &p, hipStream_t s);               // behind the scan of row_len: the per-batch outputs, the counts, status bit 0
+void launch_bucket_fill(const BucketParams &p, hipStream_t s);                  // the two planes
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -513,6 +513,51 @@ BF_API int64_t IdsToPackedRowsPlanesBatch(void *ModelPtr, const int32_t *ids, co
                                    int32_t *seq_row_out, int32_t *seq_col_out,
                                    int nplanes, const int32_t *const *src, const int32_t *fill, int32_t *const *planes_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): LENGTH-BUCKETED batches -- the sequences sorted by length, the
+ * sorted list cut into batches under a cell budget (fairseq's max_tokens), every batch padded only to its own longest member.  For fine-tuning,
+ * embedding and reranking over a corpus, and models that cannot take the block-diagonal mask of packed rows.
+ * Units.  Sequence q of nseq = ids[off[q] .. off[q+1]), n_q ids; a range outside [0, ids_len] or with decreasing offsets is read as empty and sets
+ * BfLastStatus bit 3, as in IdsToRowsBatchDevice.  lead = (cls_id >= 0), trail = (sep_id >= 0), body = max_len - lead - trail.  Unit q is
+ * [cls_id] ids[0 .. k_q) [sep_id] with k_q = min(n_q, body): a longer sequence is truncated silently.  Its width is w_q = lead + k_q + trail,
+ * 0 <= w_q <= max_len.  These are the units of IdsToPackedRowsBatch with row_len = max_len.
+ * Order.  pi = the permutation of 0 .. nseq-1 by w descending, ties by q ascending (a stable sort on the key max_len - w).
+ * d_order_out[i] = pi(i); d_seq_pos_out[q] = the sorted position of q, with which one index_select puts model outputs back in input order.
+ * Batches.  up(x) = ceil(x / multiple) * multiple.  A batch that starts at sorted position i has rows of L(i) = max(multiple, up(w_pi(i))) cells
+ * (its first row is its longest) and holds cnt(i) = max(1, min(max_cells / L(i), max_rows > 0 ? max_rows : infinity)) rows, the division rounding
+ * down; next(i) = min(nseq, i + cnt(i)).  The batch starts are the chain 0, next(0), next(next(0)), ... until nseq; B is their count; nseq = 0
+ * gives B = 0.  Batch b has n_b rows of L_b cells and starts at cell C_b = the sum of n_b' * L_b' over b' < b (int64); C_B is the cell total.
+ * The three per-batch arrays have batches_cap + 1 entries each and are written for b = 0 .. min(B, batches_cap): d_batch_first_out[b] = the sorted
+ * position of batch b's first row, with entry B = nseq; d_batch_len_out[b] = L_b, with entry B = 0; d_batch_cell_out[b] = C_b, with entry B = C_B.
+ * d_counts_out[0] = B, d_counts_out[1] = C_B: both always written.
+ * Planes.  d_rows_out (int32) and d_mask_out (uint8) are flat, cells_cap cells each: batch b is the row-major [n_b, L_b] block that starts at
+ * cell C_b; row i - first_b of it holds unit pi(i), then pad_id; the mask is 1 over the unit and 0 behind it.  Padding is on the right.
+ * Caps.  No cell >= cells_cap is written, no entry beyond min(B, batches_cap) of a per-batch array; either loss, from an output the caller takes,
+ * sets BfLastStatus bit 0 (the call clears the status word first).
+ * BF_E_ARG for max_len outside 1 .. 1 << 20, body < 1, multiple < 1, max_cells < max(multiple, up(max_len)) (so that every batch takes at least
+ * one row within the budget), max_rows < 0, flags != 0 (the flag word is reserved), nseq < 0 or nseq > INT32_MAX, a negative cap, ids_len < 0, a
+ * NULL ModelPtr (any live handle of any kind serves: it lends its device, workspaces and status word; the model is not consulted), a NULL
+ * d_id_offsets or d_counts_out, and a NULL d_ids with ids_len > 0.  A refused call touches neither the device nor the status word.
+ * Device form: every output but d_counts_out may be NULL; with both planes NULL it is a size query.  It enqueues on `stream` (a hipStream_t), does
+ * not synchronise, reads nothing back and returns 0 or BF_E_*.  After BfReserve(h, max_docs >= nseq, ...) it allocates nothing, the first call
+ * included.  The kernels it launches depend on nseq, max_len and on which outputs are taken, never on the data: a least-significant-digit radix
+ * sort of 8 bits a pass (1 pass for max_len <= 255, 2 up to 65535, 3 above) whose placement is decided by ballots and prefix sums alone -- stable,
+ * and byte-identical from run to run -- then the pointer doubling of the packed call over next().  Every pointer needs only the natural alignment
+ * of its type; a 16-byte aligned d_rows_out, a 4-byte aligned d_mask_out and multiple % 4 == 0 take the wide stores.
+ * Host form: stages the ids like IdsToPackedRowsBatch (id_offsets[0] < 0 = BF_E_ARG) and returns C_B.  With both planes NULL it is a size query,
+ * whatever the caps are: order_out, seq_pos_out and counts_out are complete, the per-batch arrays are not written.  Otherwise, when C_B > cells_cap
+ * or B > batches_cap, it returns BF_E_CAPACITY with order_out, seq_pos_out and counts_out complete and nothing else written.
+ * Not here: ascending order; windows for sequences longer than max_len (IdsToRowsBatch has them); companion planes; sharding (the sort is global). */
+BF_API int IdsToBucketedRowsBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                                 int max_len, int cls_id, int sep_id, int pad_id, int multiple, int64_t max_cells, int max_rows, int flags,
+                                 int32_t *d_rows_out, uint8_t *d_mask_out, int64_t cells_cap, int32_t *d_order_out, int32_t *d_seq_pos_out,
+                                 int32_t *d_batch_first_out, int32_t *d_batch_len_out, int64_t *d_batch_cell_out, int64_t batches_cap,
+                                 int64_t *d_counts_out, void *stream);
+BF_API int64_t IdsToBucketedRowsBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                               int max_len, int cls_id, int sep_id, int pad_id, int multiple, int64_t max_cells, int max_rows, int flags,
+                               int32_t *rows_out, uint8_t *mask_out, int64_t cells_cap, int32_t *order_out, int32_t *seq_pos_out,
+                               int32_t *batch_first_out, int32_t *batch_len_out, int64_t *batch_cell_out, int64_t batches_cap,
+                               int64_t *counts_out);
+
 /* additive (no counterpart in the reference; this comment is the specification): STREAM rows -- "concatenate and chunk", the input of causal-LM
  * pretraining: every sequence closed by its specials, all of them laid end to end, the stream cut into rows of exactly row_len cells, with
  * next-token labels, a segment plane and a position plane.  Where IdsToPackedRowsBatch truncates a sequence longer than a row and never splits
@@ -704,17 +749,20 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * fill and the kernel of the companion planes behind it.  After IdsToStreamRowsBatchDevice: [0] widths + scan, [2] the per-sequence outputs and
  * the counts, [3] the fill, [4] total ([1] and [5] are 0).  After ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice: [0] the index pass
  * over the text, [2] the scan of the chunk counts, [3] the per-document and the per-item kernel, [4] total ([1] and [5] are 0).
+ * After IdsToBucketedRowsBatchDevice: [0] widths and keys, [1] the sort passes, [2] the chain, the scans and the per-batch outputs, [3] the fill,
+ * [4] total, [5] the scatter kernel of the last pass alone (with max_len <= 255, one pass, that is every scatter kernel there is).
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
- * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
+ * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, bucketed, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
  * and CharToByteOffsetsBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
  * no status.
- * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow (RowsDenoiseBatchDevice: a row longer than enc_len / dec_len); bit 1 (2) and bit 4 (16) = an internal
+ * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow (RowsDenoiseBatchDevice: a row longer than enc_len / dec_len; IdsToBucketedRowsBatchDevice: cells
+ * beyond cells_cap or batches beyond batches_cap of an output the caller takes); bit 1 (2) and bit 4 (16) = an internal
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
  * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
  * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
@@ -739,7 +787,8 @@ BF_API int BfModelKind(void *ModelPtr);
  * IdsToPackedRowsBatchDevice (about 36 bytes per sequence) sized for max_docs sequences or pairs (an [i2w]-only handle has no others).
  * The packed stage's workspaces also cover IdsToPackedRowsPlanesBatchDevice (one kernel behind the base call's, over what that call left
  * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
- * bound).  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
+ * bound).  IdsToBucketedRowsBatchDevice borrows the packed stage's workspaces and adds its sort's: 17.5 bytes per sequence (two key and two
+ * value arrays, and 12 bytes of digit counts per 8 sequences), on every kind of handle.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
  * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
  * Every kind of handle also gets the index of ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice, sized from max_bytes alone (28 bytes per
  * 64 bytes of text, and the scan's block sums for that many chunks): after that the two calls allocate nothing, the first one included.
