@@ -123,9 +123,19 @@ def build_test_infra(force=False):
 def build_unioffs_san(out_dir):
     """tests/hosttest/bf_unioffstest.cpp as a stand-alone program under the address and undefined-behaviour sanitizers (the offsets instance of the
     Unigram cut form in the host driver, against the oracle linked into it): `bf_unioffs MODEL...`, exit status 0 = no difference, no report"""
+    return _build_offs_san(out_dir, "bf_unioffstest.cpp", "-DBF_UNIOFFS_MAIN", "bf_unioffs")
+
+
+def build_bpeoffs_san(out_dir):
+    """tests/hosttest/bf_bpeoffstest.cpp the same way (the SPANS instance of the BPE wave program in the wave simulator, the span logic of
+    k_bpe_home_spans, against the oracle): `bf_bpeoffs MODEL...`"""
+    return _build_offs_san(out_dir, "bf_bpeoffstest.cpp", "-DBF_BPEOFFS_MAIN", "bf_bpeoffs")
+
+
+def _build_offs_san(out_dir, unit, main_flag, name):
     flags = ["-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan"]
     ht = os.path.join(ROOT, "tests", "hosttest")
-    units = [(["g++", "-std=c++17", "-DBF_UNIOFFS_MAIN"], os.path.join(ht, "bf_unioffstest.cpp")), (["g++", "-std=c++17"], os.path.join(ht, "bf_hosttest.cpp")),
+    units = [(["g++", "-std=c++17", main_flag], os.path.join(ht, unit)), (["g++", "-std=c++17"], os.path.join(ht, "bf_hosttest.cpp")),
              (["g++", "-std=c++17"], os.path.join(CSRC, "bf_model.cpp")), (["gcc", "-std=c99"], os.path.join(ROOT, "oracle", "bf_oracle.c"))]
     objs, procs = [], []
     for cc, src in units:
@@ -136,7 +146,7 @@ def build_unioffs_san(out_dir):
     for cmd, pr in procs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
-    exe = os.path.join(out_dir, "bf_unioffs")
+    exe = os.path.join(out_dir, name)
     _run(["g++"] + flags + objs + ["-o", exe])
     return exe
 

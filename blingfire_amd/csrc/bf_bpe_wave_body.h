@@ -79,8 +79,12 @@ struct BwLds {
 
 constexpr int32_t BW_HOME_NONE = (int32_t)0x80000000;      // HOME form: a cell of the staging slot that holds no id (an id is a dictionary id + IdOffset: never this)
 
-template <class LDS, int STEPS = 3, int UMIN = 4, bool HOME = false>
+// SPANS (the offsets calls; HOME only): an id goes to the cell under its piece's FIRST element, not to the next free cell under the word.  The pieces
+// of a word tile it and the words tile the document (emit() of bf_bpe_seg_body.h relies on the same), so the cell index of an id is its `from`
+// and the next id cell minus one -- or the document's last element -- its `to`: k_bpe_home_spans reads both off the cells.  No second array here.
+template <class LDS, int STEPS = 3, int UMIN = 4, bool HOME = false, bool SPANS = false>
 struct BpeWave {
+    static_assert(HOME || !SPANS, "the spans instance is a HOME form");
     static constexpr int RING = LDS::RING, QCAP = LDS::QCAP, DTN = LDS::DTN;
     static constexpr uint32_t RMASK = RING - 1, QMASK = QCAP - 1, DMASK = DTN - 1;
     static_assert((RING & (RING - 1)) == 0 && RING >= 1024 && (QCAP & (QCAP - 1)) == 0 && QCAP >= 128 && (DTN & (DTN - 1)) == 0, "sizes");
@@ -423,12 +427,13 @@ struct BpeWave {
                 const uint32_t c = sym_at(u, pos);
                 id = p.info[(int)(p.T[p.initial + c] >> SG_OW_SHIFT)].id;
             }
-            if (cnt == 0) first = id + p.id_offset; else { if (cnt == 1) home[0] = first; home[cnt] = id + p.id_offset; }
+            if (SPANS) home[pos] = id + p.id_offset;
+            else if (cnt == 0) first = id + p.id_offset; else { if (cnt == 1) home[0] = first; home[cnt] = id + p.id_offset; }
             ++cnt;
             pos = end + 1;
         }
         if (bad || cnt == 0) { unit_fallback(u, 6); return; }
-        if (cnt == 1) { if (HOME) home[0] = first; else S.q[(uint32_t)u.tok & QMASK].pos = (uint32_t)first; }
+        if (cnt == 1 && !SPANS) { if (HOME) home[0] = first; else S.q[(uint32_t)u.tok & QMASK].pos = (uint32_t)first; }
         unit_finish(u, cnt);
     }
     // the walk of the unit is over (ev): the whole word matched / go on collecting / all arcs collected
@@ -538,12 +543,13 @@ struct BpeWave {
                 const uint64_t e1 = p.T[p.initial + c];
                 id = p.info[(int)(e1 >> SG_OW_SHIFT)].id;
             } else id = id_of_order(id);
-            if (cnt == 0) first = id + p.id_offset; else { if (cnt == 1) home[0] = first; home[cnt] = id + p.id_offset; }
+            if (SPANS) home[pos] = id + p.id_offset;
+            else if (cnt == 0) first = id + p.id_offset; else { if (cnt == 1) home[0] = first; home[cnt] = id + p.id_offset; }
             ++cnt;
             pos = end + 1;
         }
         if (bad || cnt == 0) { unit_fallback(u, 6); return; }
-        if (cnt == 1) { if (HOME) home[0] = first; else S.q[(uint32_t)u.tok & QMASK].pos = (uint32_t)first; }
+        if (cnt == 1 && !SPANS) { if (HOME) home[0] = first; else S.q[(uint32_t)u.tok & QMASK].pos = (uint32_t)first; }
         unit_finish(u, cnt);
     }
     // Words with more arcs, one after the other by the whole wave: lane j takes arc j (BW_WIN <= 64), its rank among the keys from an
@@ -590,7 +596,7 @@ struct BpeWave {
             const int cnt = __builtin_popcountll(mt), k = __builtin_popcountll(mt & ((1ull << lane) - 1ull));
             if (wv::any(bad) || cnt == 0) { if (lane == o) unit_fallback(u, 6); wv::sync(); continue; }
             int32_t *home = p.ids_tmp + S.dt_slot[ke] + (int64_t)(rs - S.dt_rbase[ke]);
-            if (is_tok) { if (cnt == 1 && !HOME) S.q[(uint32_t)tok & QMASK].pos = (uint32_t)(idv + p.id_offset); else home[k] = idv + p.id_offset; }
+            if (is_tok) { if (cnt == 1 && !HOME) S.q[(uint32_t)tok & QMASK].pos = (uint32_t)(idv + p.id_offset); else home[SPANS ? lane : k] = idv + p.id_offset; }      // (lane = the piece's first position)
             wv::sync();
             if (lane == o) unit_finish(u, cnt);
             wv::sync();

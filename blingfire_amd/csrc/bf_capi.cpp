@@ -432,8 +432,13 @@ bool use_flat(const Handle *h, bool want_off, int words, int64_t ndocs, int64_t 
 }
 
 // the BPE wave program (bf_bpe_wave_body.h) in front of the lane-per-document kernels, for the models its load-time analysis admits
-// (Model::bpe_wave_ok); BfSetVariant bit 0x40 switches it off (A/B runs against the lane-per-document kernels alone)
-bool use_bpe_wave(const Handle *h, bool want_off) { return h->m.bpe_wave_ok && !want_off && !bpe_wave_knobs(h->variant).off; }
+// (Model::bpe_wave_ok); BfSetVariant bit 0x40 switches it off (A/B runs against the lane-per-document kernels alone).  The offsets calls take
+// the SPANS instance of a HOME tune (ids under their pieces' first elements -> k_bpe_home_spans); with the in-order tune they keep the lane kernels
+bool use_bpe_wave(const Handle *h, bool want_off)
+{
+    const BpeWaveKnobs bk = bpe_wave_knobs(h->variant);
+    return h->m.bpe_wave_ok && !bk.off && (!want_off || bpe_wave_home(bk.tune, EXPERIMENTS_BUILD));
+}
 
 // Words modes (TextToWords / TextToSentences): documents of more than `thresh` characters go through the long-document path
 // (bf_lex.h lex_one_start), which spends about three times the transitions of the lane kernel on a document of short words but spreads
@@ -714,7 +719,7 @@ StepTail enqueue_bpe_wave(const Step &st, const SpSegParams &sg)
     bw.ids_tmp = sg.ids_tmp; bw.counts = sg.counts; bw.flags = h->w_bwflags.as<int32_t>(); bw.max_ids = st.max_ids; bw.next_doc = sg.next_doc; bw.status = st.b.status;
     bw.scratch = (uint32_t *)sg.arcs; bw.stats = h->lex_stats ? h->misc()->stats : nullptr;
     st.record(EV_DOM0);
-    launch_bpe_wave(bw, bk.tune, s);
+    launch_bpe_wave(bw, bk.tune, st.want_off, s);
     st.record(EV_DOM1);
     launch_bpe_seg_flags(sg, bw.flags, h->w_perm.as<int32_t>(), h->w_hist.as<unsigned int>(), s);
     return StepTail{bpe_wave_home(bk.tune, EXPERIMENTS_BUILD) ? StepTail::BPE_HOME : StepTail::COMPACT, sg.slot_mul, nullptr};
@@ -792,6 +797,7 @@ int finish_step(const Step &st, const StepTail &t)
         if (b.ndocs > 0) launch_uni_ids(up, s);
     } else if (t.kind == StepTail::BPE_HOME) {
         BpeHomeParams hp{b, h->w_tmp.as<int32_t>(), h->w_nchars.as<int32_t>(), h->w_bwflags.as<int32_t>(), t.slot_mul, h->w_counts.as<int32_t>(), st.id_off, st.ids_out, st.ids_cap, st.max_ids, b.status};
+        if (st.want_off) { hp.span_tmp = h->w_span.as<int32_t>(); hp.src_off = h->w_srcoff.as<int32_t>(); hp.starts_out = st.starts; hp.ends_out = st.ends; }
         if (b.ndocs > 0) launch_bpe_home_gather(hp, s);
     } else if (b.ndocs > 0) {
         const bool want_off = st.want_off;
@@ -2921,7 +2927,8 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     // both forms of the WordPiece path: the wave program's workspaces and (words = 1 skips use_wave()'s early return) the class stream and flags of
     // the lane-per-document kernels, which TextToWords / TextToSentences, lexers outside the unit form and BfSetVariant(2) run -- no hipMalloc
     // (= device synchronisation) inside a later call of either kind
-    // want_offsets sizes the offsets API as well, not instead: a BPE model's ids-only call takes the wave program, whose hand-back flags the offsets path lacks
+    // want_offsets sizes the offsets API as well, not instead: the two calls of a model need not take the same program (a BPE model under the in-order
+    // tune: the ids-only call takes the wave program with its hand-back flags, the offsets call the lane kernels with their arc lists)
     if (!reserve_ids_workspaces(h, max_docs, max_bytes, false) || (want_offsets && !reserve_ids_workspaces(h, max_docs, max_bytes, true))) return BF_E_DEVICE;
     // (not the long-document workspace of the words modes, w_long: 40 .. 56 bytes per cell, allocated by the first words call that is that large)
     if (h->m.kind == KIND_WP && (!reserve_ids_workspaces(h, max_docs, max_bytes, true, 1, false) || !reserve_words_workspaces(h, max_docs, max_bytes, true))) return BF_E_DEVICE;
@@ -3176,7 +3183,7 @@ const char *BfStepKernels(void *p)
         return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_seg_unigram_lane, k_uni_back | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids (offsets: k_compact)";
     case KIND_I2W: case KIND_W2H: return "";
     default:
-        if (use_bpe_wave(h, false)) return bpe_wave_home(bpe_wave_knobs(h->variant).tune, EXPERIMENTS_BUILD) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather"
+        if (use_bpe_wave(h, false)) return bpe_wave_home(bpe_wave_knobs(h->variant).tune, EXPERIMENTS_BUILD) ? "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_bpe_home_gather (offsets: the spans instance of k_bpe_wave, k_bpe_home_spans)"
                                                                               : "prep: k_prep_sp8 | tokenise: k_bpe_wave, k_bpe_flag_list, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
         return "prep: k_prep_sp8 | tokenise: k_sp_hist, k_sp_hist_scan, k_sp_scatter, k_bpe_fused, k_bpe_collect_list, k_bpe_sort, k_bpe_apply_flat, k_bpe_seg | scan: k_scan_block_sums, k_scan_top, k_scan_apply | compact: k_compact_ids";
     }

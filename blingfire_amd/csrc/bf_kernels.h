@@ -160,8 +160,11 @@ void launch_uni_ids(const UniIdsParams &p, hipStream_t s);
 struct BpeHomeParams {
     Batch b; const int32_t *ids_tmp; const int32_t *lens; const int32_t *flags; int slot_mul;
     int32_t *counts; const int64_t *id_off; int32_t *ids_out; int64_t ids_cap; int max_ids; int *status;
+    // the offsets call (all four or none; k_bpe_home_spans): the (from, to) pairs k_bpe_seg staged for the documents handed back, k_prep_sp8's
+    // element -> source byte stream, the caller's arrays
+    const int32_t *span_tmp = nullptr; const int32_t *src_off = nullptr; int32_t *starts_out = nullptr, *ends_out = nullptr;
 };
-void launch_bpe_home_gather(const BpeHomeParams &p, hipStream_t s);
+void launch_bpe_home_gather(const BpeHomeParams &p, hipStream_t s);      // starts_out set: k_bpe_home_spans, the cells of the wave program's SPANS instance
 
 struct ScanParams { const int32_t *counts; int64_t ndocs; int64_t *id_off; int64_t *block_sums; int nblocks; };
 
@@ -189,7 +192,7 @@ void launch_wp_units(const WfUnitParams &p, const WpUnitsKnobs &k, hipStream_t s
 void launch_wp_hardlist(const int32_t *dstat, const int *unsafe, int64_t ndocs, int32_t *list, unsigned int *list_n, hipStream_t s);
 void launch_wp_count(const WfMergeParams &p, hipStream_t s);
 void launch_wp_merge(const WfMergeParams &p, hipStream_t s);
-void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s);                  // bpe-opt models (bf_bpe_wave_body.h); tune: bf_variant.h BPE_WAVE_TUNES
+void launch_bpe_wave(const BpeWaveParams &p, int tune, bool spans, hipStream_t s);      // bpe-opt models (bf_bpe_wave_body.h); tune: bf_variant.h BPE_WAVE_TUNES; spans: the SPANS instance (HOME tunes only)
 void launch_bpe_seg_flags(const SpSegParams &p, const int32_t *flags, int32_t *list, unsigned int *count, hipStream_t s);   // the documents it hands back: bf_bpe_seg_body.h
 void launch_prep_sp(const SpPrepParams &p, hipStream_t s);
 void launch_seg_sp(const SpSegParams &p, const SegKnobs &k, hipStream_t s);

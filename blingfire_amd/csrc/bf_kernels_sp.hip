@@ -4,7 +4,8 @@
 //              order of the documents (longest first).
 //  k_seg_unigram_lane, k_uni_back   Unigram-LM: forward pass (scores and the live window in LDS rings) and backward pass (bf_seg.h).
 //  k_bpe_wave, k_bpe_seg, k_bpe_*   BPE: the wave program with a word unit (bf_bpe_wave_body.h), one wave per document for any input
-//              (bf_bpe_seg_body.h), the lane kernels of plain BPE and the offsets API.
+//              (bf_bpe_seg_body.h), the gathers of the HOME form (ids: k_bpe_home_gather, ids + byte offsets: k_bpe_home_spans), the lane
+//              kernels of plain BPE.
 //  k_dict_*    FADictInterpreter_t::GetInfo for many keys.
 //  k_scan_*    exclusive scan of per-document counts -> offsets.
 //  k_compact*  gather of the per-document staging slots into one contiguous id array (+ byte offsets).
@@ -12,6 +13,7 @@
 //              NormalizeSpaces, TextToHashes: variable-length byte gathers and streaming kernels.
 #include "bf_kernels_common.h"
 #include "bf_bpe_wave_body.h"
+#include "bf_bpe_home.h"
 #include <utility>
 namespace bfa {
 
@@ -20,22 +22,22 @@ namespace bfa {
 // the documents it hands back (flags[d] = 1) are redone one wave each by k_bpe_seg (launch_bpe_seg_flags).
 __host__ __device__ __forceinline__ int64_t sp_slot(int64_t doc_off_d, int64_t d, int mul) { return (int64_t)mul * (doc_off_d + d); }
 
-template <class LDS, int WPE, int STEPS, int UMIN, bool HOME>
+template <class LDS, int WPE, int STEPS, int UMIN, bool HOME, bool SPANS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_bpe_wave(BpeWaveParams p, int grab)
 {
     __shared__ LDS lds[4];
-    BpeWave<LDS, STEPS, UMIN, HOME> w(p, lds[wave_in_block()]);
+    BpeWave<LDS, STEPS, UMIN, HOME, SPANS> w(p, lds[wave_in_block()]);
     w.run(grab, (int)(blockIdx.x * 4) + wave_in_block(), (int)(gridDim.x * 4));
 }
 
-template <int STEPS, int UMIN, int QCAP = 256, bool HOME = true>
+template <int STEPS, int UMIN, int QCAP = 256, bool HOME = true, bool SPANS = false>
 static void launch_bpe_wave_cfg(const BpeWaveParams &p, hipStream_t s)
 {
     typedef BwLds<1024, QCAP, 8> L;
     static int per_cu = 0;
     if (per_cu <= 0) {
         int q = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k_bpe_wave<L, 4, STEPS, UMIN, HOME>, 256, 0) != hipSuccess || q <= 0) q = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k_bpe_wave<L, 4, STEPS, UMIN, HOME, SPANS>, 256, 0) != hipSuccess || q <= 0) q = 2;
         (void)hipGetLastError();
         per_cu = q;
     }
@@ -45,23 +47,25 @@ static void launch_bpe_wave_cfg(const BpeWaveParams &p, hipStream_t s)
     const int64_t need = (p.ndocs + (int64_t)grab * 4 - 1) / ((int64_t)grab * 4);
     if (blocks > need) blocks = need;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL((k_bpe_wave<L, 4, STEPS, UMIN, HOME>), dim3((unsigned)blocks), dim3(256), 0, s, p, grab);
+    hipLaunchKernelGGL((k_bpe_wave<L, 4, STEPS, UMIN, HOME, SPANS>), dim3((unsigned)blocks), dim3(256), 0, s, p, grab);
 }
 
 // The instance bf_variant.h BPE_WAVE_TUNES names for `tune`, all with a queue of 256 words (queues of 512 / 1024 words cost a block per CU each:
 // 22.9 / 31.5 ms against 18.8).  An entry this build does not carry is the shipped one, like bpe_wave_home says of it.
+// `spans`: the SPANS instance of a HOME tune (the offsets calls; bf_capi.cpp use_bpe_wave asks for it with no other tune).
 template <int I>
-static void launch_bpe_wave_entry(const BpeWaveParams &p, hipStream_t s)
+static void launch_bpe_wave_entry(const BpeWaveParams &p, bool spans, hipStream_t s)
 {
     constexpr BpeWaveTune t = bpe_wave_tune(I, EXPERIMENTS_BUILD);
-    launch_bpe_wave_cfg<t.steps, t.umin, 256, t.home>(p, s);
+    if (t.home && spans) launch_bpe_wave_cfg<t.steps, t.umin, 256, t.home, t.home>(p, s);
+    else launch_bpe_wave_cfg<t.steps, t.umin, 256, t.home>(p, s);
 }
 template <int... I>
-static void launch_bpe_wave_by(int tune, const BpeWaveParams &p, hipStream_t s, std::integer_sequence<int, I...>)
+static void launch_bpe_wave_by(int tune, const BpeWaveParams &p, bool spans, hipStream_t s, std::integer_sequence<int, I...>)
 {
-    ((tune == I ? launch_bpe_wave_entry<I>(p, s) : (void)0), ...);
+    ((tune == I ? launch_bpe_wave_entry<I>(p, spans, s) : (void)0), ...);
 }
-void launch_bpe_wave(const BpeWaveParams &p, int tune, hipStream_t s) { launch_bpe_wave_by(tune & 15, p, s, std::make_integer_sequence<int, 16>{}); }
+void launch_bpe_wave(const BpeWaveParams &p, int tune, bool spans, hipStream_t s) { launch_bpe_wave_by(tune & 15, p, spans, s, std::make_integer_sequence<int, 16>{}); }
 
 // The HOME form of the BPE wave program leaves every id at its word's home -- a cell of the document's staging slot under the word's own elements,
 // BW_HOME_NONE in the cells between -- with the document's count (the program adds it up as the words report); this puts them where the API wants
@@ -96,12 +100,69 @@ __global__ __launch_bounds__(256) void k_bpe_home_gather(BpeHomeParams p)
     }
     if (over) atomicOr(p.status, 1);
 }
+
+// k_bpe_home_spans: the same gather for the offsets calls, on the cells of the wave program's SPANS instance (an id sits under its piece's first
+// element): id, first byte and last byte of every token (bf_bpe_home.h).  A wave per document, 128 cells per trip as above; a cell's `to` needs
+// the next id cell, which lies in its own block of 64 or in the one behind (a piece has at most BW_WORD_MAX elements) -- so a trip looks at three
+// masks, and the third block is the next trip's first: it is loaded once and carried.  Only the first c = min(count, max_ids) ids are written, but
+// the masks hold every id cell: the last kept token ends in front of the first dropped one.  A handed-back document takes k_compact's loop on the
+// dense ids and the (from, to) pairs k_bpe_seg staged.
+static_assert(BW_WORD_MAX <= BH_PIECE_MAX, "one block of look-ahead: a piece is no longer than a word of the wave program");
+__global__ __launch_bounds__(256) void k_bpe_home_spans(BpeHomeParams p)
+{
+    const int lane = lane_id();
+    const int64_t wave0 = (int64_t)blockIdx.x * 4 + wave_in_block();
+    const int64_t nwaves = (int64_t)gridDim.x * 4;
+    bool over = false;
+    for (int64_t d = wave0; d < p.b.ndocs; d += nwaves) {
+        int c = p.counts[d];
+        if (c <= 0) continue;
+        const int64_t o = p.id_off[d];
+        if (o + c > p.ids_cap) { over = true; c = o < p.ids_cap ? (int)(p.ids_cap - o) : 0; }
+        const int64_t b = p.b.doc_off[d], slot = sp_slot(b, d, p.slot_mul);
+        const int32_t *cell = p.ids_tmp + slot, *so = p.src_off + slot;
+        const uint8_t *text = p.b.text + b;
+        int32_t *out = p.ids_out + o, *starts = p.starts_out + o, *ends = p.ends_out + o;
+        if (p.flags[d]) {
+            const int32_t *span = p.span_tmp + 2 * slot;
+            for (int i = lane; i < c; i += 64) {
+                int first, last;
+                bh_bytes(so, text, span[2 * i], span[2 * i + 1], first, last);
+                out[i] = cell[i]; starts[i] = first; ends[i] = last;
+            }
+            continue;
+        }
+        const int L = p.lens[d];
+        int k = 0;
+        int32_t va = lane < L ? cell[lane] : BW_HOME_NONE;
+        for (int i0 = 0; i0 < L && k < c; i0 += 128) {
+            const int ib = i0 + 64 + lane, ic = i0 + 128 + lane;
+            const int32_t vb = ib < L ? cell[ib] : BW_HOME_NONE, vc = ic < L ? cell[ic] : BW_HOME_NONE;
+            const unsigned long long ma = __ballot(va != BW_HOME_NONE), mb = __ballot(vb != BW_HOME_NONE), mc = __ballot(vc != BW_HOME_NONE);
+            const int ka = k + __popcll(ma & lanemask_lt()), kb = k + __popcll(ma) + __popcll(mb & lanemask_lt());
+            if (va != BW_HOME_NONE && ka < c) {
+                int from, to, first, last;
+                bh_span(ma, mb, i0, lane, L, from, to); bh_bytes(so, text, from, to, first, last);
+                out[ka] = va; starts[ka] = first; ends[ka] = last;
+            }
+            if (vb != BW_HOME_NONE && kb < c) {
+                int from, to, first, last;
+                bh_span(mb, mc, i0 + 64, lane, L, from, to); bh_bytes(so, text, from, to, first, last);
+                out[kb] = vb; starts[kb] = first; ends[kb] = last;
+            }
+            k += __popcll(ma) + __popcll(mb);
+            va = vc;
+        }
+    }
+    if (over) atomicOr(p.status, 1);
+}
 void launch_bpe_home_gather(const BpeHomeParams &p, hipStream_t s)
 {
     int64_t blocks = (p.b.ndocs + 3) / 4;
     if (blocks > device_cus() * 16) blocks = device_cus() * 16;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_bpe_home_gather, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    if (p.starts_out) hipLaunchKernelGGL(k_bpe_home_spans, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(k_bpe_home_gather, dim3((unsigned)blocks), dim3(256), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------

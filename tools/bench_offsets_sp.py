@@ -1,18 +1,19 @@
-"""MEASUREMENT: the offsets step of the Unigram models (TextToIdsWithOffsetsBatchDevice) on text that is resident in HBM, beside the ids-only
-step (TextToIdsBatchDevice) on the same corpus and beside the same calls under BfSetVariant 6 (the forward / backward kernels of round 4 with
-k_compact), in one process.
+"""MEASUREMENT: the offsets step of the Unigram and BPE models (TextToIdsWithOffsetsBatchDevice) on text that is resident in HBM, beside the ids-only
+step (TextToIdsBatchDevice) on the same corpus and beside the same calls under the family's baseline variant -- Unigram: BfSetVariant 6 (the
+forward / backward kernels of round 4 with k_compact); BPE: 3 | 0x40 = 67 (the lane kernels with k_compact) -- in one process.
 
-Two workloads of tests/bfutil.py: config4 (xlm_roberta_base.bin) and config5 (laser500k.bin), `--docs` documents each.  Before anything is
-timed every id, first byte, last byte and id offset of the default call is compared with variant 6's on the whole corpus, and with the checker
+`--family unigram`: two workloads of tests/bfutil.py, config4 (xlm_roberta_base.bin) and config5 (laser500k.bin); `--family bpe`: config3
+(gpt2.bin), written to profiles/offsets_bpe_bench.json; `--docs` documents each.  Before anything is
+timed every id, first byte, last byte and id offset of the default call is compared with the baseline variant's on the whole corpus, and with the checker
 (the compiled reference where oracle/_ref is built, else the oracle) on every `--check-step`-th document.
 
 Timed, per variant (3 = the default, 6): a whole call in windows of at least `--window-seconds` (device events on the call's stream around a
 window, calls back to back), `--windows` windows, the variants and the two calls alternating; and the per-kernel split of one call from the
 events BfLastKernelMs reads (prep, tokenise, its dominant kernel, scan, compact), median of `--calls` calls.  `spread` is (max - min) / median
-of a series' windows.  `--lib` times another build of the library (the parent commit's) with the same script; `--parent` merges such a run's
+of a series' windows (the series' keys carry the baseline's number: ..._variant6, ..._variant67).  `--lib` times another build of the library (the parent commit's) with the same script; `--parent` merges such a run's
 file into this one's and states the three comparisons: offsets and ids-only against the parent, offsets over ids-only on this build.
 
-  python tools/bench_offsets_sp.py [--docs 1000000] [--windows 7] [--calls 11] [--lib OTHER.so] [--parent PARENT.json] [--out profiles/offsets_sp_bench.json]"""
+  python tools/bench_offsets_sp.py [--family unigram|bpe] [--docs 1000000] [--windows 7] [--calls 11] [--lib OTHER.so] [--parent PARENT.json] [--out profiles/offsets_sp_bench.json]"""
 import argparse
 import ctypes
 import json
@@ -26,10 +27,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 SEGMENTS = ("prep", "tokenise", "scan", "compact", "total", "dominant")
+FAMILIES = {"unigram": (("config4", "config5"), 6, "offsets_sp_bench.json"), "bpe": (("config3",), 3 | 0x40, "offsets_bpe_bench.json")}      # workloads, baseline variant, file
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--family", choices=sorted(FAMILIES), default="unigram")
     ap.add_argument("--docs", type=int, default=1000000)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--calls", type=int, default=11)
@@ -37,8 +40,10 @@ def main():
     ap.add_argument("--window-seconds", type=float, default=0.5)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--parent", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "offsets_sp_bench.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    workloads, base, out_name = FAMILIES[a.family]
+    a.out = a.out or os.path.join(ROOT, "profiles", out_name)
 
     import torch
     import bfutil
@@ -74,7 +79,7 @@ def main():
                 return ms / reps
 
     res = {"docs": a.docs, "library": a.lib or "this build", "device": torch.cuda.get_device_name(0), "window_seconds": a.window_seconds, "verified": True, "workloads": {}}
-    for name in ("config4", "config5"):
+    for name in workloads:
         wl = bfutil.WORKLOADS[name]
         mx, unk = wl["max_ids"], wl["unk"]
         text, off = bfutil.gen_workload(name, a.docs)
@@ -87,14 +92,14 @@ def main():
 
         # ---- verification: the default against variant 6, every element; against the checker, every check-step-th document
         got = {}
-        for v in (3, 6):
+        for v in (3, base):
             assert lib.BfSetVariant(VP(h), v) >= 0
             out = offs()
             torch.cuda.synchronize()
             assert lib.BfLastStatus(VP(h)) == 0
             got[v] = (out, lib.BfTokeniseKernel(VP(h)).decode())
         n = int(got[3][0][3][-1].item())
-        assert torch.equal(got[3][0][3], got[6][0][3]) and all(torch.equal(x[:n], y[:n]) for x, y in zip(got[3][0][:3], got[6][0][:3])), (name, "the default differs from variant 6")
+        assert torch.equal(got[3][0][3], got[base][0][3]) and all(torch.equal(x[:n], y[:n]) for x, y in zip(got[3][0][:3], got[base][0][:3])), (name, "the default differs from variant %d" % base)
         g_ids, g_st, g_en, g_off = (t.cpu().numpy() for t in got[3][0])
         hck = ck.load(bfutil.model_path(wl["model"]))
         raw = text.tobytes()
@@ -106,11 +111,11 @@ def main():
             checked += c
         ck.free(hck)
         kernels = {v: got[v][1] for v in got}
-        print("%s: %d documents, %d bytes, %d tokens: equal to variant 6; %d tokens equal to the checker; kernels %s" % (name, ndocs, total, n, checked, kernels), file=sys.stderr, flush=True)
+        print("%s: %d documents, %d bytes, %d tokens: equal to variant %d; %d tokens equal to the checker; kernels %s" % (name, ndocs, total, n, base, checked, kernels), file=sys.stderr, flush=True)
         del got, g_ids, g_st, g_en, raw
 
         # ---- timing: windows of whole calls, the series alternating; then the per-kernel split
-        series = [("offsets", 3, offs), ("offsets_variant6", 6, offs), ("ids", 3, ids_only), ("ids_variant6", 6, ids_only)]
+        series = [("offsets", 3, offs), ("offsets_variant%d" % base, base, offs), ("ids", 3, ids_only), ("ids_variant%d" % base, base, ids_only)]
         times = {k: [] for k, _, _ in series}
         split = {}
         for k, v, fn in series:
@@ -134,7 +139,7 @@ def main():
             out[k] = summary(times[k])
             out[k]["kernel_ms"] = split[k]
         out["offsets_over_ids"] = out["offsets"]["median_ms"] / out["ids"]["median_ms"]
-        out["offsets_over_variant6"] = out["offsets"]["median_ms"] / out["offsets_variant6"]["median_ms"]
+        out["offsets_over_variant%d" % base] = out["offsets"]["median_ms"] / out["offsets_variant%d" % base]["median_ms"]
         res["workloads"][name] = out
         bf.free_model(h)
         del d_text, d_off
