@@ -81,6 +81,10 @@ _SIGNATURES = {
     # the bucketed call: max_len, cls, sep, pad, multiple, max_cells, max_rows, flags; the planes and their cap, order, seq_pos, the per-batch arrays and their cap, counts
     "IdsToBucketedRowsBatch": (_L, [_P, _P, _P, _L] + [_I] * 5 + [_L, _I, _I, _P, _P, _L] + [_P] * 5 + [_L, _P]),
     "IdsToBucketedRowsBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 5 + [_L, _I, _I, _P, _P, _L] + [_P] * 5 + [_L, _P, _P]),
+    # the MinHash call: shingle, num_perm, band_rows, seed, flags; the signatures and their cap, band keys, shingle counts.  Pairs: sig, H, nseq, pairs, npairs, out
+    "IdsToMinHashBatch": (_L, [_P, _P, _P, _L] + [_I] * 3 + [c_uint64, _I, _P, _L, _P, _P]),
+    "IdsToMinHashBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 3 + [c_uint64, _I, _P, _L, _P, _P, _P]),
+    "MinHashPairsBatchDevice": (_I, [_P, _P, _I, _L, _P, _L, _P, _P]),
     "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
     "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
     "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
@@ -1118,6 +1122,70 @@ def bucketed_views(rows, mask, batch_first, batch_len, batch_cell, counts):
         if hi > len(rows):
             break
         yield rows[lo:hi].reshape(-1, L), mask[lo:hi].reshape(-1, L), slice(int(first[b]), int(first[b + 1]))
+
+
+def _minhash_args(num_perm, shingle, band_rows, seed):
+    return (int(shingle), int(num_perm), int(band_rows), int(seed) & 0xFFFFFFFFFFFFFFFF, 0)
+
+
+def _minhash_outs(nseq, num_perm, band_rows, new):
+    """sig, band_keys (None without bands), nshingles: new(shape, dtype) makes an array"""
+    H, r = int(num_perm), int(band_rows)
+    return [new((nseq, H), "int32"), new((nseq, H // r), "int64") if r > 0 else None, new((nseq,), "int32")]
+
+
+def ids_to_minhash_batch(h, ids, id_off, num_perm=128, shingle=5, band_rows=0, seed=0):
+    """additive: ragged ids (int32 array + int64 offsets[nseq+1]) -> MINHASH signatures over shingles of `shingle` consecutive ids
+    (IdsToMinHashBatch; the header has the specification, integer-only and bit-exact).  Returns (sig int32[nseq, num_perm], band_keys
+    int64[nseq, num_perm / band_rows] or None with band_rows = 0, nshingles int32[nseq]).  The share of equal slots of two rows estimates the
+    Jaccard similarity of their shingle sets; a sequence without ids has the row of all ones (-1)."""
+    name = "IdsToMinHashBatch"
+    ids, id_off, nseq = _host_ragged(ids, id_off)
+    outs = _minhash_outs(nseq, num_perm, band_rows, lambda shape, t: np.empty(shape, dtype=t))
+    a = [None if o is None else o.ctypes.data for o in outs]
+    r = getattr(lib(), name)(*_head(h, nseq, (ids, id_off)), *_minhash_args(num_perm, shingle, band_rows, seed), a[0], nseq, a[1], a[2])
+    _check(name, r, r == nseq, _COUNT)
+    return tuple(outs)
+
+
+def ids_to_minhash_batch_device(h, d_ids, d_id_off, num_perm=128, shingle=5, band_rows=0, seed=0, stream=None):
+    """Device-resident ids_to_minhash_batch: torch int32 ids + int64 offsets on one GPU (text_to_ids_batch_device's results as they are) ->
+    (sig, band_keys or None, nshingles) as tensors on that device, enqueued on torch's current stream (or `stream`); nothing is read back.
+    From band keys to candidate pairs takes three lines of torch (a recipe, not API): the band index is mixed into a key, so one sort of all
+    keys groups the candidates of every band, and equal neighbours are candidates --
+        k, order = band_keys.flatten().sort()
+        hit = (k[1:] == k[:-1]).nonzero().squeeze(1)
+        pairs = torch.stack((order[hit], order[hit + 1]), 1) // band_keys.shape[1]
+    -- then minhash_pairs_device(h, sig, pairs) counts the equal slots of each pair."""
+    import torch
+    name = "IdsToMinHashBatchDevice"
+    dev = d_ids.device
+    nseq = d_id_off.numel() - 1
+    outs = _minhash_outs(nseq, num_perm, band_rows, lambda shape, t: torch.empty(shape, dtype=getattr(torch, t), device=dev))
+    r = getattr(lib(), name)(*_head(h, nseq, (d_ids, d_id_off)), *_minhash_args(num_perm, shingle, band_rows, seed), outs[0].data_ptr(), nseq, _dev_addr(outs[1]),
+                             outs[2].data_ptr(), _stream_arg(stream, dev))
+    _check(name, r, r == 0)
+    return tuple(outs)
+
+
+def minhash_pairs_device(h, sig, pairs, stream=None):
+    """equal slots of candidate pairs (MinHashPairsBatchDevice): sig = int32[nseq, H] signatures and pairs = int64[npairs, 2] row indices, torch
+    tensors on one GPU -> int32[npairs]; divided by H, the Jaccard estimate of each pair.  A pair with an index outside [0, nseq) gives -1
+    (BfLastStatus bit 3)."""
+    import torch
+    name = "MinHashPairsBatchDevice"
+    sig, pairs = sig.contiguous(), pairs.contiguous()
+    out = torch.empty(pairs.shape[0], dtype=torch.int32, device=sig.device)
+    r = getattr(lib(), name)(c_void_p(h), sig.data_ptr(), sig.shape[1], sig.shape[0], pairs.data_ptr(), pairs.shape[0], out.data_ptr(), _stream_arg(stream, sig.device))
+    _check(name, r, r == 0)
+    return out
+
+
+def encode_minhash_batch_device(h, d_text, d_doc_off, max_len, num_perm=128, shingle=5, band_rows=0, seed=0, unk=0):
+    """Text in HBM -> MinHash signatures, nothing on the host: text_to_ids_batch_device (every document tokenised up to max_len ids) and
+    ids_to_minhash_batch_device on one stream.  Returns what ids_to_minhash_batch_device returns."""
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_len), unk)
+    return ids_to_minhash_batch_device(h, d_ids, d_id_off, num_perm, shingle, band_rows, seed)
 
 
 def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,

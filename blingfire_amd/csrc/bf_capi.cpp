@@ -115,9 +115,9 @@ struct PinBuf {
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
 //                            calls on one handle).  Nobody keeps a list of entry points here: begin_launch() is called by the drivers they all go
 //                            through -- run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_i2t_host and
+//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_minhash_device, run_i2t_host and
 //                            IdsToTextBatchDevice -- and by rows_call(), the prologue of every Rows...BatchDevice entry point (span cells, MLM mask,
-//                            MLM predictions, denoise).  The host forms reach
+//                            MLM predictions, denoise) and of MinHashPairsBatchDevice.  The host forms reach
 //                            it through the Device drivers they call.  The fill passes of the two-pass calls keep the size pass's words.
 //                            NormalizeSpacesBatch and TextToHashesBatch run on a handle of the library's own (util_handle) that no caller can ask for
 //                            its status, and their kernels use none of the words: they clear nothing.
@@ -218,6 +218,7 @@ struct Handle {
     DevBuf w_plsrc[2][ROWS_MAX_PLANES], w_plout[ROWS_MAX_PLANES]; // IdsToRowsPlanesBatch / IdsToPairRowsPlanesBatch, host forms: the staged companion arrays of each side, the planes
     DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
     DevBuf w_bkkey[2], w_bkval[2], w_bkcnt, w_bkbase;            // IdsToBucketedRowsBatch (bf_kernels.h BucketParams): the sort's records, a pass's digit counts, their scan
+    DevBuf w_mhab;                                               // IdsToMinHashBatch (bf_kernels.h MinhashParams): a_i, b_i of the permutations, 4 KiB
     DevBuf w_cplead, w_cpfour, w_cpcnt, w_cpP;                  // Byte / CharToByteOffsetsBatchDevice (bf_kernels.h CharposParams): the two masks, the weights, P -- 28 bytes per 64 bytes of text
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
@@ -1788,6 +1789,67 @@ int64_t run_bucket_host(Handle *h, const int32_t *ids, const int64_t *id_off, in
     return hip_ok(hipStreamSynchronize(s), "hipStreamSynchronize") ? total : BF_E_DEVICE;
 }
 
+// IdsToMinHashBatch on device buffers (bf_kernels_minhash.hip).  The lengths, their block sums and W are the packed stage's workspaces (16 bytes
+// per sequence of the 36 that stage reserves); its own workspace is the parameters a_i, b_i: MINHASH_PARAM_BYTES = 4096 bytes, whatever the batch.
+bool reserve_minhash_workspaces(Handle *h, int64_t nseq) { return reserve_packed_workspaces(h, nseq) && h->w_mhab.reserve(MINHASH_PARAM_BYTES); }
+
+// parameters, lengths, scan, the all-ones rows, then the signature kernel and -- when keys are taken -- the band keys.  The launches depend on
+// nseq, ids_len, sig_cap and on which outputs are taken, never on the data.  A refused argument touches neither the device nor the status word.
+int run_minhash_device(Handle *h, const MinhashSpec &spec, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_off, int64_t nseq, int32_t *d_sig, int64_t sig_cap,
+                       int64_t *d_keys, int32_t *d_nshingles, hipStream_t s)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || sig_cap < 0 || ids_len < 0 || !d_id_off || (ids_len > 0 && !d_ids)) return BF_E_ARG;
+    const int64_t rows = nseq < sig_cap ? nseq : sig_cap;
+    if ((rows > 0 && !d_sig) || (d_keys && spec.r == 0)) return BF_E_ARG;
+    if (!reserve_minhash_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    MinhashParams p;
+    p.spec = spec; p.ids = d_ids; p.ids_len = ids_len; p.id_off = d_id_off; p.nseq = nseq; p.status = &h->misc()->status;
+    p.lens = h->w_counts.as<int32_t>(); p.W = h->w_pkW.as<int64_t>(); p.ab = h->w_mhab.as<uint32_t>();
+    p.sig = (uint32_t *)d_sig; p.sig_cap = sig_cap; p.keys = d_keys; p.nshingles = d_nshingles;
+    // the events BfLastKernelMs reads: [0] parameters, lengths, scan and the all-ones rows, [1] and [5] the signature kernel, [2] nothing, [3] the band keys
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (nseq > 0) {
+        launch_minhash_prepare(p, s);
+        scan_counts(h, nseq, h->w_pkW.as<int64_t>(), s);
+        if (rows > 0) launch_minhash_init(p, s);
+    }
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    if (rows > 0 && ids_len > 0) launch_minhash_sig(p, s);
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    if (rows > 0 && d_keys) launch_minhash_bands(p, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "IdsToMinHash kernels") ? 0 : BF_E_DEVICE;
+}
+
+// IdsToMinHashBatch on host buffers: the ids through stage_ragged, then count_fill_host.  The row count is nseq, known in advance: the size
+// pass runs the length kernel alone (sig_cap = 0) and answers nshingles; the fill pass writes the signatures and the keys into their stagings.
+int64_t run_minhash_host(Handle *h, const int32_t *ids, const int64_t *id_off, int64_t nseq, const MinhashSpec &spec, int32_t *sig_out, int64_t sig_cap,
+                         int64_t *keys_out, int32_t *nshingles_out)
+{
+    if (nseq < 0 || nseq > 0x7fffffff || sig_cap < 0 || !id_off || (keys_out && (spec.r == 0 || !sig_out))) return BF_E_ARG;
+    const int64_t ids_len = host_side_len(id_off, nseq);
+    if (ids_len < 0 || (ids_len > 0 && !ids)) return BF_E_ARG;
+    std::lock_guard<std::mutex> dlock(h->defer_mu);
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    hipStream_t s = h->stream;
+    const size_t seq_bytes = (size_t)nseq * 4;
+    if (!h->w_starts.reserve(seq_bytes + 16)) return BF_E_DEVICE;
+    Staged st;
+    const int rc = stage_ragged(st, ids, 4, id_off, nseq, h->w_ids, h->w_docoff, s, ids_len);
+    if (rc != 0) return rc;
+    const RowOut outs[ROW_HOST_OUTS] = {{sig_out, &h->w_out, (size_t)spec.H * 4, "D2H signatures"}, {keys_out, &h->w_vals, (size_t)spec.B * 8, "D2H band keys"}};
+    const int64_t R = nseq;
+    return count_fill_host(s, {{nshingles_out, &h->w_starts, seq_bytes, "D2H shingle counts"}}, &R, outs, sig_cap, false, [&](void *const d[ROW_HOST_OUTS], int64_t cap) {
+        return run_minhash_device(h, spec, h->w_ids.as<int32_t>(), ids_len, h->w_docoff.as<int64_t>(), nseq, (int32_t *)d[0], d[0] ? cap : 0, (int64_t *)d[1],
+                                  nshingles_out ? h->w_starts.as<int32_t>() : nullptr, s); });
+}
+
 // IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
 // outputs the caller takes -- the fill.  The launches depend on nseq and on which outputs are taken, never on the data; the workspaces are the
 // first three of the packed stage (reserve_packed_workspaces): nothing here is sized by the row count.
@@ -2744,6 +2806,36 @@ int64_t IdsToBucketedRowsBatch(void *p, const int32_t *ids, const int64_t *id_of
                            counts_out);
 }
 
+/* ---- additive: MinHash signatures and LSH band keys over shingles of ids (bf_minhash.h); the equal slots of candidate pairs */
+int IdsToMinHashBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int shingle, int num_perm, int band_rows,
+                            uint64_t seed, int flags, int32_t *d_sig_out, int64_t sig_cap, int64_t *d_band_keys_out, int32_t *d_nshingles_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    MinhashSpec spec;
+    if (!h || !minhash_spec(shingle, num_perm, band_rows, seed, flags, &spec)) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_minhash_device(h, spec, d_ids, ids_len, d_id_offsets, nseq, d_sig_out, sig_cap, d_band_keys_out, d_nshingles_out, (hipStream_t)stream);
+}
+
+int64_t IdsToMinHashBatch(void *p, const int32_t *ids, const int64_t *id_offsets, int64_t nseq, int shingle, int num_perm, int band_rows, uint64_t seed, int flags,
+                          int32_t *sig_out, int64_t sig_cap, int64_t *band_keys_out, int32_t *nshingles_out)
+{
+    Handle *h = as_handle(p);
+    MinhashSpec spec;
+    if (!h || !minhash_spec(shingle, num_perm, band_rows, seed, flags, &spec)) return BF_E_ARG;
+    return run_minhash_host(h, ids, id_offsets, nseq, spec, sig_out, sig_cap, band_keys_out, nshingles_out);
+}
+
+int MinHashPairsBatchDevice(void *p, const int32_t *d_sig, int num_perm, int64_t nseq, const int64_t *d_pairs, int64_t npairs, int32_t *d_equal_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h || num_perm < 1 || num_perm > MINHASH_MAX_PERM || nseq < 0 || npairs < 0 || (npairs > 0 && (!d_pairs || !d_equal_out)) || (npairs > 0 && nseq > 0 && !d_sig))
+        return BF_E_ARG;
+    return rows_call(h, stream, npairs, "MinHashPairs kernel", [&](hipStream_t s) {
+        launch_minhash_pairs(MinhashPairsParams{(const uint32_t *)d_sig, num_perm, nseq, d_pairs, npairs, d_equal_out, &h->misc()->status}, s); });
+}
+
 /* ---- additive: packed rows with companion planes (k_packed_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */
 int IdsToPackedRowsPlanesBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
                                      int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
@@ -2920,6 +3012,7 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     if (!reserve_rows_workspaces(h, max_docs)) return BF_E_DEVICE;                                   // IdsToRowsBatchDevice, any handle: documents = sequences
     if (!reserve_packed_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToPackedRowsBatchDevice, any handle
     if (!reserve_bucket_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToBucketedRowsBatchDevice, any handle
+    if (!reserve_minhash_workspaces(h, max_docs)) return BF_E_DEVICE;                                // IdsToMinHashBatchDevice, any handle
     if (!reserve_charpos_workspaces(h, max_bytes)) return BF_E_DEVICE;                               // Byte / CharToByteOffsetsBatchDevice, any handle: sized by the text alone
     if (h->m.kind == KIND_I2W) return 0;                                                            // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words

@@ -14,6 +14,7 @@
 #include "bf_packed.h"
 #include "bf_bucket.h"
 #include "bf_stream.h"
+#include "bf_minhash.h"
 #include "bf_mlm.h"
 #include "bf_denoise.h"
 #include "bf_charpos.h"
@@ -436,6 +437,24 @@ void launch_bucket_first(const BucketParams &p, hipStream_t s);                 
 void launch_bucket_lens(const BucketParams &p, hipStream_t s);                  // row_len
 void launch_bucket_batches(const BucketParams &p, hipStream_t s);               // behind the scan of row_len: the per-batch outputs, the counts, status bit 0
 void launch_bucket_fill(const BucketParams &p, hipStream_t s);                  // the two planes
+// IdsToMinHashBatch (additive; bf_minhash.h has the lane code and the split, bf_kernels_minhash.hip the kernels): MinHash signatures over shingles
+// of ids, LSH band keys.  The lengths and W are the packed stage's workspaces; rows at or beyond sig_cap are never written.
+struct MinhashParams {
+    MinhashSpec spec;
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    int32_t *lens; const int64_t *W;             // [nseq] the ids of a sequence (0 for a bad range); [nseq + 1] their exclusive scan
+    uint32_t *ab;                                // [H][4] a lo, a hi, b lo, b hi (MINHASH_PARAM_BYTES)
+    uint32_t *sig; int64_t sig_cap;              // [sig_cap, H]
+    int64_t *keys;                               // [sig_cap, B] or NULL
+    int32_t *nshingles;                          // [nseq] or NULL
+};
+void launch_minhash_prepare(const MinhashParams &p, hipStream_t s);             // the parameters; lens, nshingles, status bits 0 and 3
+void launch_minhash_init(const MinhashParams &p, hipStream_t s);                // behind the scan of the lengths: the all-ones rows
+void launch_minhash_sig(const MinhashParams &p, hipStream_t s);                 // the signatures, a tile of the id stream per wave
+void launch_minhash_bands(const MinhashParams &p, hipStream_t s);               // the band keys from the finished signatures
+// MinHashPairsBatchDevice: the equal slots of two signature rows
+struct MinhashPairsParams { const uint32_t *sig; int H; int64_t nseq; const int64_t *pairs; int64_t npairs; int32_t *equal; int *status; };
+void launch_minhash_pairs(const MinhashPairsParams &p, hipStream_t s);
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

@@ -558,6 +558,56 @@ BF_API int64_t IdsToBucketedRowsBatch(void *ModelPtr, const int32_t *ids, const 
                                int32_t *batch_first_out, int32_t *batch_len_out, int64_t *batch_cell_out, int64_t batches_cap,
                                int64_t *counts_out);
 
+/* additive (no counterpart in the reference; this comment is the specification): MINHASH signatures over shingles of token ids, and LSH band
+ * keys -- near-duplicate detection of a corpus on the ids the tokenizer calls leave on the device.  Integer-only, so bit-exact by specification.
+ * All arithmetic is unsigned and wraps; an id enters as (uint32)id.
+ * Shingles.  Sequence q of nseq = ids[off[q] .. off[q+1]), n ids; a range outside [0, ids_len] or with decreasing offsets is read as empty and sets
+ * BfLastStatus bit 3, as in IdsToRowsBatchDevice (so is a sequence of more than INT32_MAX - 2 ids).  With k = shingle, 1 <= k <= 8: n >= k gives
+ * n - k + 1 shingles, one at every start p over t[p .. p + k); 0 < n < k gives one shingle over all n ids; n = 0 gives none.
+ * d_nshingles_out[q] (int32, may be NULL) = that count.
+ * Shingle hash.  s = (uint32)seed; for each id of the shingle in order s = fmix32((s ^ id) + 0x9E3779B9), where fmix32 is the MurmurHash3
+ * finalizer: h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16.
+ * Permutation i, 0 <= i < H = num_perm, 1 <= H <= 256.  w = philox4x32_10(counter = {i, 0, 0, 0x4D48}, key = {seed low word, seed high word}),
+ * the generator of RowsMlmMaskBatchDevice; a_i = ((uint64)w[1] << 32 | w[0]) | 1; b_i = (uint64)w[3] << 32 | w[2];
+ * h_i(s) = (uint32)((a_i * (uint64)s + b_i) >> 32) -- multiply-shift universal hashing (Dietzfelbinger).
+ * Signature.  d_sig_out[q * H + i] = the minimum over the shingles of q of h_i(s), 0xFFFFFFFF with no shingles, stored as int32 bit patterns.
+ * The share of equal slots of two rows estimates the Jaccard similarity of their shingle sets with standard deviation sqrt(J (1 - J) / H).
+ * Band keys (d_band_keys_out, may be NULL; band_rows = r > 0 must divide H, B = H / r; r = 0 = no keys, and a non-NULL d_band_keys_out is then
+ * BF_E_ARG).  d_band_keys_out[q * B + b] starts at x = seed ^ ((uint64)(b + 1) * 0x9E3779B97F4A7C15); for each of the band's r signature words v
+ * (sig[q][b * r .. b * r + r)) in order x = fmix64(x ^ v), where fmix64 is the MurmurHash3 64-bit finalizer: x ^= x >> 33;
+ * x *= 0xFF51AFD7ED558CCD; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53; x ^= x >> 33.  The band index is mixed into the key: one sort of all keys
+ * groups the candidates and never confuses bands.
+ * Caps.  Rows q >= sig_cap of d_sig_out and d_band_keys_out are not written; nseq > sig_cap with d_sig_out taken sets BfLastStatus bit 0 (the call
+ * clears the status word first).  d_nshingles_out is always complete.
+ * BF_E_ARG for shingle outside 1 .. 8, num_perm outside 1 .. 256, band_rows < 0 or not dividing num_perm, flags != 0 (reserved), nseq < 0 or
+ * nseq > INT32_MAX, sig_cap < 0, ids_len < 0, a NULL ModelPtr (any live handle of any kind serves: the model is not consulted), a NULL
+ * d_id_offsets, a NULL d_ids with ids_len > 0, a NULL d_sig_out with min(nseq, sig_cap) > 0.  A refused call touches neither the device nor the
+ * status word.  nseq = 0 is a valid call that writes nothing.
+ * Device form: enqueues on `stream` (a hipStream_t), does not synchronise, reads nothing back, returns 0 or BF_E_*.  After
+ * BfReserve(h, max_docs >= nseq, ...) it allocates nothing, the first call included (its own workspace is 4096 bytes of parameters; the lengths
+ * and their scan are the packed stage's).  The kernels it launches depend on the sizes and on which outputs are taken, never on the data.  The
+ * ids of all sequences laid end to end are cut into tiles of 1024 positions and a wave takes a tile, so the time of a batch does not follow
+ * its longest sequence; a sequence that spans a tile's edge is combined with 32-bit atomic min, which is associative and commutative: the
+ * output is byte-identical from run to run.
+ * Host form: stages the ids like IdsToRowsBatch (id_offsets[0] < 0 = BF_E_ARG) and returns nseq.  With sig_out NULL it is a query that fills
+ * nshingles_out alone (band_keys_out without sig_out is BF_E_ARG); otherwise nseq > sig_cap returns BF_E_CAPACITY with nshingles_out complete and
+ * nothing else written.
+ * Not here: shingles of text or bytes; grouping candidates into clusters; sharding; H > 256. */
+BF_API int IdsToMinHashBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                            int shingle, int num_perm, int band_rows, uint64_t seed, int flags,
+                            int32_t *d_sig_out, int64_t sig_cap, int64_t *d_band_keys_out, int32_t *d_nshingles_out, void *stream);
+BF_API int64_t IdsToMinHashBatch(void *ModelPtr, const int32_t *ids, const int64_t *id_offsets, int64_t nseq,
+                          int shingle, int num_perm, int band_rows, uint64_t seed, int flags,
+                          int32_t *sig_out, int64_t sig_cap, int64_t *band_keys_out, int32_t *nshingles_out);
+
+/* additive: the equal slots of candidate pairs.  d_sig = int32 [nseq, num_perm] signatures on the device (IdsToMinHashBatchDevice's), d_pairs =
+ * int64 [npairs][2] row indices; d_equal_out[j] (int32) = the number of i < num_perm with sig[a][i] == sig[b][i] -- divided by num_perm, the
+ * Jaccard estimate of the pair.  A pair with an index outside [0, nseq) gives -1 in its cell and sets BfLastStatus bit 3 (the call clears the
+ * word first).  BF_E_ARG for num_perm outside 1 .. 256, nseq < 0, npairs < 0, a NULL ModelPtr, and with npairs > 0 a NULL d_pairs or d_equal_out
+ * or, with nseq > 0, a NULL d_sig.  Enqueues one kernel on `stream`, allocates nothing, reads nothing back; returns 0 or BF_E_*. */
+BF_API int MinHashPairsBatchDevice(void *ModelPtr, const int32_t *d_sig, int num_perm, int64_t nseq, const int64_t *d_pairs, int64_t npairs,
+                            int32_t *d_equal_out, void *stream);
+
 /* additive (no counterpart in the reference; this comment is the specification): STREAM rows -- "concatenate and chunk", the input of causal-LM
  * pretraining: every sequence closed by its specials, all of them laid end to end, the stream cut into rows of exactly row_len cells, with
  * next-token labels, a segment plane and a position plane.  Where IdsToPackedRowsBatch truncates a sequence longer than a row and never splits
@@ -751,22 +801,24 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * over the text, [2] the scan of the chunk counts, [3] the per-document and the per-item kernel, [4] total ([1] and [5] are 0).
  * After IdsToBucketedRowsBatchDevice: [0] widths and keys, [1] the sort passes, [2] the chain, the scans and the per-batch outputs, [3] the fill,
  * [4] total, [5] the scatter kernel of the last pass alone (with max_len <= 255, one pass, that is every scatter kernel there is).
+ * After IdsToMinHashBatchDevice: [0] parameters and initialisation (a_i, b_i, lengths, their scan, the all-ones rows), [1] the signature kernel,
+ * [3] the band keys, [4] total ([2] is 0, [5] equals [1]).
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
  * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, bucketed, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
- * and CharToByteOffsetsBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
+ * and CharToByteOffsetsBatchDevice, IdsToMinHashBatch, IdsToMinHashBatchDevice and MinHashPairsBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
  * no status.
  * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow (RowsDenoiseBatchDevice: a row longer than enc_len / dec_len; IdsToBucketedRowsBatchDevice: cells
- * beyond cells_cap or batches beyond batches_cap of an output the caller takes); bit 1 (2) and bit 4 (16) = an internal
+ * beyond cells_cap or batches beyond batches_cap of an output the caller takes; IdsToMinHashBatchDevice: sequences beyond sig_cap); bit 1 (2) and bit 4 (16) = an internal
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
  * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
  * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
- * [0, ids_len]; the span cells: a row whose item is out of range; the offset conversions: also a position beyond its document).  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
+ * [0, ids_len]; the span cells: a row whose item is out of range; the offset conversions: also a position beyond its document; MinHashPairsBatchDevice: a pair with an index outside [0, nseq)).  Per-document, the rest of the batch is valid: bit 5 (32) = a BPE document on which the reference itself does not
  * terminate (a skipped start position left without an arc, FATokenSegmentationTools_1best_bpe_t.h:299-313) got 0 ids; bit 6 (64) = a
  * BPE document's arcs did not fit the pool and it got 0 ids (only the ...BatchDevice forms: the host-buffer calls grow the pool and
  * run again; BfSetBpePoolBytes). */
@@ -788,7 +840,8 @@ BF_API int BfModelKind(void *ModelPtr);
  * The packed stage's workspaces also cover IdsToPackedRowsPlanesBatchDevice (one kernel behind the base call's, over what that call left
  * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
  * bound).  IdsToBucketedRowsBatchDevice borrows the packed stage's workspaces and adds its sort's: 17.5 bytes per sequence (two key and two
- * value arrays, and 12 bytes of digit counts per 8 sequences), on every kind of handle.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
+ * value arrays, and 12 bytes of digit counts per 8 sequences), on every kind of handle.  IdsToMinHashBatchDevice borrows the packed stage's
+ * lengths, block sums and W and adds 4096 bytes for the parameters of its permutations, on every kind of handle; MinHashPairsBatchDevice has no workspace.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
  * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
  * Every kind of handle also gets the index of ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice, sized from max_bytes alone (28 bytes per
  * 64 bytes of text, and the scan's block sums for that many chunks): after that the two calls allocate nothing, the first one included.
