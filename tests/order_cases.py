@@ -24,7 +24,15 @@ base call, as IdsToPackedRowsPlanesBatchDevice wide and narrow (a NULL plane amo
 borrows the packed stage's widths, block sums and W, with many sequences and few, cut by rows_cap (status 1), with a bad range (status 8) and as
 its host form; the host form of the rows-planes call, which owns the plane staging buffers the stream host form puts its labels in; the base MLM
 kernel beside RowsMlmPredictionsBatchDevice with max_pred > 0 (the capped kernel) and == 0 (the base kernel again); and RowsDenoiseBatchDevice
-with status 0 and with the status 1 its kernel sets by an atomic -- every one of them in front of and behind every other.
+with status 0 and with the status 1 its kernel sets by an atomic -- every one of them in front of and behind every other.  `ragged`, on a third
+WordPiece handle, is the catalogue of the calls that own no state: IdsToBucketedRowsBatchDevice (the packed stage's chain and scan workspaces, w_counts
+as its row lengths, w_bsums sized by digit bins and by sequences within one call) wide on the big batch, narrow and cut by both caps (status 1), with
+a bad range (status 8), as a size query and as its host form; IdsToMinHashBatchDevice (w_counts, w_pkW) over many tiles, cut by sig_cap, with a bad
+range and as its host form, and MinHashPairsBatchDevice with and without a pair out of range; the two offset conversions, which size w_bsums by
+64-byte chunks of text, over the big text, with a position beyond its document (status 8) and with doc_units alone -- between the tokenizer
+calls that feed them and the packed, stream and rows stages whose workspaces they borrow (restatements: bucketed_cases, minhash_cases,
+charpos_cases).  unigram and bpe take their offsets under two variants each: the cut form beside the lane program, the wave program's HOME /
+SPANS form beside the lane kernels, both pairs of steps with one answer.
 
 The status a step wants is stated where the step is built, with its reason: 0, 1 (bit 0: its capacity was below the need), 8 (bit 3: a range outside
 the input) and, for IdsToText alone, 4 (bit 2: a sequence with an unknown id).  Bit 6 (the BPE pool too small) stays out: the pool only grows, so
@@ -35,8 +43,11 @@ import numpy as np
 
 import bfutil
 import blingfire_amd as bf
+import bucketed_cases
+import charpos_cases
 import denoise_cases
 import flat_cases
+import minhash_cases
 import mlm_cases
 import mlmcap_cases
 import packed_cases
@@ -255,8 +266,9 @@ def set_host_chunk(h, nbytes):
     assert f(VP(h), nbytes) >= 0
 
 
-def tok_device_step(name, size, inputs, ans, variant, pair, cap=None, status=0, why="status 0: ids_cap is the exact total, every range inside the text"):
-    """TextToIdsBatchDevice, or TextToIdsWithOffsetsBatchDevice when `ans` carries byte offsets, with ids_cap == cap (default: the exact total)"""
+def tok_device_step(name, size, inputs, ans, variant, pair, cap=None, status=0, why="status 0: ids_cap is the exact total, every range inside the text", share=None):
+    """TextToIdsBatchDevice, or TextToIdsWithOffsetsBatchDevice when `ans` carries byte offsets, with ids_cap == cap (default: the exact total).
+    share: a step over the same inputs, answer and cap under another variant, whose wanted arrays this one takes as they are -- one answer, two programs"""
     text, off = inputs
     ids, st, en, ido = ans
     nd, with_off = len(off) - 1, st is not None
@@ -264,6 +276,9 @@ def tok_device_step(name, size, inputs, ans, variant, pair, cap=None, status=0, 
     where = ("docs", ido)
     want = [Want("ids", padded(ids, cap), where)] + ([Want("first bytes", padded(st, cap), where), Want("last bytes", padded(en, cap), where)] if with_off else [])
     want.append(Want("id offsets", ido))
+    if share is not None:
+        assert [w.label for w in share.want] == [w.label for w in want] and all(np.array_equal(a.array, b.array) for a, b in zip(share.want, want))
+        want = share.want
 
     def call(h, cx):
         set_variant(h, variant)
@@ -276,7 +291,9 @@ def tok_device_step(name, size, inputs, ans, variant, pair, cap=None, status=0, 
         else:
             r = L.TextToIdsBatchDevice(VP(h), cx.ptr(text), cx.ptr(off), nd, len(text), outs[0].data_ptr(), cap, o.data_ptr(), pair[0], pair[1], cx.stream)
         return r, outs + [o]
-    return Step(name, call, want, 0, status, why, size)
+    step = Step(name, call, want, 0, status, why, size)
+    step.variant = variant
+    return step
 
 
 def host_batch_step(name, size, ans, variant, pair, chunk=HOST_CHUNK_DEFAULT, why="status 0: the capacity is the exact total"):
@@ -704,6 +721,138 @@ def denoise_truncated_step(name, size, ids, ido, L=12):
     return denoise_step(name, size, rows, seg, L, L, DENOISE_TRUNCATED_DEC, 1, "status 1: a row's decoder targets are longer than dec_len (bit 0, set by the kernel's atomic)")
 
 
+# ---- the calls over ragged ids and text that borrow the packed stage's workspaces or size w_bsums their own way: bucketed rows, MinHash, offsets in characters
+BUCKET_OUTS = ("rows", "mask", "order", "seq_pos", "first", "len", "cell", "counts")
+BUCKET_TILE = 2048                                       # bf_bucket.h: the records a block of the sort owns in one pass
+
+
+def bucketed_answer(ids, off, max_len, multiple, max_cells):
+    """bucketed_cases.restate with [CLS], [SEP] and the padding id, once per input"""
+    def compute():
+        ans = bucketed_cases.restate(ids, off, max_len, CLS, SEP, PAD, multiple, max_cells)
+        frozen(*ans.values())
+        return (ids, off), ans
+    return memo(("bucketed answer", id(ids), id(off), max_len, multiple, max_cells), compute)[1]
+
+
+def bucketed_step(name, size, ids, off, max_len, multiple, max_cells, cells_cap=None, batches_cap=None, narrow=False, query=False, host=False, status=0,
+                  why="status 0: every id range inside [0, ids_len], both caps are the exact counts"):
+    """IdsToBucketedRowsBatchDevice with all eight outputs, or (host) IdsToBucketedRowsBatch into numpy buffers, which returns the cell total; a cap
+    None = the exact count.  narrow: d_rows_out begins 4 bytes behind a 16-byte boundary, one sentinel entry into its buffer, so the fill stores
+    cell by cell (aligned planes and multiple % 4 == 0 take the wide stores); query: both planes NULL.  No cell at or past cells_cap and no entry past
+    min(B, batches_cap) of a per-batch array is written: `want` holds the sentinel there"""
+    nseq = len(off) - 1
+    ans = bucketed_answer(ids, off, max_len, multiple, max_cells)
+    B, C = (int(x) for x in ans["counts"])
+    ccap = (0 if query else C) if cells_cap is None else cells_cap
+    bcap = B if batches_cap is None else batches_cap
+    lead = 1 if narrow else 0
+    assert status == (ans["status"] | int((C > ccap and not query) or B > bcap)) and not (host and (status or narrow or query))
+    want = []
+    if not query:
+        want += [Want("bucketed rows", np.concatenate([np.full(lead, -7, dtype=np.int32), padded(ans["rows"], ccap)]), ("batches", ans["cell"], lead)),
+                 Want("bucketed mask", padded(ans["mask"], ccap), ("batches", ans["cell"]))]
+    want += [Want(w, padded(ans[w], nseq)) for w in BUCKET_OUTS[2:4]] + [Want("batch " + w, padded(ans[w], bcap + 1)) for w in BUCKET_OUTS[4:7]]
+    want.append(Want("counts", padded(ans["counts"], 2)))
+    tail = [(nseq, np.int32)] * 2 + [(bcap + 1, np.int32)] * 2 + [(bcap + 1, np.int64), (2, np.int64)]
+
+    def call_device(h, cx):
+        planes = [] if query else [cx.full(lead + ccap + TAIL, np.int32), cx.full(ccap + TAIL, np.uint8)]
+        rest = [cx.full(n + TAIL, t) for n, t in tail]
+        assert query or (planes[0].data_ptr() % 16 == 0 and planes[1].data_ptr() % 4 == 0)
+        p = [None, None] if query else [planes[0].data_ptr() + 4 * lead, planes[1].data_ptr()]
+        o = [t.data_ptr() for t in rest]
+        r = bf.lib().IdsToBucketedRowsBatchDevice(VP(h), cx.ptr(ids), len(ids), cx.ptr(off), nseq, max_len, CLS, SEP, PAD, multiple, max_cells, 0, 0, p[0], p[1], ccap, *o[:5], bcap,
+                                                  o[5], cx.stream)
+        return r, planes + rest
+
+    def call_host(h, cx):
+        outs = host_buffers([(C, np.int32), (C, np.uint8)] + tail)
+        o = [a.ctypes.data for a in outs]
+        r = bf.lib().IdsToBucketedRowsBatch(VP(h), ids.ctypes.data, off.ctypes.data, nseq, max_len, CLS, SEP, PAD, multiple, max_cells, 0, 0, o[0], o[1], C, *o[2:7], B, o[7])
+        return r, outs
+    step = Step(name, call_host if host else call_device, want, C if host else 0, status, why, size)
+    step.bucketed = dict(ids=ids, off=off, max_len=max_len, multiple=multiple, max_cells=max_cells, cells_cap=ccap, batches_cap=bcap, lead=lead, query=query, host=host, answer=ans)
+    return step
+
+
+def minhash_answer(ids, off, k, H, r, seed):
+    """minhash_cases.restate, once per input"""
+    def compute():
+        ans = minhash_cases.restate(ids, off, k, H, r, seed)
+        frozen(*ans.values())
+        return (ids, off), ans
+    return memo(("minhash answer", id(ids), id(off), k, H, r, seed), compute)[1]
+
+
+def minhash_step(name, size, ids, off, k, H, r, seed, sig_cap=None, host=False, status=0, why="status 0: every id range inside [0, ids_len], sig_cap is nseq"):
+    """IdsToMinHashBatchDevice with the signatures, the band keys (r > 0) and nshingles, or (host) IdsToMinHashBatch into numpy buffers, which
+    returns nseq; sig_cap None = nseq.  Rows at or past sig_cap of the signatures and the keys are not written: `want` holds the sentinel there"""
+    nseq = len(off) - 1
+    ans = minhash_answer(ids, off, k, H, r, seed)
+    cap = nseq if sig_cap is None else sig_cap
+    nb = H // r if r else 0
+    assert status == (ans["status"] | int(nseq > cap)) and not (host and status)
+    want = [Want("signatures", padded(ans["sig"], cap * H), ("rows", H))] + ([Want("band keys", padded(ans["keys"], cap * nb), ("rows", nb))] if r else [])
+    want.append(Want("nshingles", padded(ans["nshingles"], nseq)))
+    caps = [(cap * H, np.int32)] + ([(cap * nb, np.int64)] if r else []) + [(nseq, np.int32)]
+
+    def call_device(h, cx):
+        outs = [cx.full(n + TAIL, t) for n, t in caps]
+        r_ = bf.lib().IdsToMinHashBatchDevice(VP(h), cx.ptr(ids), len(ids), cx.ptr(off), nseq, k, H, r, seed, 0, outs[0].data_ptr(), cap, outs[1].data_ptr() if r else None,
+                                              outs[-1].data_ptr(), cx.stream)
+        return r_, outs
+
+    def call_host(h, cx):
+        outs = host_buffers(caps)
+        r_ = bf.lib().IdsToMinHashBatch(VP(h), ids.ctypes.data, off.ctypes.data, nseq, k, H, r, seed, 0, outs[0].ctypes.data, cap, outs[1].ctypes.data if r else None,
+                                        outs[-1].ctypes.data)
+        return r_, outs
+    step = Step(name, call_host if host else call_device, want, nseq if host else 0, status, why, size)
+    step.minhash = dict(ids=ids, off=off, k=k, H=H, r=r, seed=seed, sig_cap=cap, host=host, answer=ans)
+    return step
+
+
+def minhash_pairs_step(name, size, sig, pairs, status, why):
+    """MinHashPairsBatchDevice over a signature array int32[nseq, H] and pairs int64[npairs, 2]: the equal slots of each pair by plain numpy, -1 for a
+    pair with an index outside [0, nseq)"""
+    nseq, H = sig.shape
+    equal = np.array([(sig[a] == sig[b]).sum() if 0 <= a < nseq and 0 <= b < nseq else -1 for a, b in pairs], dtype=np.int32)
+    assert status == (8 if (equal < 0).any() else 0)
+    want = [Want("equal slots", padded(equal, len(pairs)))]
+
+    def call(h, cx):
+        out = cx.full(len(pairs) + TAIL, np.int32)
+        return bf.lib().MinHashPairsBatchDevice(VP(h), cx.ptr(sig), H, nseq, cx.ptr(pairs), len(pairs), out.data_ptr(), cx.stream), [out]
+    step = Step(name, call, want, 0, status, why, size)
+    step.pairs = dict(sig=sig, pairs=pairs, equal=frozen(equal))
+    return step
+
+
+def charpos_step(name, size, direction, text, doc_off, unit, flags=0, starts=None, ends=None, item_off=None, status=0,
+                 why="status 0: every document inside the text, every position inside its document"):
+    """ByteToCharOffsetsBatchDevice (charpos_cases.FWD) / CharToByteOffsetsBatchDevice (INV) with items_cap == the number of items and doc_units
+    taken; without starts and ends doc_units is the only output.  `want` is charpos_cases.restate_array's"""
+    ndocs = len(doc_off) - 1
+    given = starts is not None or ends is not None
+    n = len(starts if starts is not None else ends) if given else 0
+    ws, we, wu, wst = charpos_cases.restate_array(text, doc_off, unit, direction, flags, starts if given else np.zeros(0, dtype=np.int32), ends, item_off if given else None)
+    assert status == wst
+    want = [Want(w, padded(a, n)) for w, a, src in (("starts", ws, starts), ("ends", we, ends)) if src is not None] + [Want("doc_units", padded(wu, ndocs))]
+    fn_name = "ByteToCharOffsetsBatchDevice" if direction == charpos_cases.FWD else "CharToByteOffsetsBatchDevice"
+
+    def call(h, cx):
+        outs = [None if src is None else cx.full(n + TAIL, np.int32) for src in (starts, ends)] + [cx.full(ndocs + TAIL, np.int32)]
+        ins = [None if src is None else cx.ptr(src) for src in (starts, ends)]
+        o = [None if t is None else t.data_ptr() for t in outs]
+        r = getattr(bf.lib(), fn_name)(VP(h), cx.ptr(text), cx.ptr(doc_off), ndocs, len(text), cx.ptr(item_off) if given and item_off is not None else None, n, ins[0], ins[1],
+                                       unit, flags, o[0], o[1], o[2], cx.stream)
+        return r, [t for t in outs if t is not None]
+    step = Step(name, call, want, 0, status, why, size)
+    step.charpos = dict(direction=direction, text=text, doc_off=doc_off, unit=unit, flags=flags, starts=starts, ends=ends, item_off=item_off if given else None)
+    return step
+
+
 # ---- the secondary calls
 def two_pass_step(name, size, fn_name, pre, n, w_flat, w_off, post=(), extras=(), query=False, status=0, why="status 0: the capacity is the exact total", where=None):
     """a Device call of the two-pass kind (IdsToText, DictGetInfo, WordHyphenation): pre = the arguments in front of the output, (array | int), post
@@ -804,6 +953,8 @@ def unigram():
             steps.append(tok_device_step("%s %s ids" % (vname, size), size, batch(size), ids_answer(model, size, pair), variant, pair))
     steps += [tok_device_step("big offsets", "big", batch("big"), offsets_answer(model, "big", pair), 3, pair),
               tok_device_step("small offsets", "small", batch("small"), offsets_answer(model, "small", pair), 3, pair)]
+    # the offsets of the lane program beside those of the cut form (variant 3): both over the same staging cells, one answer
+    steps += [tok_device_step("lane %s offsets" % s.size, s.size, batch(s.size), offsets_answer(model, s.size, pair), 6, pair, share=s) for s in steps[-2:]]
     steps += common_tokenizer_steps(model, pair, 3)
     bi, _, _, bo = ids_answer(model, "big", pair)
     si, _, _, so = ids_answer(model, "small", pair)
@@ -825,6 +976,8 @@ def bpe():
             steps.append(tok_device_step("%s %s ids" % (vname, size), size, batch(size), ids_answer(model, size, pair), variant, pair))
     steps += [tok_device_step("big offsets", "big", batch("big"), offsets_answer(model, "big", pair), 3, pair),
               tok_device_step("small offsets", "small", batch("small"), offsets_answer(model, "small", pair), 3, pair)]
+    # the offsets of the lane kernels beside those of the wave program's HOME / SPANS form (variant 3): one answer
+    steps += [tok_device_step("lanes %s offsets" % s.size, s.size, batch(s.size), offsets_answer(model, s.size, pair), 3 | 0x40, pair, share=s) for s in steps[-2:]]
 
     def pool_batch():
         docs = small_docs()
@@ -984,7 +1137,83 @@ def inputs():
     return Catalogue("inputs", bfutil.model_path(model), steps)
 
 
-BUILDERS = {"wordpiece": wordpiece, "unigram": unigram, "bpe": bpe, "i2w": i2w, "w2h": w2h, "inputs": inputs}
+BUCKET_SMALL = (64, 8, 128)                              # (max_len, multiple, max_cells) of the small bucketed steps that are not cut
+MINHASH_SMALL = (3, 32, 8, 0x0123456789ABCDEF)           # (k, H, r, seed) of the small MinHash steps that are not cut; the pairs steps compare its signatures
+
+
+def pairs_of(sig):
+    """pairs of rows of a signature array [nseq, H] for the pairs steps: one whose rows share some slots and not all, a row with itself, two rows
+    of all ones (sequences without ids), two rows that share nothing -- and, last, one with an index of nseq: out of range"""
+    nseq, H = sig.shape
+    eq = (sig[:, None, :] == sig[None, :, :]).sum(axis=2)
+    some = np.argwhere((eq > 0) & (eq < H))
+    none = np.argwhere(eq == 0)
+    ones = np.flatnonzero((sig == -1).all(axis=1))
+    assert len(some) and len(none) and len(ones) >= 2
+    return frozen(np.array([some[0], (5, 5), ones[:2], none[0], some[-1], (0, nseq)], dtype=np.int64))
+
+
+def ragged():
+    """the calls over ragged ids and over text on a WordPiece handle: bucketed rows (the packed stage's chain and scan workspaces, w_counts as row
+    lengths, w_bsums sized by digit bins and by sequences in one call), MinHash (w_counts, w_pkW, its parameters) with the pairs call, and the
+    offset conversions (w_bsums sized by 64-byte chunks of text), in front of and behind the tokenizer calls that feed them and the owners of the
+    workspaces they borrow: the packed, stream and rows stages and the host tokenizer call.  20 steps, five on the big batch"""
+    model = bfutil.bert_model_name()
+    if not bfutil.have_model(model):
+        return None
+    pair = WP_PAIR
+    si, ss, se, so = offsets_answer(model, "small", pair)
+    bi, bs, be, bo = offsets_answer(model, "big", pair)
+    bad = bad_range_offsets(so)
+    steps = [tok_device_step("wave small offsets", "small", batch("small"), (si, ss, se, so), 5, pair),
+             tok_device_step("flat big ids", "big", batch("big"), ids_answer(model, "big", pair), 4, pair),
+             host_batch_step("TextToIdsBatch small", "small", ids_answer(model, "small", pair), 3, pair),
+             packed_step("packed L=12 small", "small", si, so, 12),
+             stream_step("stream L=64 big", "big", bi, bo, 64, CLS, SEP),
+             rows_step("rows L=12 windows small", "small", si, so, 12, 3, 0, narrow=True)]
+    # bucketed rows
+    cut = bucketed_answer(si, so, 300, 3, 300)
+    b = int(cut["counts"][0]) // 2                       # cells_cap: cell 1 of the last row of a batch in the middle
+    cut_cells = int(cut["cell"][b + 1]) - int(cut["len"][b]) + 1
+    mx, mult, cells = BUCKET_SMALL
+    steps += [bucketed_step("bucketed max_len=64 big", "big", bi, bo, 64, 8, 4096),
+              bucketed_step("bucketed max_len=300 small, narrow, cut", "small", si, so, 300, 3, 300, cells_cap=cut_cells, batches_cap=int(cut["counts"][0]) - 1, narrow=True, status=1,
+                            why="status 1: cells_cap ends inside a row and batches_cap is B - 1 (bit 0); nothing at or past either cap is written"),
+              bucketed_step("bucketed small bad range", "small", si, bad, mx, mult, cells, status=8,
+                            why="status 8: the last sequence claims ids behind ids_len (bit 3) and is read as empty; every other sequence keeps its row"),
+              bucketed_step("bucketed small, size query", "small", si, so, mx, mult, cells, query=True,
+                            why="status 0: both planes are NULL, so no cell is lost to cells_cap; batches_cap is B"),
+              bucketed_step("bucketed host small", "small", si, so, mx, mult, cells, host=True)]
+    # MinHash
+    k, H, r, seed = MINHASH_SMALL
+    sig = minhash_answer(si, so, k, H, r, seed)["sig"]
+    pairs = pairs_of(sig)
+    steps += [minhash_step("minhash H=64 r=4 k=5 big", "big", bi, bo, 5, 64, 4, 0x51ED),
+              minhash_step("minhash H=65 k=2 small, cut", "small", si, so, 2, 65, 0, 7, sig_cap=len(so) // 2, status=1,
+                           why="status 1: sig_cap is below nseq (bit 0); no row at or past sig_cap is written"),
+              minhash_step("minhash small bad range", "small", si, bad, k, H, r, seed, status=8,
+                           why="status 8: the last sequence claims ids behind ids_len (bit 3) and is read as empty: the row of all ones"),
+              minhash_step("minhash host small", "small", si, so, k, H, r, seed, host=True),
+              minhash_pairs_step("minhash pairs small", "small", sig, pairs, 8, "status 8: the last pair names row nseq (bit 3) and answers -1"),
+              minhash_pairs_step("minhash pairs small, clean", "small", sig, frozen(pairs[:-1].copy()), 0, "status 0: every index inside [0, nseq)")]
+    # offsets in characters
+    btext, boff = batch("big")
+    stext, soff = batch("small")
+    fs, fe, units, status = charpos_cases.restate_array(stext, soff, charpos_cases.CHAR, charpos_cases.FWD, 0, ss, se, so)
+    assert status == 0 and (fs >= 0).all() and (fe >= 0).all()
+    d = len(soff) - 2                                    # the first position of the last document (it has ids): one unit behind the document's last
+    assert so[d + 1] > so[d]
+    fs = fs.copy()
+    fs[so[d]] = units[d] + 1
+    frozen(fs, fe)
+    steps += [charpos_step("byte to char big, utf16", "big", charpos_cases.FWD, btext, boff, charpos_cases.UTF16, 0, bs, be, bo),
+              charpos_step("char to byte small, one beyond", "small", charpos_cases.INV, stext, soff, charpos_cases.CHAR, 0, fs, fe, so, status=8,
+                           why="status 8: one start lies beyond its document (bit 3) and answers -1"),
+              charpos_step("byte to char small, units only", "small", charpos_cases.FWD, stext, soff, charpos_cases.UTF16)]
+    return Catalogue("ragged", bfutil.model_path(model), steps)
+
+
+BUILDERS = {"wordpiece": wordpiece, "unigram": unigram, "bpe": bpe, "i2w": i2w, "w2h": w2h, "inputs": inputs, "ragged": ragged}
 
 
 def catalogue(kind):
@@ -1006,6 +1235,10 @@ def describe_difference(want, got):
         off = want.where[1]
         d = int(np.searchsorted(off, at, side="right")) - 1
         place = "behind the last document (the sentinel)" if at >= off[-1] else "document %d, element %d of its %d" % (d, at - off[d], off[d + 1] - off[d])
+    elif want.where[0] == "batches":
+        cell, c = want.where[1], at - (want.where[2] if len(want.where) > 2 else 0)
+        b = int(np.searchsorted(cell, c, side="right")) - 1
+        place = "behind the last batch (the sentinel)" if c >= cell[-1] else "in front of the plane (the sentinel)" if c < 0 else "batch %d, cell %d of its %d" % (b, c - cell[b], cell[b + 1] - cell[b])
     elif want.where[0] == "rows":
         place = "row %d, cell %d" % divmod(at - (want.where[2] if len(want.where) > 2 else 0), want.where[1])
     else:

@@ -5,7 +5,10 @@ on a big and a small batch, the host forms, words and sentences, rows, pair rows
 hyphenation, calls that end with status 1, 4 or 8; and, as the kind `inputs` on a WordPiece handle of its own, the model-input calls: packed rows with
 their planes form, stream rows, the capped MLM call beside the base one, span corruption, and the host-buffer forms of the packed, stream and rows-planes
 stages, crossed with each other and with a Device and a host tokenizer call (the i2w kind crosses stream rows and a denoise call of status 1 with
-IdsToText's status 4) -- run in the order of order_cases.circuit(), in which every ordered pair, a step behind itself included,
+IdsToText's status 4); and, as the kind `ragged` on a third WordPiece handle, the calls that borrow their state: bucketed rows (wide, narrow and cut,
+a bad range, a size query, the host form), MinHash (many tiles, cut, a bad range, the host form) with the pairs call, and the two offset conversions
+(the big text, a position beyond its document, doc_units alone), between tokenizer calls and the packed, stream and rows stages; unigram and bpe take
+their offsets from two programs each -- run in the order of order_cases.circuit(), in which every ordered pair, a step behind itself included,
 is neighbours exactly once (tests/test_order_host.py asserts that).  Behind every call: its return value, BfLastStatus -- the rule is that it is the call's
 OWN, whatever the call before it left -- and every output buffer in full (every element up to the count, the sentinel behind it, the offsets) against the
 checker's answer, on the device; a failure names the pair and the first document or row that differs, and ends the walk of that handle.

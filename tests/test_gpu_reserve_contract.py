@@ -8,6 +8,11 @@ not moved, every output equals the CPU checker's (the compiled reference where o
 row stages; the stored reference answers of the hyphenation fixture), and BfLastStatus is 0.  The counter sees the library's own hipMalloc
 calls alone: torch's allocator and other processes on the card cannot move it, and nothing here reads the card's free memory.
 
+The row stages (STAGES) include `bucketed_rows` -- at one and at two radix passes, the second with the long sequence whole -- and `minhash` with
+MinHashPairsBatchDevice over the signatures it just wrote; `charpos` has a test of its own, both conversions in both units on text that holds
+exactly B bytes, because its workspaces are sized by bytes and not by sequences; the text-to-model-inputs test also makes bucketed batches, MinHash
+signatures and UTF-16 offsets from text.
+
 These are also parity checks on workspaces of exactly the reserved size.  A workspace that BfReserve sized too small shows as an allocation, not
 as memory corruption: the calls still grow their buffers on demand."""
 import ctypes
@@ -17,7 +22,10 @@ import pytest
 
 import bfutil
 import blingfire_amd as bf
+import bucketed_cases
+import charpos_cases
 import denoise_cases
+import minhash_cases
 import mlm_cases
 import mlmcap_cases
 import packed_cases
@@ -470,9 +478,53 @@ def stage_denoise(r, lens, name):
         _same([got[k] for k in names], [want[n] for n in names.values()], what)
 
 
+BUCKET_NAMES = ("rows", "mask", "order", "seq_pos", "first", "len", "cell", "counts")
+BUCKET_MULTIPLE, BUCKET_CELLS = 8, 4096
+BUCKET_SPECS = ((16, CLS, SEP), (300, None, None))      # (max_len, cls, sep): one radix pass and two; without specials max_len 300 keeps the `one_long` sequence whole
+
+
+def stage_bucketed(r, lens, name):
+    """bucketed rows with both caps given (nothing is read back): the sort's own workspaces, the packed stage's chain, w_bsums by digit bins and by sequences"""
+    ids, off = packed_cases.ragged(lens)
+    d_ids, d_off = _dev(r.stream, ids, off)
+    for max_len, cls, sep in BUCKET_SPECS:
+        want = bucketed_cases.restate(ids, off, max_len, -1 if cls is None else cls, -1 if sep is None else sep, PAD, BUCKET_MULTIPLE, BUCKET_CELLS)
+        B, C = (int(x) for x in want["counts"])
+        with torch_().cuda.stream(r.stream):
+            got = bf.ids_to_bucketed_rows_batch_device(r.h, d_ids, d_off, max_len, BUCKET_CELLS, cls, sep, PAD, BUCKET_MULTIPLE, cells_cap=C, batches_cap=B,
+                                                       stream=r.stream.cuda_stream)
+        what = r.check("IdsToBucketedRowsBatchDevice, max_len %d, shape %s" % (max_len, name))
+        assert want["status"] == 0 and (max_len < 300 or int(want["mask"].sum()) == sum(lens)), what      # at 300 no id is cut off
+        _same(got, [want[k] for k in BUCKET_NAMES], what)
+
+
+MINHASH_SPEC = dict(num_perm=65, shingle=5, band_rows=5, seed=0x51ED)
+
+
+def stage_minhash(r, lens, name):
+    """signatures, band keys and nshingles, then MinHashPairsBatchDevice (no workspace) over the signatures the call just left on the device"""
+    ids, off = packed_cases.ragged(lens)
+    d_ids, d_off = _dev(r.stream, ids, off)
+    with torch_().cuda.stream(r.stream):
+        got = bf.ids_to_minhash_batch_device(r.h, d_ids, d_off, stream=r.stream.cuda_stream, **MINHASH_SPEC)
+    what = r.check("IdsToMinHashBatchDevice, shape %s" % name)
+    want = minhash_cases.restate(ids, off, MINHASH_SPEC["shingle"], MINHASH_SPEC["num_perm"], MINHASH_SPEC["band_rows"], MINHASH_SPEC["seed"])
+    assert want["status"] == 0, what
+    _same(got, [want[k] for k in ("sig", "keys", "nshingles")], what)
+    nseq = len(lens)
+    q = np.arange(nseq, dtype=np.int64)
+    pairs = np.stack([q, np.where(q % 3 == 0, q, (7 * q + 3) % max(nseq, 1))], axis=1)           # every third row with itself
+    d_pairs, = _dev(r.stream, pairs)
+    with torch_().cuda.stream(r.stream):
+        equal = bf.minhash_pairs_device(r.h, got[0], d_pairs, stream=r.stream.cuda_stream)
+    what = r.check("MinHashPairsBatchDevice, shape %s" % name)
+    _same([equal], [np.array([(want["sig"][a] == want["sig"][b]).sum() for a, b in pairs], dtype=np.int32)], what)
+
+
 STAGES = {"rows": stage_rows, "pair_rows": stage_pairs, "rows_planes": stage_rows_planes, "pair_rows_planes": stage_pair_planes, "span_cells": stage_span_cells,
           "packed_rows": stage_packed, "packed_rows_planes": stage_packed_planes, "stream_rows": stage_stream, "mlm_mask": stage_mlm,
-          "mlm_predictions": lambda r, lens, name: stage_mlm(r, lens, name, MLM_MAX_PRED), "denoise": stage_denoise}
+          "mlm_predictions": lambda r, lens, name: stage_mlm(r, lens, name, MLM_MAX_PRED), "denoise": stage_denoise, "bucketed_rows": stage_bucketed,
+          "minhash": stage_minhash}
 
 
 @pytest.mark.parametrize("stage", list(STAGES))
@@ -483,6 +535,36 @@ def test_row_stages_allocate_nothing_after_reserve(model, stage):
     try:
         for name, lens in rv.seq_shapes(D, long_len=300).items():
             STAGES[stage](r, lens, name)
+    finally:
+        r.close()
+
+
+CHARPOS_SHAPES = ("even", "one_long", "bytes", "empty", "half")
+
+
+@pytest.mark.parametrize("model", [WP, "gpt2.i2w"])
+def test_charpos_allocates_nothing_after_reserve(model):
+    """ByteToCharOffsetsBatchDevice and CharToByteOffsetsBatchDevice in both units on the text shapes of the small bound: the index and the block
+    sums of its scan are sized by the bytes alone, and `even` and `one_long` hold exactly B of them.  One item per document (no item offsets):
+    a start in the middle of the document and its last position as an inclusive end, -1 ("none") as the end of an empty document"""
+    torch = torch_()
+    D, B = rv.SMALL
+    shapes = rv.shapes(D, B)
+    assert len(rv.pack(shapes["even"])[0]) == len(rv.pack(shapes["one_long"])[0]) == B
+    r = Reserved(model, D, B)
+    try:
+        for name in CHARPOS_SHAPES:
+            text, doc_off = rv.pack(shapes[name])
+            d_text, d_off = _dev(r.stream, text, doc_off)
+            for unit, unit_name in ((charpos_cases.CHAR, "char"), (charpos_cases.UTF16, "utf16")):
+                limit = {charpos_cases.FWD: np.diff(doc_off), charpos_cases.INV: charpos_cases.restate_array(text, doc_off, unit, charpos_cases.FWD, 0, np.zeros(0, np.int32), None, None)[2]}
+                for direction, fn in ((charpos_cases.FWD, bf.byte_to_char_offsets_device), (charpos_cases.INV, bf.char_to_byte_offsets_device)):
+                    starts, ends = (limit[direction] // 2).astype(np.int32), (limit[direction] - 1).astype(np.int32)
+                    d_starts, d_ends = _dev(r.stream, starts, ends)
+                    with torch.cuda.stream(r.stream):
+                        got = fn(r.h, d_text, d_off, d_starts, d_ends, None, unit=unit_name, stream=r.stream.cuda_stream, return_doc_units=True)
+                    what = r.check("%s, unit %s, shape %s" % (fn.__name__, unit_name, name))
+                    _same(got, charpos_cases.restate_array(text, doc_off, unit, direction, 0, starts, ends, None)[:3], what)
     finally:
         r.close()
 
@@ -560,5 +642,35 @@ def test_text_to_model_inputs_allocates_nothing_after_reserve():
             assert len(got) == 10 and int(got[6].item()) == pk[6], what
             _same(got[:6] + got[7:], [w_ids] + list(pk[1:6]) + [S, E, w_labels], what)
             assert (w_labels != -100).any(), what
+
+            # length-bucketed rows: every document cut to the ids a row of L holds, which is what the restatement does with max_len = L
+            want = bucketed_cases.restate(ids, off, L, CLS, SEP, PAD, BUCKET_MULTIPLE, BUCKET_CELLS)
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_bucketed_batch_device(r.h, d_text, d_off, L, CLS, SEP, PAD, BUCKET_CELLS, BUCKET_MULTIPLE, unk=UNK, cells_cap=int(want["counts"][1]),
+                                                      batches_cap=int(want["counts"][0]))
+            what = r.check("encode_bucketed_batch_device, shape %s" % name)
+            _same(got, [want[k] for k in BUCKET_NAMES], what)
+            assert want["status"] == 0 and (want["len"][:-1] == L).any(), what             # a document of more ids than a row holds
+
+            # MinHash signatures over every id of every document
+            mx = max_ids_of(docs)
+            with torch.cuda.stream(r.stream):
+                got = bf.encode_minhash_batch_device(r.h, d_text, d_off, mx, unk=UNK, **MINHASH_SPEC)
+            what = r.check("encode_minhash_batch_device, shape %s" % name)
+            want = minhash_cases.restate(ids, off, MINHASH_SPEC["shingle"], MINHASH_SPEC["num_perm"], MINHASH_SPEC["band_rows"], MINHASH_SPEC["seed"])
+            _same(got, [want[k] for k in ("sig", "keys", "nshingles")], what)
+
+            # the byte offsets of the offsets call, as it leaves them on the device, in UTF-16 units with exclusive ends
+            with torch.cuda.stream(r.stream):
+                t_ids, t_st, t_en, t_off = bf.text_to_ids_with_offsets_batch_device(r.h, d_text, d_off, mx, UNK)
+            what = r.check("TextToIdsWithOffsetsBatchDevice, shape %s" % name)
+            n = int(off[-1])
+            _same([t_ids[:n], t_st[:n], t_en[:n], t_off], [ids, st, en, off], what)
+            with torch.cuda.stream(r.stream):
+                got = bf.byte_to_char_offsets_device(r.h, d_text, d_off, t_st, t_en, t_off, unit="utf16", ends_out_exclusive=True, return_doc_units=True)
+            what = r.check("byte_to_char_offsets_device, shape %s" % name)
+            want = charpos_cases.restate_array(text, doc_off, charpos_cases.UTF16, charpos_cases.FWD, charpos_cases.ENDS_OUT_EXCLUSIVE, st, en, off)
+            assert want[3] == 0, what
+            _same([got[0][:n], got[1][:n], got[2]], want[:3], what)
     finally:
         r.close()

@@ -3,7 +3,11 @@ and the inputs of the steps do what they are for -- proven with the checkers and
 under test.  For the model-input steps that means: rows that several sequences share, planes that hold their fill, a sequence split at a row's edge,
 a rows_cap that cuts, a bad range that empties one sequence and moves no other, a cap on the predictions that binds in some rows and not in
 others, a whole word selected, a denoise step that truncates some rows and not all, no span across an eos -- and the array form of the stream
-restatement held to the sequential one on every small step."""
+restatement held to the sequential one on every small step.  For the `ragged` steps: a sort of more than one block, a cells_cap strictly inside a row
+and a batches_cap below the count, the wide and the narrow alignment, a bad range that empties the last sequence alone; sequences over a MinHash
+tile's edge, inside a tile and empty, a sig_cap that cuts, pairs that share some slots and not all; a text of several scan blocks with characters
+of 2, 3 and 4 bytes, exactly one position beyond its document, the array form of the offsets restatement held to the sequential one; and the two
+offsets programs of unigram and of bpe share one answer, object by object."""
 import numpy as np
 import pytest
 
@@ -329,3 +333,182 @@ def test_row_stage_steps_have_windows_and_an_empty_sequence(cat):
             ido = oc.ids_answer(model, size, oc.WP_PAIR)[3]
             for L in oc.ROW_LENS:
                 assert oc.row_geometry_ok(ido, L), (size, L)
+
+
+# ---- the calls over ragged ids and text (the "ragged" catalogue), and the second offsets program of unigram and bpe
+def ragged_cat():
+    c = oc.catalogue("ragged")
+    if c is None:
+        pytest.skip("no WordPiece model")
+    return c
+
+
+def flat_of(want, n):
+    """the first n entries of an output in front of its sentinel tail"""
+    assert len(want.array) >= n + oc.TAIL
+    return want.array[:n]
+
+
+def test_ragged_catalogue_has_the_twenty_steps():
+    cat = ragged_cat()
+    assert [s.name for s in cat.steps] == [
+        "wave small offsets", "flat big ids", "TextToIdsBatch small", "packed L=12 small", "stream L=64 big", "rows L=12 windows small",
+        "bucketed max_len=64 big", "bucketed max_len=300 small, narrow, cut", "bucketed small bad range", "bucketed small, size query", "bucketed host small",
+        "minhash H=64 r=4 k=5 big", "minhash H=65 k=2 small, cut", "minhash small bad range", "minhash host small", "minhash pairs small", "minhash pairs small, clean",
+        "byte to char big, utf16", "char to byte small, one beyond", "byte to char small, units only"]
+    assert sum(s.size == "big" for s in cat.steps) == 5 and len(cat.steps) <= 24 and len(oc.circuit(len(cat.steps))) == 401
+    assert sorted(s.status for s in cat.steps if s.status) == [1, 1, 8, 8, 8, 8]
+    # the inputs are those of the `inputs` catalogue: the checker's ids and byte offsets of the two batches
+    model = bfutil.bert_model_name()
+    si, ss, se, so = oc.offsets_answer(model, "small", oc.WP_PAIR)
+    bi, bs, be, bo = oc.offsets_answer(model, "big", oc.WP_PAIR)
+    for s in cat.steps:
+        p = getattr(s, "bucketed", None) or getattr(s, "minhash", None)
+        if p:
+            assert p["ids"] is (bi if s.size == "big" else si) and (p["off"] is (bo if s.size == "big" else so) or s.status == 8), s.name
+    big = by_name(cat)["byte to char big, utf16"].charpos
+    assert big["starts"] is bs and big["ends"] is be and big["item_off"] is bo and big["text"] is oc.big_batch()[0]
+
+
+def unit_of(ans, q):
+    """the ids of sequence q's row in front of its padding: through seq_pos, the batch that holds the sorted position and the batch's first cell"""
+    pos = int(ans["seq_pos"][q])
+    b = int(np.searchsorted(ans["first"], pos, side="right")) - 1
+    L = int(ans["len"][b])
+    at = int(ans["cell"][b]) + (pos - int(ans["first"][b])) * L
+    assert ans["order"][pos] == q and 0 <= b < ans["counts"][0] and at + L <= ans["counts"][1]
+    return ans["rows"][at:at + L][ans["mask"][at:at + L] == 1]
+
+
+def test_bucketed_steps_sort_in_blocks_cut_inside_a_row_and_empty_one_sequence():
+    import bucketed_cases
+    cat = ragged_cat()
+    steps = [s for s in cat.steps if hasattr(s, "bucketed")]
+    assert [s.name for s in steps] == ["bucketed max_len=64 big", "bucketed max_len=300 small, narrow, cut", "bucketed small bad range", "bucketed small, size query",
+                                       "bucketed host small"]
+    for s in steps:
+        p = s.bucketed
+        ans = bucketed_cases.restate(p["ids"], p["off"], p["max_len"], oc.CLS, oc.SEP, oc.PAD, p["multiple"], p["max_cells"])
+        B, C = (int(x) for x in ans["counts"])
+        assert s.status == (ans["status"] | int((C > p["cells_cap"] and not p["query"]) or B > p["batches_cap"])), s.name
+        assert all(np.array_equal(ans[k], p["answer"][k]) for k in oc.BUCKET_OUTS), s.name
+        assert (np.diff(p["answer"]["len"][:-1]) <= 0).all() and B >= 2, s.name       # the batches narrow: the widest unit comes first
+        assert len(s.want) == (6 if p["query"] else 8) and s.ret == (C if p["host"] else 0), s.name
+    big, cut, bad, query, host = steps
+    p = big.bucketed
+    assert len(p["off"]) - 1 > oc.BUCKET_TILE == 2048 and p["answer"]["counts"][0] > 1            # the sort takes more than one block; more than one batch
+    assert p["lead"] == 0 and p["multiple"] % 4 == 0 and (p["multiple"], p["max_cells"]) == (8, 4096)      # 0 mod 16 and whole groups of 4 cells: the wide stores
+    assert (big.status, p["cells_cap"], p["batches_cap"]) == (0, p["answer"]["counts"][1], p["answer"]["counts"][0])
+    # the cut step: two radix passes from max_len alone, keys with either top digit, the narrow stores, both caps below the counts
+    p = cut.bucketed
+    ans = p["answer"]
+    B, C = (int(x) for x in ans["counts"])
+    keys = p["max_len"] - (np.minimum(np.diff(p["off"]), p["max_len"] - 2) + 2)
+    assert p["max_len"] > 255 and sorted(set((keys >> 8).tolist())) == [0, 1]
+    assert (4 * p["lead"]) % 16 == 4 and p["multiple"] % 4 != 0 and p["multiple"] == 3
+    assert cut.status == 1 and C > p["cells_cap"] > 0 and B > p["batches_cap"] == B - 1
+    assert p["cells_cap"] not in ans["cell"]
+    b = int(np.searchsorted(ans["cell"], p["cells_cap"], side="right")) - 1
+    assert (p["cells_cap"] - int(ans["cell"][b])) % int(ans["len"][b]) != 0 and 0 < b < B - 1      # strictly inside a row of a batch in the middle
+    rows, mask = cut.want[0].array, cut.want[1].array
+    assert rows[0] == -7 and np.array_equal(rows[1:1 + p["cells_cap"]], ans["rows"][:p["cells_cap"]]) and (rows[1 + p["cells_cap"]:] == -7).all()
+    assert len(rows) == 1 + p["cells_cap"] + oc.TAIL and np.array_equal(mask[:p["cells_cap"]], ans["mask"][:p["cells_cap"]]) and (mask[p["cells_cap"]:] == 0x7F).all()
+    for w, k in zip(cut.want[4:7], oc.BUCKET_OUTS[4:7]):                                # entries 0 .. batches_cap, the sentinel from there on
+        assert len(w.array) == B + oc.TAIL and np.array_equal(w.array[:B], ans[k][:B]) and (w.array[B:] == -7).all(), w.label
+    assert np.array_equal(flat_of(cut.want[7], 2), [B, C])                              # the counts are complete
+    # the bad range: the last sequence alone is empty, every other sequence's row holds what it held (order and seq_pos are the restatement's)
+    p, g = bad.bucketed, host.bucketed
+    assert bad.status == 8 and p["ids"] is g["ids"] and all(p[k] == g[k] for k in ("max_len", "multiple", "max_cells")) and query.bucketed["off"] is g["off"]
+    wrong = (p["off"][:-1] < 0) | (p["off"][1:] < p["off"][:-1]) | (p["off"][1:] > len(p["ids"]))
+    assert wrong.sum() == 1 and wrong[-1] and np.array_equal(p["off"][:-1], g["off"][:-1]) and g["off"][-1] > g["off"][-2]
+    nseq = len(p["off"]) - 1
+    for q in range(nseq - 1):
+        assert np.array_equal(unit_of(p["answer"], q), unit_of(g["answer"], q)), q
+    assert unit_of(p["answer"], nseq - 1).tolist() == [oc.CLS, oc.SEP] and len(unit_of(g["answer"], nseq - 1)) > 2
+    assert not np.array_equal(p["answer"]["order"], g["answer"]["order"])                 # (it moved in the order: it is among the narrowest now)
+    assert np.array_equal(flat_of(bad.want[2], nseq), p["answer"]["order"]) and np.array_equal(flat_of(bad.want[3], nseq), p["answer"]["seq_pos"])
+    assert (np.minimum(np.diff(g["off"]), g["max_len"] - 2) + 2).max() == g["max_len"]    # a width that reaches max_len: a truncated sequence
+    assert [w.label for w in query.want] == [w.label for w in host.want[2:]] and all(np.array_equal(a.array, b.array) for a, b in zip(query.want, host.want[2:]))
+
+
+def test_minhash_steps_cross_tiles_cut_rows_and_count_partial_pairs():
+    import minhash_cases
+    cat = ragged_cat()
+    by = by_name(cat)
+    steps = [s for s in cat.steps if hasattr(s, "minhash")]
+    assert [s.name for s in steps] == ["minhash H=64 r=4 k=5 big", "minhash H=65 k=2 small, cut", "minhash small bad range", "minhash host small"]
+    big, cut, bad, host = (s.minhash for s in steps)
+    off = big["off"]
+    n, first, last = np.diff(off), off[:-1] // minhash_cases.TILE, (off[1:] - 1) // minhash_cases.TILE
+    assert minhash_cases.TILE == 1024 and off[-1] > 100 * minhash_cases.TILE                # many tiles
+    assert ((n > 0) & (last > first)).any() and ((n > 0) & (last == first)).any() and (n == 0).any()      # a sequence over a tile's edge (the atomic path), one inside a tile, an empty one
+    assert (big["k"], big["H"], big["r"]) == (5, 64, 4) and len(by["minhash H=64 r=4 k=5 big"].want) == 3 and ((n > 0) & (n < big["k"])).any()
+    nseq = len(cut["off"]) - 1
+    H, cap = cut["H"], cut["sig_cap"]
+    assert 0 < cap < nseq and H % 64 != 0 and (cut["k"], H, cut["r"]) == (2, 65, 0) and steps[1].status == 1
+    sig = steps[1].want[0].array
+    assert len(sig) == cap * H + oc.TAIL and np.array_equal(sig[:cap * H], cut["answer"]["sig"].reshape(-1)[:cap * H]) and (sig[cap * H:] == -7).all()
+    assert np.array_equal(flat_of(steps[1].want[1], nseq), cut["answer"]["nshingles"]) and (cut["answer"]["nshingles"][cap:] > 0).any()      # nshingles is complete
+    small = minhash_cases.restate(host["ids"], host["off"], host["k"], host["H"], host["r"], host["seed"])
+    assert small["status"] == 0 and host["r"] > 0 and host["host"] and all(np.array_equal(small[k], host["answer"][k]) for k in ("sig", "keys", "nshingles"))
+    assert steps[2].status == 8 == bad["answer"]["status"] and all(bad[k] == host[k] for k in ("k", "H", "r", "seed")) and bad["ids"] is host["ids"]
+    assert np.array_equal(bad["answer"]["sig"][:-1], small["sig"][:-1]) and (bad["answer"]["sig"][-1] == -1).all() and not (small["sig"][-1] == -1).all()
+    assert bad["answer"]["nshingles"][-1] == 0 < small["nshingles"][-1]
+    # the pairs steps: the host step's signatures; -1 at the pair out of range and nowhere else, a pair that shares some slots and not all
+    p8, p0 = by["minhash pairs small"], by["minhash pairs small, clean"]
+    sig, pairs = p8.pairs["sig"], p8.pairs["pairs"]
+    assert sig is host["answer"]["sig"] and p0.pairs["sig"] is sig and sig.shape == (nseq, host["H"])
+    outside = ((pairs < 0) | (pairs >= nseq)).any(axis=1)
+    equal = flat_of(p8.want[0], len(pairs))
+    assert p8.status == 8 and outside.sum() >= 1 and np.array_equal(equal == -1, outside)
+    assert ((equal > 0) & (equal < host["H"])).any() and (equal == host["H"]).any() and (equal == 0).any()
+    assert p0.status == 0 and np.array_equal(p0.pairs["pairs"], pairs[~outside]) and np.array_equal(flat_of(p0.want[0], len(pairs) - outside.sum()), equal[~outside])
+
+
+def test_char_offset_steps_scan_in_blocks_and_hold_one_position_beyond():
+    import charpos_cases as cc
+    cat = ragged_cat()
+    by = by_name(cat)
+    steps = [s for s in cat.steps if hasattr(s, "charpos")]
+    assert [s.name for s in steps] == ["byte to char big, utf16", "char to byte small, one beyond", "byte to char small, units only"]
+    big = steps[0].charpos
+    text = big["text"]
+    assert len(text) > cc.TILE_CHUNKS * 64 * 4                                          # the scan of the chunk weights takes several blocks
+    lead = text[(text & 0xC0) != 0x80]
+    assert all(((lead >= lo) & (lead < hi)).any() for lo, hi in ((0xC0, 0xE0), (0xE0, 0xF0), (0xF0, 0xF8)))      # characters of 2, 3 and 4 bytes
+    nd = len(big["doc_off"]) - 1
+    u16 = flat_of(steps[0].want[2], nd)
+    chars = cc.restate_array(text, big["doc_off"], cc.CHAR, cc.FWD, 0, big["starts"], big["ends"], big["item_off"])[2]
+    nbytes = np.diff(big["doc_off"])
+    assert big["unit"] == cc.UTF16 and big["direction"] == cc.FWD and (u16 > chars).any() and (chars < nbytes).any() and (u16 != nbytes).any()
+    n = len(big["starts"])
+    assert steps[0].status == 0 and (flat_of(steps[0].want[0], n) != big["starts"]).any() and len(steps[0].want) == 3
+    # the small steps: the array form of the restatement is the sequential one
+    for s in steps[1:]:
+        p = s.charpos
+        r = cc.restate(p["text"], p["doc_off"], p["unit"], p["direction"], p["flags"], p["starts"], p["ends"], p["item_off"])
+        assert r["status"] == s.status, s.name
+        got = {w.label: w.array for w in s.want}
+        for k in ("starts", "ends"):
+            assert (r[k] is None) == (k not in got) and (r[k] is None or np.array_equal(got[k][:r["n"]], r[k]) and len(got[k]) == r["n"] + oc.TAIL), (s.name, k)
+        assert np.array_equal(got["doc_units"][:len(r["doc_units"])], r["doc_units"]) and (got["doc_units"][len(r["doc_units"]):] == -7).all(), s.name
+    beyond = steps[1]
+    p = beyond.charpos
+    n = len(p["starts"])
+    assert beyond.status == 8 and p["direction"] == cc.INV and p["unit"] == cc.CHAR and n == p["item_off"][-1]
+    assert (flat_of(beyond.want[0], n) == -1).sum() + (flat_of(beyond.want[1], n) == -1).sum() == 1
+    units = steps[2]
+    assert [w.label for w in units.want] == ["doc_units"] and units.charpos["starts"] is None and units.charpos["ends"] is None and units.status == 0
+
+
+@pytest.mark.parametrize("kind,program,variants", [("unigram", "lane", (3, 6)), ("bpe", "lanes", (3, 3 | 0x40))])
+def test_both_offsets_programs_take_one_answer(kind, program, variants):
+    cat = oc.catalogue(kind)
+    if cat is None:
+        pytest.skip("the model of the %s catalogue is not present" % kind)
+    by = by_name(cat)
+    for size in ("big", "small"):
+        a, b = by["%s offsets" % size], by["%s %s offsets" % (program, size)]
+        assert (a.variant, b.variant) == variants and a.size == b.size == size and a.status == b.status == 0
+        assert [w.label for w in a.want] == ["ids", "first bytes", "last bytes", "id offsets"] and len(b.want) == 4
+        assert all(x is y and x.array is y.array for x, y in zip(a.want, b.want))        # one answer, two programs
