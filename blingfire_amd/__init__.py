@@ -17,6 +17,7 @@ There is no CPU fallback: if the shared library is missing or no HIP device is v
 raise / return the reference's error value, loudly.  ``torch`` is imported only inside the functions that need it.
 """
 import ctypes
+import math
 import os
 from ctypes import POINTER, byref, c_bool, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_longlong, c_uint32, c_uint64, c_void_p
 
@@ -85,6 +86,8 @@ _SIGNATURES = {
     "IdsToMinHashBatch": (_L, [_P, _P, _P, _L] + [_I] * 3 + [c_uint64, _I, _P, _L, _P, _P]),
     "IdsToMinHashBatchDevice": (_I, [_P, _P, _L, _P, _L] + [_I] * 3 + [c_uint64, _I, _P, _L, _P, _P, _P]),
     "MinHashPairsBatchDevice": (_I, [_P, _P, _I, _L, _P, _L, _P, _P]),
+    # clusters: sig, H, band keys, bands, nseq, nshingles, min_equal, flags; label, keep, size, counts; stream
+    "MinHashClustersBatchDevice": (_I, [_P, _P, _I, _P, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P]),
     "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
     "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
     "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
@@ -1186,6 +1189,36 @@ def encode_minhash_batch_device(h, d_text, d_doc_off, max_len, num_perm=128, shi
     ids_to_minhash_batch_device on one stream.  Returns what ids_to_minhash_batch_device returns."""
     d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_len), unk)
     return ids_to_minhash_batch_device(h, d_ids, d_id_off, num_perm, shingle, band_rows, seed)
+
+
+def minhash_clusters_device(h, band_keys, sig=None, min_equal=0, nshingles=None, stream=None):
+    """clusters of near-duplicates (MinHashClustersBatchDevice; the header has the specification): band_keys = int64[nseq, B], sig = int32[nseq, H]
+    (needed while min_equal > 0) and nshingles = int32[nseq] (a sequence without shingles is its own cluster), torch tensors on one GPU ->
+    (label int32[nseq], keep bool[nseq], size int32[nseq], counts int64[2] = {clusters, candidates}), enqueued on torch's current stream (or
+    `stream`); nothing is read back.  Sequences that share a band key are joined when at least min_equal slots of their signatures agree;
+    label[q] is the smallest index of q's cluster and keep[q] = (label[q] == q)."""
+    import torch
+    name = "MinHashClustersBatchDevice"
+    band_keys = band_keys.contiguous()
+    dev, (nseq, B) = band_keys.device, band_keys.shape
+    sig = None if sig is None else sig.contiguous()
+    nshingles = None if nshingles is None else nshingles.contiguous()
+    label, keep, size = (torch.empty(nseq, dtype=t, device=dev) for t in (torch.int32, torch.uint8, torch.int32))
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    r = getattr(lib(), name)(c_void_p(h), _dev_addr(sig), 1 if sig is None else sig.shape[1], band_keys.data_ptr(), B, nseq, _dev_addr(nshingles), int(min_equal), 0,
+                             label.data_ptr(), keep.data_ptr(), size.data_ptr(), counts.data_ptr(), _stream_arg(stream, dev))
+    _check(name, r, r == 0)
+    return label, keep.view(torch.bool), size, counts
+
+
+def encode_dedup_batch_device(h, d_text, d_doc_off, max_len, num_perm=128, shingle=5, band_rows=8, min_jaccard=0.0, seed=0, unk=0, stream=None):
+    """Text in HBM -> near-duplicate clusters, nothing on the host: text_to_ids_batch_device, ids_to_minhash_batch_device and
+    minhash_clusters_device on one stream, with min_equal = ceil(min_jaccard * num_perm).  Returns (label, keep, size, counts, sig, nshingles);
+    corpus[keep] is the deduplicated corpus."""
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_len), unk, stream=stream)
+    sig, keys, nsh = ids_to_minhash_batch_device(h, d_ids, d_id_off, num_perm, shingle, band_rows, seed, stream=stream)
+    min_equal = min(int(num_perm), max(0, math.ceil(float(min_jaccard) * int(num_perm))))
+    return minhash_clusters_device(h, keys, sig, min_equal, nsh, stream=stream) + (sig, nsh)
 
 
 def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,

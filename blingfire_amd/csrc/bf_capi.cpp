@@ -115,7 +115,7 @@ struct PinBuf {
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
 //                            calls on one handle).  Nobody keeps a list of entry points here: begin_launch() is called by the drivers they all go
 //                            through -- run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_minhash_device, run_i2t_host and
+//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_minhash_device, run_mhclust_device, run_i2t_host and
 //                            IdsToTextBatchDevice -- and by rows_call(), the prologue of every Rows...BatchDevice entry point (span cells, MLM mask,
 //                            MLM predictions, denoise) and of MinHashPairsBatchDevice.  The host forms reach
 //                            it through the Device drivers they call.  The fill passes of the two-pass calls keep the size pass's words.
@@ -219,6 +219,7 @@ struct Handle {
     DevBuf w_pkW, w_pkjmp[2], w_pkmark, w_pkmoff, w_pkf;         // IdsToPackedRowsBatch (bf_kernels.h PackedParams): W, the two jump arrays, the marks, their scan, the row starts
     DevBuf w_bkkey[2], w_bkval[2], w_bkcnt, w_bkbase;            // IdsToBucketedRowsBatch (bf_kernels.h BucketParams): the sort's records, a pass's digit counts, their scan
     DevBuf w_mhab;                                               // IdsToMinHashBatch (bf_kernels.h MinhashParams): a_i, b_i of the permutations, 4 KiB
+    DevBuf w_mhckey, w_mhcrep, w_mhcsize;                        // MinHashClustersBatchDevice (MhclustParams): the table of one band (key, rep), the members per root
     DevBuf w_cplead, w_cpfour, w_cpcnt, w_cpP;                  // Byte / CharToByteOffsetsBatchDevice (bf_kernels.h CharposParams): the two masks, the weights, P -- 28 bytes per 64 bytes of text
     DevBuf t_kind;                                               // unit-form lexers: what a walk that starts on each class does (bf_wave.h)
     bool lex_stats = false;                                      // BF_LEX_STATS=1 at LoadModel: instrumented kernel instances (experiments)
@@ -1850,6 +1851,40 @@ int64_t run_minhash_host(Handle *h, const int32_t *ids, const int64_t *id_off, i
                                   nshingles_out ? h->w_starts.as<int32_t>() : nullptr, s); });
 }
 
+// MinHashClustersBatchDevice (bf_kernels_mhclust.hip).  Workspaces: the table of one band, T = 2 * nseq + 64 slots of 12 bytes (key, rep), and the
+// members per root, 4 bytes per sequence: 28 bytes per sequence and 768 beyond.  The two counts are accumulated in the caller's d_counts_out.
+bool reserve_mhclust_workspaces(Handle *h, int64_t nseq)
+{
+    const size_t T = (size_t)mhclust_slots(nseq);
+    return h->w_mhckey.reserve(T * 8) && h->w_mhcrep.reserve(T * 4) && h->w_mhcsize.reserve((size_t)nseq * 4 + 16);
+}
+
+// begin, then clear / insert / link per band over the one table, then flatten and -- when size is taken -- sizes.  The launches depend on nseq,
+// bands and on which outputs are taken, never on the data.  The argument checks are the entry point's: nothing is refused here.
+int run_mhclust_device(Handle *h, const int32_t *d_sig, int num_perm, const int64_t *d_keys, int bands, int64_t nseq, const int32_t *d_nshingles, int min_equal,
+                       int32_t *d_label, uint8_t *d_keep, int32_t *d_size, int64_t *d_counts, hipStream_t s)
+{
+    if (!reserve_mhclust_workspaces(h, nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    MhclustParams p;
+    p.sig = (const uint32_t *)d_sig; p.H = num_perm; p.keys = d_keys; p.B = bands; p.nseq = nseq; p.nshingles = d_nshingles; p.min_equal = min_equal;
+    p.tkey = h->w_mhckey.as<uint64_t>(); p.trep = h->w_mhcrep.as<int32_t>(); p.T = mhclust_slots(nseq); p.sizes = h->w_mhcsize.as<int32_t>();
+    p.label = d_label; p.keep = d_keep; p.size = d_size; p.counts = (unsigned long long *)d_counts;
+    // the events BfLastKernelMs reads: [0] begin, [1] and [5] the bands (clear, insert, link of each), [2] nothing, [3] flatten and sizes
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    launch_mhclust_begin(p, s);
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    if (nseq > 0) for (int band = 0; band < bands; ++band) launch_mhclust_band(p, band, s);
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    if (nseq > 0) launch_mhclust_finish(p, s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "MinHashClusters kernels") ? 0 : BF_E_DEVICE;
+}
+
 // IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
 // outputs the caller takes -- the fill.  The launches depend on nseq and on which outputs are taken, never on the data; the workspaces are the
 // first three of the packed stage (reserve_packed_workspaces): nothing here is sized by the row count.
@@ -2836,6 +2871,18 @@ int MinHashPairsBatchDevice(void *p, const int32_t *d_sig, int num_perm, int64_t
         launch_minhash_pairs(MinhashPairsParams{(const uint32_t *)d_sig, num_perm, nseq, d_pairs, npairs, d_equal_out, &h->misc()->status}, s); });
 }
 
+/* ---- additive: clusters of near-duplicates from the band keys (bf_mhclust.h): a table per band, verified links, union-find in d_label_out */
+int MinHashClustersBatchDevice(void *p, const int32_t *d_sig, int num_perm, const int64_t *d_band_keys, int bands, int64_t nseq, const int32_t *d_nshingles,
+                               int min_equal, int flags, int32_t *d_label_out, uint8_t *d_keep_out, int32_t *d_size_out, int64_t *d_counts_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!h || !mhclust_spec(num_perm, bands, nseq, min_equal, flags) || !d_counts_out) return BF_E_ARG;
+    if (nseq > 0 && (!d_band_keys || !d_label_out || (min_equal > 0 && !d_sig))) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    return run_mhclust_device(h, d_sig, num_perm, d_band_keys, bands, nseq, d_nshingles, min_equal, d_label_out, d_keep_out, d_size_out, d_counts_out, (hipStream_t)stream);
+}
+
 /* ---- additive: packed rows with companion planes (k_packed_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */
 int IdsToPackedRowsPlanesBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int row_len, int cls_id, int sep_id,
                                      int pad_id, int flags, int32_t *d_rows_out, int32_t *d_seg_out, int32_t *d_pos_out, int32_t *d_row_first_seq_out, int64_t rows_cap,
@@ -3013,6 +3060,7 @@ int BfReserve(void *p, int64_t max_docs, int64_t max_bytes, int want_offsets)
     if (!reserve_packed_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToPackedRowsBatchDevice, any handle
     if (!reserve_bucket_workspaces(h, max_docs)) return BF_E_DEVICE;                                 // IdsToBucketedRowsBatchDevice, any handle
     if (!reserve_minhash_workspaces(h, max_docs)) return BF_E_DEVICE;                                // IdsToMinHashBatchDevice, any handle
+    if (!reserve_mhclust_workspaces(h, max_docs)) return BF_E_DEVICE;                                // MinHashClustersBatchDevice, any handle
     if (!reserve_charpos_workspaces(h, max_bytes)) return BF_E_DEVICE;                               // Byte / CharToByteOffsetsBatchDevice, any handle: sized by the text alone
     if (h->m.kind == KIND_I2W) return 0;                                                            // (nothing else of such a handle takes batches of documents)
     if (h->m.w2h_ready && !reserve_w2h_workspaces(h, max_docs, max_bytes)) return BF_E_DEVICE;      // WordHyphenationBatchDevice: documents = words

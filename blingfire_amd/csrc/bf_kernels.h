@@ -15,6 +15,7 @@
 #include "bf_bucket.h"
 #include "bf_stream.h"
 #include "bf_minhash.h"
+#include "bf_mhclust.h"
 #include "bf_mlm.h"
 #include "bf_denoise.h"
 #include "bf_charpos.h"
@@ -455,6 +456,20 @@ void launch_minhash_bands(const MinhashParams &p, hipStream_t s);               
 // MinHashPairsBatchDevice: the equal slots of two signature rows
 struct MinhashPairsParams { const uint32_t *sig; int H; int64_t nseq; const int64_t *pairs; int64_t npairs; int32_t *equal; int *status; };
 void launch_minhash_pairs(const MinhashPairsParams &p, hipStream_t s);
+// MinHashClustersBatchDevice (additive; bf_mhclust.h has the lane code and the split, bf_kernels_mhclust.hip the kernels): band keys -> the
+// connected components of the candidate graph.  The union-find lives in label; the two counts are accumulated in counts itself.
+struct MhclustParams {
+    const uint32_t *sig; int H;                  // [nseq, H]; NULL with min_equal == 0
+    const int64_t *keys; int B;                  // [nseq, B]
+    int64_t nseq; const int32_t *nshingles;      // [nseq] or NULL: every sequence is live
+    int min_equal;
+    uint64_t *tkey; int32_t *trep; int64_t T;    // the table of one band: T = mhclust_slots(nseq)
+    int32_t *sizes;                              // [nseq] members per root (workspace)
+    int32_t *label; uint8_t *keep; int32_t *size; unsigned long long *counts;      // keep, size: or NULL
+};
+void launch_mhclust_begin(const MhclustParams &p, hipStream_t s);               // label[q] = q, the sizes and the two counts to 0
+void launch_mhclust_band(const MhclustParams &p, int band, hipStream_t s);      // clear, insert, link: the table of one band and its edges
+void launch_mhclust_finish(const MhclustParams &p, hipStream_t s);              // flatten (label, keep, the cluster count), then size when taken
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

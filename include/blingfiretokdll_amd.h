@@ -592,7 +592,7 @@ BF_API int64_t IdsToBucketedRowsBatch(void *ModelPtr, const int32_t *ids, const 
  * Host form: stages the ids like IdsToRowsBatch (id_offsets[0] < 0 = BF_E_ARG) and returns nseq.  With sig_out NULL it is a query that fills
  * nshingles_out alone (band_keys_out without sig_out is BF_E_ARG); otherwise nseq > sig_cap returns BF_E_CAPACITY with nshingles_out complete and
  * nothing else written.
- * Not here: shingles of text or bytes; grouping candidates into clusters; sharding; H > 256. */
+ * Not here: shingles of text or bytes; sharding; H > 256.  (Grouping candidates into clusters: MinHashClustersBatchDevice below.) */
 BF_API int IdsToMinHashBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
                             int shingle, int num_perm, int band_rows, uint64_t seed, int flags,
                             int32_t *d_sig_out, int64_t sig_cap, int64_t *d_band_keys_out, int32_t *d_nshingles_out, void *stream);
@@ -607,6 +607,35 @@ BF_API int64_t IdsToMinHashBatch(void *ModelPtr, const int32_t *ids, const int64
  * or, with nseq > 0, a NULL d_sig.  Enqueues one kernel on `stream`, allocates nothing, reads nothing back; returns 0 or BF_E_*. */
 BF_API int MinHashPairsBatchDevice(void *ModelPtr, const int32_t *d_sig, int num_perm, int64_t nseq, const int64_t *d_pairs, int64_t npairs,
                             int32_t *d_equal_out, void *stream);
+
+/* additive (no counterpart in the reference; this comment is the specification): CLUSTERS of near-duplicates from the band keys -- the step
+ * behind IdsToMinHashBatchDevice: for every sequence, which cluster it belongs to and whether to keep it.  Integer-only, so bit-exact by
+ * specification.  d_band_keys = int64 [nseq, bands], d_sig = int32 [nseq, num_perm], both on the device (IdsToMinHashBatchDevice's outputs as
+ * they are); d_nshingles = int32 [nseq] or NULL.
+ * live(q) holds when d_nshingles == NULL or d_nshingles[q] > 0 (the signature of an empty sequence is all ones: without this rule all empty
+ * documents would form one cluster).  For a live q and a band b, f(q, b) = the smallest live q' with key[q'][b] == key[q][b].  Keys are
+ * compared column by column only -- equal values in different bands mean nothing -- and every 64-bit value is a key, 0, -1 and INT64_MIN
+ * included.  (q, b) is a CANDIDATE when f(q, b) != q.  A candidate is an EDGE q -- f when min_equal == 0, or when the number of i < num_perm
+ * with sig[q][i] == sig[f][i] (MinHashPairsBatchDevice's count) is at least min_equal.  A member is checked against its band bucket's SMALLEST
+ * member, not against every member: with min_equal == 0 the components equal those of all pairs; with min_equal > 0 this rule IS the
+ * specification (two members that would pass against each other, but not against the smallest, are not joined by that band).
+ * Clusters are the connected components over 0 .. nseq - 1; a sequence that is not live is its own cluster.  d_label_out[q] (int32) = the
+ * smallest index of q's component; d_keep_out[q] (uint8, may be NULL) = (label[q] == q); d_size_out[q] (int32, may be NULL) = the members of
+ * q's component; d_counts_out (int64 [2]) = {the number of clusters, the number of candidates (q, b)}.  All of it depends on the inputs only.
+ * BF_E_ARG for num_perm outside 1 .. 256, bands outside 1 .. 256, min_equal outside 0 .. num_perm, flags != 0 (reserved), nseq < 0 or
+ * nseq >= INT32_MAX, a NULL ModelPtr (any live handle of any kind serves: the model is not consulted), a NULL d_counts_out, and with nseq > 0 a
+ * NULL d_band_keys or d_label_out or, while min_equal > 0, a NULL d_sig.  A refused call touches neither the device nor the status word.
+ * nseq = 0 writes counts = {0, 0}.  The call clears the status word (it sets no bit of its own), enqueues on `stream` (a hipStream_t), does not
+ * synchronise, reads nothing back and returns 0 or BF_E_*.  The kernels it launches -- one to begin, three per band (clear, insert and link over
+ * one hash table, reused band after band), one or two to finish -- depend on nseq, bands, num_perm and on which outputs are taken, never on the
+ * data.  After BfReserve(h, max_docs >= nseq, ...) it allocates nothing, the first call included: its workspaces are that table (2 * nseq + 64
+ * slots of 12 bytes) and a member count per sequence, 28 bytes per sequence.  The table keeps the minimum of the sequences that arrive at a
+ * key, and the union-find in d_label_out hooks the larger root under the smaller: both are independent of the order of arrival, so the output
+ * is byte-identical from run to run.
+ * Not here: a host form; merging with the labels of an earlier batch; all-pairs verification; sharding. */
+BF_API int MinHashClustersBatchDevice(void *ModelPtr, const int32_t *d_sig, int num_perm, const int64_t *d_band_keys, int bands,
+                                      int64_t nseq, const int32_t *d_nshingles, int min_equal, int flags,
+                                      int32_t *d_label_out, uint8_t *d_keep_out, int32_t *d_size_out, int64_t *d_counts_out, void *stream);
 
 /* additive (no counterpart in the reference; this comment is the specification): STREAM rows -- "concatenate and chunk", the input of causal-LM
  * pretraining: every sequence closed by its specials, all of them laid end to end, the stream cut into rows of exactly row_len cells, with
@@ -803,12 +832,14 @@ BF_API int DictGetInfoBatchDevice(void *ModelPtr, const int32_t *d_keys, const i
  * [4] total, [5] the scatter kernel of the last pass alone (with max_len <= 255, one pass, that is every scatter kernel there is).
  * After IdsToMinHashBatchDevice: [0] parameters and initialisation (a_i, b_i, lengths, their scan, the all-ones rows), [1] the signature kernel,
  * [3] the band keys, [4] total ([2] is 0, [5] equals [1]).
+ * After MinHashClustersBatchDevice: [0] the begin kernel, [1] the bands (clear, insert and link of each), [3] flatten and sizes, [4] total
+ * ([2] is 0, [5] equals [1]).
  * Returns the number of values written, or a negative error. */
 BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
  * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, bucketed, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
- * and CharToByteOffsetsBatchDevice, IdsToMinHashBatch, IdsToMinHashBatchDevice and MinHashPairsBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
+ * and CharToByteOffsetsBatchDevice, IdsToMinHashBatch, IdsToMinHashBatchDevice, MinHashPairsBatchDevice and MinHashClustersBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
@@ -841,7 +872,7 @@ BF_API int BfModelKind(void *ModelPtr);
  * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
  * bound).  IdsToBucketedRowsBatchDevice borrows the packed stage's workspaces and adds its sort's: 17.5 bytes per sequence (two key and two
  * value arrays, and 12 bytes of digit counts per 8 sequences), on every kind of handle.  IdsToMinHashBatchDevice borrows the packed stage's
- * lengths, block sums and W and adds 4096 bytes for the parameters of its permutations, on every kind of handle; MinHashPairsBatchDevice has no workspace.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
+ * lengths, block sums and W and adds 4096 bytes for the parameters of its permutations, on every kind of handle; MinHashPairsBatchDevice has no workspace.  MinHashClustersBatchDevice has the hash table of one band and a member count per sequence: 28 bytes per sequence, on every kind of handle.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
  * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
  * Every kind of handle also gets the index of ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice, sized from max_bytes alone (28 bytes per
  * 64 bytes of text, and the scan's block sums for that many chunks): after that the two calls allocate nothing, the first one included.
