@@ -88,6 +88,9 @@ _SIGNATURES = {
     "MinHashPairsBatchDevice": (_I, [_P, _P, _I, _L, _P, _L, _P, _P]),
     # clusters: sig, H, band keys, bands, nseq, nshingles, min_equal, flags; label, keep, size, counts; stream
     "MinHashClustersBatchDevice": (_I, [_P, _P, _I, _P, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P]),
+    # n-gram sets: ids, their length, offsets, nseq; ngram, seed, flags, table, slots; counts (set) or ngrams, hits, covered, mask (overlap); stream
+    "IdsToNgramSetBatchDevice": (_I, [_P, _P, _L, _P, _L, _I, c_uint64, _I, _P, _L, _P, _P]),
+    "IdsNgramOverlapBatchDevice": (_I, [_P, _P, _L, _P, _L, _I, c_uint64, _I, _P, _L, _P, _P, _P, _P, _P]),
     "RowsSpanCellsBatchDevice": (_I, [_P, _P, _P, _I, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P]),
     "RowsMlmMaskBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 5 + [_I, _P] + [c_double] * 3 + [_I] * 4 + [c_uint64, c_uint32, _P, _P, _P]),
     "RowsDenoiseBatchDevice": (_I, [_P, _P, _I, _L] + [_P] * 3 + [_I, _P, c_double] + [_I] * 8 + [c_uint64, c_uint32] + [_I, _P, _P, _P] * 2 + [_P, _P]),
@@ -1219,6 +1222,70 @@ def encode_dedup_batch_device(h, d_text, d_doc_off, max_len, num_perm=128, shing
     sig, keys, nsh = ids_to_minhash_batch_device(h, d_ids, d_id_off, num_perm, shingle, band_rows, seed, stream=stream)
     min_equal = min(int(num_perm), max(0, math.ceil(float(min_jaccard) * int(num_perm))))
     return minhash_clusters_device(h, keys, sig, min_equal, nsh, stream=stream) + (sig, nsh)
+
+
+def _ngram_table(table, dev):
+    """the set as the library takes it: a contiguous torch.int64 tensor on `dev` (the bit patterns of uint64 slots) of at least two slots"""
+    import torch
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int64 or not table.is_contiguous() or table.device != dev or table.numel() < 2:
+        raise ValueError("table must be a contiguous torch.int64 tensor of at least 2 slots on %s" % dev)
+    return table
+
+
+def ngram_set_device(h, d_ids, d_id_off, n=13, seed=0, table=None, slots=None, clear=None, stream=None):
+    """n-grams of ragged ids into a SET that outlives the call (IdsToNgramSetBatchDevice; the header has the specification): torch int32 ids +
+    int64 offsets on one GPU (text_to_ids_batch_device's results as they are) -> (table, counts).  table = the set, an opaque int64 tensor of
+    hash slots: None allocates one of `slots` (default 2 * ids + 64) and clears it; a table from an earlier call is added to (clear=True
+    empties it first), so a set is built over as many batches as it takes and may hold several n.  counts = int64[3] on the device:
+    {n-grams read, fingerprints newly stored, n-grams that found no slot}; a non-zero third count (BfLastStatus bit 0) means the table is too
+    small.  Enqueued on torch's current stream (or `stream`); nothing is read back."""
+    import torch
+    name = "IdsToNgramSetBatchDevice"
+    dev = d_ids.device
+    d_ids = _dev_i32(d_ids, dev, "ngram_set_device: d_ids")
+    if table is None:
+        table = torch.empty(int(slots) if slots is not None else 2 * d_ids.numel() + 64, dtype=torch.int64, device=dev)
+        clear = True if clear is None else clear
+    elif slots is not None and int(slots) != table.numel():
+        raise ValueError("ngram_set_device: slots is the size of a table the call allocates; the table given has %d" % table.numel())
+    table = _ngram_table(table, dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+    r = getattr(lib(), name)(*_head(h, d_id_off.numel() - 1, (d_ids, d_id_off)), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if clear else 0, table.data_ptr(),
+                             table.numel(), counts.data_ptr(), _stream_arg(stream, dev))
+    _check(name, r, r == 0)
+    return table, counts
+
+
+def ngram_overlap_device(h, d_ids, d_id_off, table, n=13, seed=0, return_mask=False, stream=None):
+    """exact n-gram overlap of ragged ids with a set built by ngram_set_device, with the same n and seed (IdsNgramOverlapBatchDevice) ->
+    (ngrams, hits, covered[, mask]): int32[nseq] each -- the n-grams of a sequence, how many of them are in the set, and how many of its ids
+    lie inside one that is (covered / length is the contaminated-token ratio to threshold) -- and with return_mask a bool tensor parallel to
+    d_ids, True at those ids (False where no sequence holds the cell).  Enqueued on torch's current stream (or `stream`); nothing is read back."""
+    import torch
+    name = "IdsNgramOverlapBatchDevice"
+    dev = d_ids.device
+    d_ids, table = _dev_i32(d_ids, dev, "ngram_overlap_device: d_ids"), _ngram_table(table, dev)
+    nseq = d_id_off.numel() - 1
+    outs = [torch.empty(nseq, dtype=torch.int32, device=dev) for _ in range(3)]
+    mask = torch.zeros(d_ids.numel(), dtype=torch.uint8, device=dev) if return_mask else None
+    r = getattr(lib(), name)(*_head(h, nseq, (d_ids, d_id_off)), int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, 0, table.data_ptr(), table.numel(),
+                             *[o.data_ptr() for o in outs], _dev_addr(mask), _stream_arg(stream, dev))
+    _check(name, r, r == 0)
+    return (*outs, mask.view(torch.bool)) if return_mask else tuple(outs)
+
+
+def encode_ngram_set_batch_device(h, d_text, d_doc_off, max_len, n=13, seed=0, table=None, unk=0):
+    """Text in HBM -> the n-grams of its ids in a set, nothing on the host: text_to_ids_batch_device (every document tokenised up to max_len ids)
+    and ngram_set_device on one stream.  Returns what ngram_set_device returns."""
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_len), unk)
+    return ngram_set_device(h, d_ids, d_id_off, n, seed, table)
+
+
+def encode_ngram_overlap_batch_device(h, d_text, d_doc_off, max_len, table, n=13, seed=0, return_mask=False, unk=0):
+    """Text in HBM -> its n-gram overlap with a set, nothing on the host: text_to_ids_batch_device and ngram_overlap_device on one stream.
+    Returns (ngrams, hits, covered[, mask], ids, id_offsets): the mask is parallel to ids."""
+    d_ids, d_id_off = text_to_ids_batch_device(h, d_text, d_doc_off, int(max_len), unk)
+    return ngram_overlap_device(h, d_ids, d_id_off, table, n, seed, return_mask) + (d_ids, d_id_off)
 
 
 def ids_to_stream_rows_batch(h, ids, id_off, L, bos_id=None, eos_id=None, pad_id=0, ignore_label=-100, drop_last=False, pos_from_row=False,

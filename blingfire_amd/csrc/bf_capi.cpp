@@ -115,7 +115,7 @@ struct PinBuf {
 //                            words or not -- the status word is the call's own (BfLastStatus; tests/test_gpu_call_order.py walks every ordered pair of
 //                            calls on one handle).  Nobody keeps a list of entry points here: begin_launch() is called by the drivers they all go
 //                            through -- run_device (TextToIds, words, sentences), the size passes of run_w2h_device and run_dict_device,
-//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_minhash_device, run_mhclust_device, run_i2t_host and
+//                            run_row_stage_device, run_packed_device, run_stream_device, run_charpos_device, run_minhash_device, run_mhclust_device, run_ngram_device, run_i2t_host and
 //                            IdsToTextBatchDevice -- and by rows_call(), the prologue of every Rows...BatchDevice entry point (span cells, MLM mask,
 //                            MLM predictions, denoise) and of MinHashPairsBatchDevice.  The host forms reach
 //                            it through the Device drivers they call.  The fill passes of the two-pass calls keep the size pass's words.
@@ -1885,6 +1885,36 @@ int run_mhclust_device(Handle *h, const int32_t *d_sig, int num_perm, const int6
     return hip_ok(hipGetLastError(), "MinHashClusters kernels") ? 0 : BF_E_DEVICE;
 }
 
+// IdsToNgramSetBatchDevice and IdsNgramOverlapBatchDevice (bf_kernels_ngram.hip).  No workspace of their own: the lengths, their block sums and W
+// are the packed stage's, as in run_minhash_device; the table is the caller's.  set = the set call (counts, clear) -- begin, lengths, scan, the
+// insert kernel; else the overlap call -- lengths (and ngrams), then, when hits, covered or the mask are taken, scan, the zero rows and the
+// probe kernel.  The launches depend on nseq, ids_len and on which outputs are taken, never on the data.  The argument checks are the entry
+// points': nothing is refused here.
+int run_ngram_device(Handle *h, NgramParams p, bool set, hipStream_t s)
+{
+    if (!reserve_packed_workspaces(h, p.nseq)) return BF_E_DEVICE;
+    if (!begin_launch(h, s)) return BF_E_DEVICE;
+    p.status = &h->misc()->status; p.lens = h->w_counts.as<int32_t>(); p.W = h->w_pkW.as<int64_t>(); p.bpow = ngram_pow(p.n);
+    const bool tiles = p.nseq > 0 && (set || p.hits || p.covered || p.mask);
+    // the events BfLastKernelMs reads: [0] begin, lengths, scan and the zero rows, [1] and [5] the tile kernel, [2] and [3] nothing
+    (void)hipEventRecord(h->ev[EV_BEGIN], s);
+    if (set) launch_ngram_begin(p, s);
+    if (p.nseq > 0) launch_ngram_lens(p, s);
+    if (tiles) {
+        scan_counts(h, p.nseq, h->w_pkW.as<int64_t>(), s);
+        if (p.hits || p.covered) launch_ngram_init(p, s);
+    }
+    (void)hipEventRecord(h->ev[EV_PREP], s);
+    (void)hipEventRecord(h->ev[EV_DOM0], s);
+    if (tiles && p.ids_len > 0) { if (set) launch_ngram_set(p, s); else launch_ngram_overlap(p, s); }
+    (void)hipEventRecord(h->ev[EV_DOM1], s);
+    (void)hipEventRecord(h->ev[EV_TOK], s);
+    (void)hipEventRecord(h->ev[EV_SCAN], s);
+    (void)hipEventRecord(h->ev[EV_COMPACT], s);
+    h->ev_valid = true;
+    return hip_ok(hipGetLastError(), "Ngram kernels") ? 0 : BF_E_DEVICE;
+}
+
 // IdsToStreamRowsBatch on device buffers (bf_kernels_stream.hip): widths, scan, the per-sequence outputs and the counts, then -- for the row
 // outputs the caller takes -- the fill.  The launches depend on nseq and on which outputs are taken, never on the data; the workspaces are the
 // first three of the packed stage (reserve_packed_workspaces): nothing here is sized by the row count.
@@ -2881,6 +2911,40 @@ int MinHashClustersBatchDevice(void *p, const int32_t *d_sig, int num_perm, cons
     std::lock_guard<std::mutex> lock(h->mu);
     DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
     return run_mhclust_device(h, d_sig, num_perm, d_band_keys, bands, nseq, d_nshingles, min_equal, d_label_out, d_keep_out, d_size_out, d_counts_out, (hipStream_t)stream);
+}
+
+/* ---- additive: exact n-gram overlap against a set that outlives a call (bf_ngram.h): fingerprints into, and against, a caller-owned table */
+static bool ngram_args_ok(Handle *h, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int ngram, const uint64_t *d_table, int64_t table_slots)
+{
+    return h && ngram_spec(ngram, table_slots, nseq, ids_len) && d_table && d_id_offsets && !(ids_len > 0 && !d_ids);
+}
+
+int IdsToNgramSetBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int ngram, uint64_t seed, int flags,
+                             uint64_t *d_table, int64_t table_slots, int64_t *d_counts_out, void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!ngram_args_ok(h, d_ids, ids_len, d_id_offsets, nseq, ngram, d_table, table_slots) || (flags & ~NGRAM_SET_CLEAR) != 0 || !d_counts_out) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    NgramParams q{};
+    q.ids = d_ids; q.ids_len = ids_len; q.id_off = d_id_offsets; q.nseq = nseq; q.n = ngram; q.seed = seed; q.table = d_table; q.slots = table_slots;
+    q.counts = (unsigned long long *)d_counts_out; q.clear = (flags & NGRAM_SET_CLEAR) ? 1 : 0;
+    return run_ngram_device(h, q, true, (hipStream_t)stream);
+}
+
+int IdsNgramOverlapBatchDevice(void *p, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq, int ngram, uint64_t seed, int flags,
+                               const uint64_t *d_table, int64_t table_slots, int32_t *d_ngrams_out, int32_t *d_hits_out, int32_t *d_covered_out, uint8_t *d_mask_out,
+                               void *stream)
+{
+    Handle *h = as_handle(p);
+    if (!ngram_args_ok(h, d_ids, ids_len, d_id_offsets, nseq, ngram, d_table, table_slots) || flags != 0) return BF_E_ARG;
+    if (!d_ngrams_out && !d_hits_out && !d_covered_out && !d_mask_out) return BF_E_ARG;
+    std::lock_guard<std::mutex> lock(h->mu);
+    DeviceGuard dg(h->device); if (!dg.ok) return BF_E_DEVICE;
+    NgramParams q{};
+    q.ids = d_ids; q.ids_len = ids_len; q.id_off = d_id_offsets; q.nseq = nseq; q.n = ngram; q.seed = seed; q.table = (uint64_t *)d_table; q.slots = table_slots;
+    q.ngrams = d_ngrams_out; q.hits = d_hits_out; q.covered = d_covered_out; q.mask = d_mask_out;
+    return run_ngram_device(h, q, false, (hipStream_t)stream);
 }
 
 /* ---- additive: packed rows with companion planes (k_packed_planes): up to BF_ROWS_MAX_PLANES int32 arrays parallel to the ids, in the rows' layout */

@@ -16,6 +16,7 @@
 #include "bf_stream.h"
 #include "bf_minhash.h"
 #include "bf_mhclust.h"
+#include "bf_ngram.h"
 #include "bf_mlm.h"
 #include "bf_denoise.h"
 #include "bf_charpos.h"
@@ -470,6 +471,21 @@ struct MhclustParams {
 void launch_mhclust_begin(const MhclustParams &p, hipStream_t s);               // label[q] = q, the sizes and the two counts to 0
 void launch_mhclust_band(const MhclustParams &p, int band, hipStream_t s);      // clear, insert, link: the table of one band and its edges
 void launch_mhclust_finish(const MhclustParams &p, hipStream_t s);              // flatten (label, keep, the cluster count), then size when taken
+// IdsToNgramSetBatchDevice / IdsNgramOverlapBatchDevice (additive; bf_ngram.h has the lane code and the split, bf_kernels_ngram.hip the kernels):
+// n-gram fingerprints of ragged ids into, and against, a caller-owned hash table.  The lengths and W are the packed stage's workspaces.
+struct NgramParams {
+    const int32_t *ids; int64_t ids_len; const int64_t *id_off; int64_t nseq; int *status;
+    int32_t *lens; const int64_t *W;             // [nseq] the ids of a sequence (0 for a bad range); [nseq + 1] their exclusive scan
+    int n; uint64_t seed, bpow;                  // bpow = B^(n-1) (ngram_pow)
+    uint64_t *table; int64_t slots;              // the overlap call only reads it
+    unsigned long long *counts; int clear;       // the set call: [3] read, stored, no slot; the table is zeroed first
+    int32_t *ngrams, *hits, *covered; uint8_t *mask;      // the overlap call: [nseq] each or NULL; indexed like ids or NULL
+};
+void launch_ngram_begin(const NgramParams &p, hipStream_t s);                   // the set call: the counts to 0, the table when cleared
+void launch_ngram_lens(const NgramParams &p, hipStream_t s);                    // lens, ngrams, status bit 3
+void launch_ngram_init(const NgramParams &p, hipStream_t s);                    // behind the scan: 0 into the rows that take atomic adds
+void launch_ngram_set(const NgramParams &p, hipStream_t s);                     // inserts, a tile of the id stream per wave; status bit 0
+void launch_ngram_overlap(const NgramParams &p, hipStream_t s);                 // hits, covered, mask, a tile of the id stream per wave
 void launch_compact(const CompactParams &p, hipStream_t s);
 int scan_nblocks(int64_t ndocs);
 

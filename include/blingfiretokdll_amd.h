@@ -637,6 +637,46 @@ BF_API int MinHashClustersBatchDevice(void *ModelPtr, const int32_t *d_sig, int 
                                       int64_t nseq, const int32_t *d_nshingles, int min_equal, int flags,
                                       int32_t *d_label_out, uint8_t *d_keep_out, int32_t *d_size_out, int64_t *d_counts_out, void *stream);
 
+/* additive (no counterpart in the reference; this comment is the specification): exact N-GRAM OVERLAP against a set that outlives a call --
+ * benchmark decontamination, block lists, filtering a batch against one already seen -- on the ids the tokenizer calls leave on the device.
+ * IdsToNgramSetBatchDevice adds the n-grams of a batch to a set; IdsNgramOverlapBatchDevice says, per sequence, how many of its n-grams are in
+ * the set and how many of its ids they cover.  Integer-only, so bit-exact by specification.  All arithmetic is uint64 and wraps; an id enters
+ * as (uint32)id.
+ * Sequences are read as in IdsToMinHashBatchDevice: a range outside [0, ids_len] or with decreasing offsets, or a sequence of more than
+ * INT32_MAX - 2 ids, is read as empty and sets BfLastStatus bit 3.
+ * N-grams.  A sequence of len ids has max(0, len - n + 1) n-grams, one at every start p over t[p .. p + n), n = ngram, 1 <= n <= 64.  A sequence
+ * shorter than n has none (unlike MinHash shingles).
+ * Fingerprint.  m(id) = fmix64(seed ^ (((uint64)(uint32)id + 1) * 0x9E3779B97F4A7C15)), fmix64 the MurmurHash3 64-bit finalizer as above;
+ * P = 0, then for each id of the n-gram in order P = P * B + m(id) with B = 0x100000001B3; g = fmix64(P ^ ((uint64)n * 0xC2B2AE3D27D4EB4F)).
+ * A g of 0 is stored and looked up as 1, because 0 is the empty mark.  n is part of g, so one table may hold several n.
+ * Table.  Caller-owned uint64 d_table[table_slots] on the device, table_slots >= 2, 0 = empty.  The home slot of g is the high 64 bits of
+ * g * table_slots; probing is linear, wraps at the end and takes at most table_slots steps; insert is a 64-bit compare-and-swap from 0, and an
+ * equal value found means already present.  Which slot a fingerprint ends in depends on the order of arrival; which fingerprints are members
+ * does not, while the table does not fill.  The bytes of the table are opaque; every output below is a function of the inputs alone.
+ * IdsToNgramSetBatchDevice.  flags bit 0 set: the table is zeroed first; clear: the n-grams are added to what is there, so a set can be built over
+ * several calls; any other bit is BF_E_ARG.  d_counts_out (int64 [3], required) = {n-grams read, fingerprints newly stored, n-grams that found
+ * no slot}.  A non-zero third count sets BfLastStatus bit 0; the set is then some subset of the n-grams and only "third count > 0" is specified.
+ * IdsNgramOverlapBatchDevice.  flags must be 0.  Each output is [nseq] and may be NULL, but at least one of the four must be taken:
+ * d_ngrams_out[q] = the n-gram count of q; d_hits_out[q] = the starts whose fingerprint is in the table; d_covered_out[q] = the ids of q that
+ * lie inside at least one hit n-gram (the "contaminated tokens"; covered / len is the ratio to threshold).  d_mask_out (uint8) is indexed like
+ * d_ids: 1 or 0 for every id of a well-formed sequence, other cells are not written (where ranges overlap a cell holds the answer of one of them).
+ * BF_E_ARG for ngram outside 1 .. 64, table_slots < 2, a NULL d_table, d_id_offsets or ModelPtr (any live handle of any kind serves: the model
+ * is not consulted), nseq < 0 or nseq > INT32_MAX, ids_len < 0, a NULL d_ids with ids_len > 0, a NULL d_counts_out.  A refused call touches
+ * neither the device nor the status word.  nseq = 0 is a valid call (the set call still zeroes the table when asked and writes its counts).
+ * Both calls clear the status word, enqueue on `stream` (a hipStream_t), do not synchronise, read nothing back and return 0 or BF_E_*.  The
+ * kernels they launch depend on the sizes and on which outputs are taken, never on the data.  They have no workspace of their own: the lengths
+ * and their scan are the packed stage's, so after BfReserve(h, max_docs >= nseq, ...) neither allocates, the first call included.  The ids of
+ * all sequences laid end to end are cut into tiles of 1024 positions and a wave takes a tile, 16 consecutive positions a lane, so the time of a
+ * batch does not follow its longest sequence; counts of a sequence that several lanes meet are combined with 32-bit atomic adds, which commute:
+ * the outputs are byte-identical from run to run.
+ * Not here: host forms; removal from a set; n-grams of bytes or text; sharding. */
+BF_API int IdsToNgramSetBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                                    int ngram, uint64_t seed, int flags, uint64_t *d_table, int64_t table_slots,
+                                    int64_t *d_counts_out, void *stream);
+BF_API int IdsNgramOverlapBatchDevice(void *ModelPtr, const int32_t *d_ids, int64_t ids_len, const int64_t *d_id_offsets, int64_t nseq,
+                                      int ngram, uint64_t seed, int flags, const uint64_t *d_table, int64_t table_slots,
+                                      int32_t *d_ngrams_out, int32_t *d_hits_out, int32_t *d_covered_out, uint8_t *d_mask_out, void *stream);
+
 /* additive (no counterpart in the reference; this comment is the specification): STREAM rows -- "concatenate and chunk", the input of causal-LM
  * pretraining: every sequence closed by its specials, all of them laid end to end, the stream cut into rows of exactly row_len cells, with
  * next-token labels, a segment plane and a position plane.  Where IdsToPackedRowsBatch truncates a sequence longer than a row and never splits
@@ -839,13 +879,13 @@ BF_API int BfLastKernelMs(void *ModelPtr, float *ms, int n);
 
 /* Status word of the last batch call on this handle (synchronises).  It is that call's OWN: every batch call that takes a handle -- the
  * tokenizer calls, words and sentences, the row, pair-row, plane, packed, stream, bucketed, span-cell, MLM and denoise calls, ByteToCharOffsetsBatchDevice
- * and CharToByteOffsetsBatchDevice, IdsToMinHashBatch, IdsToMinHashBatchDevice, MinHashPairsBatchDevice and MinHashClustersBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
+ * and CharToByteOffsetsBatchDevice, IdsToMinHashBatch, IdsToMinHashBatchDevice, MinHashPairsBatchDevice, MinHashClustersBatchDevice, IdsToNgramSetBatchDevice and IdsNgramOverlapBatchDevice, IdsToText, DictGetInfo and WordHyphenation, Device and host forms alike, and the single-document calls, which are batches of one -- clears the word when it begins,
  * on its stream, so nothing an earlier call reported survives it, whatever the order of the calls (tests/test_gpu_call_order.py runs every
  * ordered pair of them on one handle).  A call of the two-pass kind reports what its size pass found; a call that was refused with BF_E_ARG
  * or BF_E_UNSUPPORTED before it enqueued anything leaves the word alone.  NormalizeSpacesBatch and TextToHashesBatch take no handle and have
  * no status.
  * 0 = ok; bit 0 (1) = ids_cap / rows_cap overflow (RowsDenoiseBatchDevice: a row longer than enc_len / dec_len; IdsToBucketedRowsBatchDevice: cells
- * beyond cells_cap or batches beyond batches_cap of an output the caller takes; IdsToMinHashBatchDevice: sequences beyond sig_cap); bit 1 (2) and bit 4 (16) = an internal
+ * beyond cells_cap or batches beyond batches_cap of an output the caller takes; IdsToMinHashBatchDevice: sequences beyond sig_cap; IdsToNgramSetBatchDevice: an n-gram found no slot in the table); bit 1 (2) and bit 4 (16) = an internal
  * limit the load-time checks exclude was met (the results of the batch are not to be trusted; the host-buffer calls return
  * BF_E_INTERNAL); bit 2 (4) = IdsToText: a sequence held an id the model does not know and yields no text; bit 3 (8) = a document's byte
  * range was outside [0, total_bytes] (Device calls: see the precondition above) and was treated as empty (the row calls: an id range outside
@@ -872,7 +912,7 @@ BF_API int BfModelKind(void *ModelPtr);
  * there) and IdsToStreamRowsBatchDevice (the widths, block sums and W; nothing of it is sized by the row count, which max_docs does not
  * bound).  IdsToBucketedRowsBatchDevice borrows the packed stage's workspaces and adds its sort's: 17.5 bytes per sequence (two key and two
  * value arrays, and 12 bytes of digit counts per 8 sequences), on every kind of handle.  IdsToMinHashBatchDevice borrows the packed stage's
- * lengths, block sums and W and adds 4096 bytes for the parameters of its permutations, on every kind of handle; MinHashPairsBatchDevice has no workspace.  MinHashClustersBatchDevice has the hash table of one band and a member count per sequence: 28 bytes per sequence, on every kind of handle.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
+ * lengths, block sums and W and adds 4096 bytes for the parameters of its permutations, on every kind of handle; MinHashPairsBatchDevice has no workspace.  IdsToNgramSetBatchDevice and IdsNgramOverlapBatchDevice borrow the same lengths, block sums and W and add nothing (the table is the caller's).  MinHashClustersBatchDevice has the hash table of one band and a member count per sequence: 28 bytes per sequence, on every kind of handle.  RowsSpanCellsBatchDevice, RowsMlmMaskBatchDevice, RowsMlmPredictionsBatchDevice and RowsDenoiseBatchDevice have no workspace:
  * they allocate nothing on any handle, reserved or not.  (tests/test_gpu_reserve_contract.py counts the allocations around every one of these.)
  * Every kind of handle also gets the index of ByteToCharOffsetsBatchDevice / CharToByteOffsetsBatchDevice, sized from max_bytes alone (28 bytes per
  * 64 bytes of text, and the scan's block sums for that many chunks): after that the two calls allocate nothing, the first one included.
