@@ -1059,6 +1059,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     w.run((int)(blockIdx.x * 4) + wave_in_block(), (int)(gridDim.x * 4));
 }
 
+__device__ __forceinline__ int64_t uni64(int64_t v) { return (int64_t)(((uint64_t)wv::uni((uint32_t)((uint64_t)v >> 32)) << 32) | (uint64_t)wv::uni((uint32_t)v)); }
+
 // the words of the list (bf_flat_body.h wf_units): a wave takes batches of 64 * NU records, batch number = wave number + k * waves
 template <int WPE, int NU, bool STATS, bool OFFS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_wp_units(WfUnitParams p)
@@ -1070,15 +1072,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         lut[threadIdx.x] = wf_lut_value(cold, (int)threadIdx.x);
     }
     __syncthreads();
-    const int wave = (int)(blockIdx.x * 4) + wave_in_block(), nwaves = (int)(gridDim.x * 4);
+    const int wib = wave_in_block(), wave = (int)(blockIdx.x * 4) + wib, nwaves = (int)(gridDim.x * 4);
+    uint16_t *const cb = cbuf[wib];
     unsigned long long rounds = 0, batches = 0;
     for (int r = wave; r < p.nranges; r += nwaves) {
-        const int64_t dlo = p.range_doc[r], dhi = p.range_doc[r + 1];
+        // (what a range is made of is the same in every lane, but it is read with vector loads -- the kernel stores to memory -- and would stay in
+        // vector registers, two per value, for the whole range: that was what spilled)
+        const int64_t dlo = uni64(p.range_doc[r]), dhi = uni64(p.range_doc[r + 1]);
         if (dlo >= dhi) continue;
-        const int64_t b0 = p.doc_off[dlo], b1 = p.doc_off[dhi];
-        const unsigned long long nfast = (unsigned long long)p.wrec_cnt[2 * r], nslow = (unsigned long long)p.wrec_cnt[2 * r + 1];
+        const int64_t b0 = uni64(p.doc_off[dlo]), b1 = uni64(p.doc_off[dhi]);
+        const unsigned long long nfast = (unsigned long long)wv::uni(p.wrec_cnt[2 * r]), nslow = (unsigned long long)wv::uni(p.wrec_cnt[2 * r + 1]);
         const uint32_t *fl = p.wrec + 4 * ((b0 + (1 << WF_REC_SHIFT) - 1) >> WF_REC_SHIFT), *sl = p.wrec + 4 * ((b1 >> WF_REC_SHIFT) - (int64_t)nslow);       // (the second list grows down from the end: its order does not matter)
-        uint16_t *cb = cbuf[wave_in_block()];
         for (unsigned long long first = 0; first < nfast; first += 64 * NU) { wf_units<NU, STATS, 0, OFFS>(p, lut, cb, fl, b0, dlo, first, nfast, &rounds); ++batches; }
         for (unsigned long long first = 0; first < nslow; first += 64) { wf_units<1, STATS, 1, OFFS>(p, lut, cb, sl, b0, dlo, first, nslow, &rounds); wf_units<1, STATS, 2, OFFS>(p, lut, cb, sl, b0, dlo, first, nslow, &rounds); ++batches; }
     }
@@ -1117,11 +1121,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFFS ? 6 : 
     if (over) atomicOr(p.status, 1);
 }
 
+// workgroups of the shipped k_wp_flat that are resident on a CU (launch_wp_flat and wp_flat_ranges go by the same figure)
+static int wp_flat_per_cu()
+{
+    static int pc = 0;
+    return wave_program_per_cu(k_wp_flat<7, false>, pc);
+}
+
 int wp_flat_ranges(int64_t ndocs, int64_t total_bytes)
 {
-    // four ranges per resident wave, of at least 16 KB and at most WF_RANGE_MAX bytes
-    int64_t r = (int64_t)device_cus() * 32 * 4;
+    // WP_FLAT_RANGES_PER_WAVE ranges per resident wave of k_wp_flat (the waves take them from a counter: what is left over at the end is at most
+    // that fraction of a wave's share), fewer -- still whole rounds of the resident waves -- as long as that keeps a range at 16 KB; at least
+    // 16 KB and at most WF_RANGE_MAX bytes.  Swept on MI355X, 10 M documents of 512 bytes, ms per step: 4.57 per wave (32,768 ranges, what it was)
+    // 16.19, 8 per wave 15.98, 16 per wave 15.80, 32 per wave 15.92 (k_wp_flat still gains there, k_wp_units loses more: it walks a range's
+    // words in batches of 128, and the last batch of a range is a part of one)
+    constexpr int64_t WP_FLAT_RANGES_PER_WAVE = 16;
+    const int64_t waves = (int64_t)device_cus() * wp_flat_per_cu() * 4;
     const int64_t most = total_bytes / 16384 + 1, least = total_bytes / WF_RANGE_MAX + 1;
+    int64_t r = waves * WP_FLAT_RANGES_PER_WAVE;
+    while (r > most && r > waves) r /= 2;
     if (r > most) r = most;
     if (r < least) r = least;
     if (r > ndocs) r = ndocs;
@@ -1140,7 +1158,7 @@ template <int WPE>
 static void launch_wp_flat_wpe(const WfParams &p, int per_cu_override, hipStream_t s)
 {
     static int pc = 0;
-    int per_cu = wave_program_per_cu(k_wp_flat<WPE, false>, pc);
+    int per_cu = WPE == 7 ? wp_flat_per_cu() : wave_program_per_cu(k_wp_flat<WPE, false>, pc);
     if (per_cu_override > 0) per_cu = per_cu_override;
     const int64_t blocks = resident_blocks(per_cu, ((int64_t)p.nranges + 3) / 4);
     if (p.cold.stats) hipLaunchKernelGGL((k_wp_flat<WPE, true>), dim3((unsigned)blocks), dim3(256), 0, s, p);
